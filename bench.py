@@ -22,6 +22,14 @@ the part needs ~50 ms under load before its clock settles (the first dozen steps
 ranks with no collective (weak scaling: every GPU gets its own 16 M-pair batch); torch.distributed is only
 used for the barrier and the max-over-ranks of the elapsed time.
 
+A plain run sets up, warms up, times the K steps, writes the last step's results when ``--dump-outputs DIR`` is given
+(DIR/r1_results.npy, DIR/r2_results.npy for paired workloads, DIR/r1_barcode.npy for config 5: float32, one row per
+read, the columns of RESULT_DTYPE; the whole shard up to DUMP_ROWS reads, above that a fixed seeded sample of
+DUMP_ROWS rows in index order; rank 0's shard) and prints the line.  ``--full`` adds what takes work of its own
+behind the timed region: the host generator's head of the shard against the device's bytes, the batch-sized launch
+against piecewise launches, the HBM copy probe, ``cpu_baseline`` (and ``cpu_baseline_cutadapt``), the N > 1 parity
+gate and the tiers.
+
 One JSON line on rank 0, with
   roofline      algorithmic bytes (616 B/pair = 2 x (150 seq + 150 qual + 8 result)) per launch over the launch
                 duration, against the 8 TB/s HBM3E peak.  Pipelined form: the duration is the step time (the scan
@@ -34,7 +42,7 @@ One JSON line on rank 0, with
                 kernels) x 2 cycles (spec issue cost of a wave64 instruction on a SIMD-32) / (1024 SIMDs x the clock
                 measured in the counter passes x step time of THIS run), plus the same at this kernel's measured mix
                 ceiling (2.3 cycles) and the scan kernel's SQ_WAIT_INST_ANY / SQ_WAVE_CYCLES;
-  cpu_baseline  the CPU oracle (own scalar C restatement of the cutseq->cutadapt chain -- cutadapt itself is not
+  cpu_baseline  (--full) the CPU oracle (own scalar C restatement of the cutseq->cutadapt chain -- cutadapt itself is not
                 installable here; when it is, ``cpu_baseline_cutadapt`` times the real chain beside it) on this box's
                 host cores on a bounded sample of the same batch; the GPU results for that sample are compared
                 bit-for-bit while at it (``all_ranks_identical``).  With N > 1 every rank checks a 200 k-pair sample
@@ -70,6 +78,8 @@ N_SIMD, MAX_CLOCK_HZ = 1024, 2.4e9  # 256 CUs x 4 SIMDs, max clock (MI355X_MICRO
 VALU_CYCLES_SPEC, VALU_CYCLES_MIX = 2.0, 2.3
 PARITY_SAMPLE = 200_000  # pairs every rank checks against the oracle when world > 1
 GEN_PIECE = 16_000_000   # pairs generated on the host and uploaded at a time
+DUMP_ROWS = 1 << 20      # reads per mate written by --dump-outputs (2 mates x 5 float32 columns: 40 MB)
+DUMP_SEED = 0x5EED       # the sample of a shard larger than DUMP_ROWS
 
 
 def parse_args():
@@ -77,22 +87,46 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)  # (the last step's resolve kernel has no scan kernel to hide under: 1/K of it per step)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and side measurements behind the timed region (host head comparison, "
+                         "piecewise launches, copy probe, CPU baseline, N > 1 parity gate, tiers)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (float32; a fixed sample of 2^20 reads per mate "
+                         "when the batch is larger)")
     ap.add_argument("--pairs", type=int, default=100_000_000,
                     help="read pairs per step = the resident batch (default: BASELINE config 3's 100 M pairs, 61 GB of HBM)")
     ap.add_argument("--workload", choices=["config3", "config2", "config4", "config5"], default="config3")
-    ap.add_argument("--cpu-sample", type=int, default=2_000_000, help="pairs timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=2_000_000, help="--full: pairs timed on the CPU oracle (0 = skip)")
     ap.add_argument("--no-filter", action="store_true", help="ablation: exact DP on every read")
     ap.add_argument("--serial", action="store_true", help="both kernels of a step on one stream (no overlap between steps)")
-    ap.add_argument("--no-copy-probe", action="store_true", help="skip the HBM copy-bandwidth probe")
+    ap.add_argument("--no-copy-probe", action="store_true", help="--full: skip the HBM copy-bandwidth probe")
     ap.add_argument("--no-piece-check", action="store_true",
-                    help="skip the piecewise launches behind the timed region (profiling runs: per-kernel averages stay clean)")
+                    help="--full: skip the piecewise launches behind the timed region (profiling runs: per-kernel averages stay clean)")
     ap.add_argument("--tier-pairs", type=int, default=4_000_000,
-                    help="pairs of the tier T / tier E legs behind the timed region (config3, one GPU; 0 = skip)")
+                    help="--full: pairs of the tier T / tier E legs behind the timed region (config3, one GPU; 0 = skip)")
     ap.add_argument("--host-generator", action="store_true",
                     help="generate the batch on the host and upload it in pieces (rounds 1-4; default: on the device)")
     ap.add_argument("--traffic-json", type=str, default=str(default_traffic_json()),
                     help="JSON with HBM bytes per launch measured in separate rocprofv3 --pmc passes (tools/pmc.sh)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def dump_outputs(out_dir: str, arrays: dict, n: int) -> None:
+    """--dump-outputs: ``arrays`` maps a name to a tensor of ``n`` rows (u8 [n, 8] RESULT_DTYPE records or u8 [n]
+    barcode indices); each goes to DIR/<name>.npy as float32, a record's fields as columns, for every row up to
+    DUMP_ROWS rows and above that for a fixed seeded sample of DUMP_ROWS rows in index order."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+    for name, t in arrays.items():
+        host = t.index_select(0, torch.from_numpy(rows).to(t.device)).cpu().numpy()
+        if host.ndim == 2:
+            rec = host.view(abi.RESULT_DTYPE).reshape(-1)
+            host = np.stack([rec[f].astype(np.float32) for f in abi.RESULT_DTYPE.names], axis=1)
+        np.save(out / f"{name}.npy", host.astype(np.float32))
 
 
 def default_traffic_json() -> Path:
@@ -209,11 +243,11 @@ def main():
     assert last - first == n
     # The resident batch is generated ON THE DEVICE (the generator is keyed by the global pair index: csrc/synth_device.hip
     # writes what csrc/cutseq_host.c writes, tests/test_gpu_synth.py): no host buffer of the batch's size, no pageable
-    # copy, start-up independent of the number of ranks.  The host only generates the head of the shard that the CPU
-    # legs need (baseline sample, parity sample, tier data) -- and that head is compared with the device's bytes.
+    # copy, start-up independent of the number of ranks.  With --full the host also generates the head of the shard that
+    # the CPU legs need (baseline sample, parity sample, tier data) -- and that head is compared with the device's bytes.
     # config 5 plants its barcodes with numpy: it keeps the host generator, in pieces.
-    tiers_on = args.tier_pairs > 0 and args.workload == "config3" and world == 1
-    keep = min(n, max(args.cpu_sample if world == 1 else 0, PARITY_SAMPLE, args.tier_pairs if tiers_on else 0))
+    tiers_on = args.full and args.tier_pairs > 0 and args.workload == "config3" and world == 1
+    keep = min(n, max(args.cpu_sample if world == 1 else 0, PARITY_SAMPLE, args.tier_pairs if tiers_on else 0)) if args.full else 0
     host_threads = max(1, synth.usable_cpus() // world)  # (the ranks share the host: the head of N shards at once)
     names = ("seq1", "qual1", "len1") + (("seq2", "qual2", "len2") if paired else ())
     stride = synth._stride_for(READ_LEN)
@@ -239,10 +273,13 @@ def main():
     else:
         ptrs = [d[name].data_ptr() for name in names] + [None] * (6 - len(names))
         assert workloads.fill_device(args.workload, n, ptrs, first_index=first) == stride
-        batch = workloads.make_batch(args.workload, keep, first_index=first, threads=host_threads)  # the generator the parity tests use
+        batch = head_equal = None
+        if keep:
+            batch = workloads.make_batch(args.workload, keep, first_index=first, threads=host_threads)  # the generator the parity tests use
         torch.cuda.synchronize(dev)
-        head_equal = all(bool(torch.equal(d[name][:keep].cpu(), torch.from_numpy(
-            getattr(batch, name).view(np.int16) if name.startswith("len") else getattr(batch, name)))) for name in names)
+        if keep:
+            head_equal = all(bool(torch.equal(d[name][:keep].cpu(), torch.from_numpy(
+                getattr(batch, name).view(np.int16) if name.startswith("len") else getattr(batch, name)))) for name in names)
         generator = "device (csrc/synth_device.hip), one launch over the shard's global indices"
     gen_s = time.perf_counter() - t_gen
     # one set of result arrays per step in flight (the engine lets a call start once the call three before it is done)
@@ -295,6 +332,10 @@ def main():
     assert timed_calls == args.steps, (timed_calls, args.steps)
     scan_ms, resolve_ms = scan_ms_total / args.steps, resolve_ms_total / args.steps
     kernel_ms = [scan_ms + resolve_ms] if args.serial else [scan_ms]
+    if args.dump_outputs and rank == 0:
+        last = sets[(args.steps - 1) % n_sets]  # (step i writes set i % n_sets)
+        dump_outputs(args.dump_outputs, {name: t for name, t in zip(("r1_results", "r2_results", "r1_barcode"), last[2:])
+                                         if t is not None}, n)
     per_rank = None
     if world > 1:
         # what a reader of the N-GPU line will ask: did every rank run at the same rate, and on its own device?
@@ -403,7 +444,7 @@ def main():
         result["parity_error"] = "the device generator's bytes differ from the host generator's on the head of the shard"
     if per_rank is not None:
         result["per_rank"] = per_rank
-    if n > GEN_PIECE and args.workload != "config5" and not args.no_piece_check:
+    if args.full and n > GEN_PIECE and args.workload != "config5" and not args.no_piece_check:
         # Full-size property (outside the timed region): the batch-sized launch must give, bit for bit, what launches of
         # GEN_PIECE reads over the same resident rows give -- the sizes the parity tests hold to the oracle.  (Tile
         # hand-out in big and small units, queue capacities and reservations all scale with the launch.)
@@ -458,7 +499,7 @@ def main():
             "source": traffic_source,
         }
 
-    if rank == 0 and world == 1 and not args.no_copy_probe:
+    if args.full and rank == 0 and world == 1 and not args.no_copy_probe:
         # measured HBM copy bandwidth of this box: a second denominator next to the 8 TB/s spec
         nbytes = 1 << 30
         src = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -479,7 +520,7 @@ def main():
         result["roofline"]["frac_of_copy_measured"] = round(achieved / copy_gbps, 5)
         del src, dst
 
-    if rank == 0 and world == 1 and args.cpu_sample > 0 and args.workload != "config5":
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0 and args.workload != "config5":
         # (config 5 has no single CPU counterpart: its parity definition is 96 oracle runs, tests/test_gpu_workloads.py)
         import oracle  # the checker, timed as the CPU baseline; never part of the product path
         m = min(args.cpu_sample, n, batch.seq1.shape[0])  # (the host keeps the head of the first generated piece)
@@ -518,7 +559,7 @@ def main():
             extra = {"error": f"{type(exc).__name__}: {exc}"}
         if extra:
             result["cpu_baseline_cutadapt"] = extra
-    if world > 1 and args.workload != "config5":
+    if args.full and world > 1 and args.workload != "config5":
         # An N-GPU rate without a parity gate is not a result: every rank checks a sample of ITS OWN shard against
         # the oracle (the host cores are shared by the ranks), rank 0 reports whether all of them agreed.
         import oracle

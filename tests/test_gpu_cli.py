@@ -353,7 +353,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(launcher):
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     env = dict(os.environ, CUTSEQ_BENCH_REHEARSAL="1", MASTER_ADDR="127.0.0.1")
-    tail = [str(util.GOLDEN.parents[1] / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--pairs", "300000"]
+    tail = [str(util.GOLDEN.parents[1] / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--pairs", "300000", "--full"]
     if launcher == "self":
         cmd = [sys.executable] + tail
         for name in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
@@ -379,6 +379,41 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(launcher):
     assert len({dv["pid"] for dv in pr["devices"]}) == 2 and pr["distinct_devices"] == 1  # two ranks on GPU 0: visible
     assert rep["all_ranks_identical"] is True
     assert rep["batch_generator"]["where"].startswith("device") and rep["batch_generator"]["device_bytes_equal_host_bytes_on_head"] is True
+
+
+@pytest.mark.parametrize("pairs,steps", [(300_000, 2), (1_100_000, 4)])
+def test_bench_plain_run_dumps_the_last_steps_results(tmp_path, pairs, steps):
+    """A plain ``bench.py --gpus 1`` run: the headline fields, exactly --steps timed steps, none of the --full legs, and
+    --dump-outputs holding the results of the last timed step (here not the first step's set of result arrays), equal
+    to the CPU oracle's on the same batch: every pair below bench.DUMP_ROWS, the seeded sample above it."""
+    import subprocess
+    import sys
+
+    import bench
+    import oracle
+    from cutseq_amd import abi, workloads
+
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, str(util.GOLDEN.parents[1] / "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+           "--pairs", str(pairs), "--dump-outputs", str(out_dir)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    rep = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert rep["metric"] == "M read-pairs/sec" and rep["unit"] == "M read-pairs/s" and rep["higher_is_better"] is True
+    assert rep["dtype"] == "u8" and rep["steps"] == steps and rep["value"] > 0 and rep["ms_per_step"] > 0
+    assert abs(rep["value"] * rep["ms_per_step"] * 1e3 / pairs - 1) < 0.01  # value = pairs / ms_per_step
+    assert not {"cpu_baseline", "tiers", "full_size_launch_equals_piecewise_launches", "all_ranks_identical"} & set(rep)
+    assert "copy_measured_GBps" not in rep["roofline"]
+    tp = workloads.make_plan("config3", True)
+    batch = workloads.make_batch("config3", pairs)
+    (o1, _, _), (o2, _, _) = util.oracle_run(tp, batch, threads=min(16, oracle.host_threads()))
+    rows = np.arange(pairs) if pairs <= bench.DUMP_ROWS else np.sort(
+        np.random.default_rng(bench.DUMP_SEED).choice(pairs, bench.DUMP_ROWS, replace=False))
+    assert sorted(p.name for p in out_dir.iterdir()) == ["r1_results.npy", "r2_results.npy"]
+    for name, want in (("r1_results", o1), ("r2_results", o2)):
+        got = np.load(out_dir / f"{name}.npy")
+        assert got.dtype == np.float32
+        assert np.array_equal(got, np.stack([want[f][rows].astype(np.float32) for f in abi.RESULT_DTYPE.names], axis=1))
 
 
 @pytest.mark.parametrize("layout", ["plain+gz", "gz-members-in-lockstep", "gz-members-out-of-step"])

@@ -728,6 +728,37 @@ def test_replayed_counters_need_matching_kernel_sources(tmp_path):
     assert bench.replayed_counters(str(tmp_path / "nope.json"), 1)[0] is None
 
 
+@pytest.mark.parametrize("n", [1000, (1 << 20) + 12345])
+def test_bench_dump_outputs_are_float32_records_of_a_fixed_sample(tmp_path, n):
+    """bench.py --dump-outputs: one float32 row per read (the RESULT_DTYPE fields as columns), every read up to
+    DUMP_ROWS, above that the same seeded sample in index order on every run; at most 64 MB in all."""
+    import bench
+    import torch
+    rng = np.random.default_rng(n)
+    rec = np.zeros(n, dtype=abi.RESULT_DTYPE)
+    for f in abi.RESULT_DTYPE.names:
+        rec[f] = rng.integers(0, np.iinfo(rec[f].dtype).max + 1, size=n)
+    bc = rng.integers(0, 97, size=n).astype(np.uint8)
+    arrays = {"r1_results": torch.from_numpy(rec.view(np.uint8).reshape(n, 8)),
+              "r2_results": torch.from_numpy(rec[::-1].copy().view(np.uint8).reshape(n, 8)), "r1_barcode": torch.from_numpy(bc)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays, n)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, n)
+    files = sorted((tmp_path / "a").iterdir())
+    assert [p.name for p in files] == ["r1_barcode.npy", "r1_results.npy", "r2_results.npy"]
+    assert sum(p.stat().st_size for p in files) <= 64 << 20
+    k = min(n, bench.DUMP_ROWS)
+    got = {p.stem: np.load(p) for p in files}
+    for name, arr in got.items():
+        assert arr.dtype == np.float32 and arr.shape == ((k,) if name == "r1_barcode" else (k, 5))
+        assert np.array_equal(arr, np.load(tmp_path / "b" / f"{name}.npy"))
+    rows = np.arange(n) if n <= bench.DUMP_ROWS else np.sort(np.random.default_rng(bench.DUMP_SEED).choice(n, k, replace=False))
+    assert len(np.unique(rows)) == k
+    want = np.stack([rec[f][rows].astype(np.float32) for f in abi.RESULT_DTYPE.names], axis=1)
+    assert np.array_equal(got["r1_results"], want)
+    assert np.array_equal(got["r2_results"][:, 1], rec["stop"][::-1][rows].astype(np.float32))
+    assert np.array_equal(got["r1_barcode"], bc[rows].astype(np.float32))
+
+
 # ---------------------------------------------------------------- text path, host side (reader / writer; no GPU)
 
 
