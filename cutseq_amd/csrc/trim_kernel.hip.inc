@@ -2245,9 +2245,14 @@ __device__ void strip_dp_pass(const DevOp &d, const char *tab, int rule, const u
       prev_up = up;
       // H cells, each the unsigned minimum of its three candidates: the cost sits in the top byte, and the two
       // bits under it rank the candidates of EQUAL cost the way cutadapt's recurrence does (diagonal first, then
-      // the indel cs_params.indel_tie prefers) before score or origin can have a say.  A match needs no select:
-      // the diagonal + 0 is never dearer than an indel (neighbouring costs differ by at most one, and clamped
-      // costs only by less) and wins the ties.  Dead cells (cost > k) are NOT clamped to a canonical one: a cell at most
+      // the indel cs_params.indel_tie prefers) before score or origin can have a say.  A match cell goes through the
+      // same minimum, where cutadapt takes its diagonal + 0 outright.  That is not because the diagonal is never dearer
+      // than an indel everywhere: beside the first column of a window that starts late (true_init false, j0 > min_n:
+      // row 0 is 0 there, rows >= 1 are held dead at k + 1) the neighbours are only upper bounds, and a match cell can
+      // take up + 1 and stay live where cutadapt would take the dead diagonal.  The argument is this: every cell on a
+      // path of cost at most k to a candidate the window reports has exact neighbours, and there the diagonal + 0 is
+      // the minimum and wins the ties; every other cell only needs to be an upper bound of its true cost, which a
+      // minimum of upper bounds is.  Dead cells (cost > k) are NOT clamped to a canonical one: a cell at most
       // k is the minimum over candidates from cells at most k (costs never fall along a path), so what the dead
       // ones hold changes no live cell, aliveness is always tested as "< live_limit", and the fields cannot overflow:
       // cost <= row 0's cost + i <= k + 1 + 32 (the insertion from above is always a candidate), so score >= -2 cost

@@ -5,6 +5,8 @@ Reference surface replaced: dnaio's record reader / writer and the name modifier
 (cutseq/run.py:330, 378, 434-441, 537-542, 642-645, 751-758, 785-794).  Edge cases are the ones ``tests/test_host_io.py``
 holds for the host parser: CRLF, no final newline, mismatched ids, malformed and truncated records.
 """
+from typing import NamedTuple
+
 import numpy as np
 import pytest
 
@@ -27,8 +29,10 @@ def fastq_text(names, seq, qual, lens, eol=b"\n", final_newline=True):
     return body if final_newline else body[: -len(eol)]
 
 
-def expected_streams(tp, batch, names1, names2):
-    (o1, cap2, _), m2 = util.oracle_run(tp, batch, threads=8)
+def oracle_streams(tp, batch, names1, names2):
+    """-> (streams[route][mate], counts[route], (stats1, stats2 | None)): the oracle's results formatted by the record
+    logic, and its per-mate statistics."""
+    (o1, cap2, ost1), m2 = util.oracle_run(tp, batch, threads=8)
     recs = util.format_batch(tp, batch, names1, names2, o1, cap2, m2[0] if m2 else None)
     streams = [[b"", b""] for _ in range(3)]
     counts = [0, 0, 0]
@@ -37,7 +41,56 @@ def expected_streams(tp, batch, names1, names2):
         if r2 is not None:
             streams[route][1] += r2
         counts[route] += 1
+    return streams, counts, (ost1, m2[2] if m2 else None)
+
+
+def expected_streams(tp, batch, names1, names2):
+    streams, counts, _ = oracle_streams(tp, batch, names1, names2)
     return streams, counts
+
+
+class TextRun(NamedTuple):
+    streams: list   # [route][mate] bytes
+    counts: list    # [route]
+    n_long: list    # [mate]: res.n_long, the reads that took the long-read kernel (long_kernel.hip.inc)
+    stats: tuple    # the engine's per-mate cs_stats after this one batch
+
+
+def run_text_exposed(tp, text1, text2, n, stride, max_records=None) -> TextRun:
+    """One batch through a fresh text engine, like TextEngine.run, keeping what run hides: res.n_long and the stats."""
+    paired = text2 is not None
+    with TrimEngine(tp, device=0, slots=0) as eng:
+        with textpath.TextEngine(eng, slots=1, max_text_bytes=max(len(text1), len(text2 or b""), 1) + 1024,
+                                 max_records=max_records or max(n, 1), stride=stride) as te:
+            te.submit(0, text1, len(text1), text2, len(text2) if paired else 0, n)
+            res = te.wait(0)
+            _got, _raw, count = te.routes(0)
+            out = [np.empty(max(int(res.out_bytes[m]), 1), dtype=np.uint8) for m in range(2)]
+            te.fetch(0, out[0], out[1] if paired else None)
+            streams = textpath.split_routes(res, out, paired)
+        stats = eng.stats()
+    return TextRun(streams, [int(c) for c in count], [int(res.n_long[0]), int(res.n_long[1])], stats)
+
+
+def check_text_path(tp, batch, text1, text2, stride, want, what=""):
+    """The text path at row stride ``stride`` against ``want`` = oracle_streams(...) of the same reads: (a) every read
+    longer than the rows took the long-read kernel (n_long per mate), (b) the streams equal the oracle's results
+    formatted by the record logic, route by route, with the same counts, (c) the per-mate statistics equal the
+    oracle's (test_gpu_parity.stats_dict: without the filter's diagnostics).  -> the TextRun."""
+    from test_gpu_parity import stats_dict
+    want_streams, want_counts, want_stats = want
+    paired = text2 is not None
+    got = run_text_exposed(tp, text1, text2, batch.n, stride)
+    lens = (batch.len1, batch.len2) if paired else (batch.len1,)
+    for m, ln in enumerate(lens):
+        assert got.n_long[m] == int((ln.astype(np.int64) > stride).sum()), (what, stride, m, got.n_long)
+    assert got.counts == want_counts, (what, stride)
+    for route in range(3):
+        for m in range(len(lens)):
+            assert got.streams[route][m] == want_streams[route][m], (what, stride, textpath.ROUTES[route], m)
+    for m in range(len(lens)):
+        assert stats_dict(got.stats[m]) == stats_dict(want_stats[m]), (what, stride, m)
+    return got
 
 
 def run_text(tp, text1, text2, n, stride, max_records=None):
@@ -47,8 +100,14 @@ def run_text(tp, text1, text2, n, stride, max_records=None):
             return te.run(text1, n, text2)
 
 
-@pytest.mark.parametrize("name,flags,paired", [c for c in CHAIN_CASES if "shortcut" not in c[1]])
+# (the SHORTCUT_FIND case last: the other cases keep the ids they had while it was left out)
+@pytest.mark.parametrize("name,flags,paired", [c for c in CHAIN_CASES if "shortcut" not in c[1]]
+                         + [c for c in CHAIN_CASES if "shortcut" in c[1]])
 def test_text_path_equals_oracle_plus_record_logic(name, flags, paired):
+    """Every preset x flag case through the text path at three row strides: the batch's own (every read in the tile
+    kernels), 100 (one batch mixes tile and long reads, some pairs have one long mate: record order and route merging
+    across the two kernels) and 4 (every read of 5 nt or more takes the long-read kernel).  SHORTCUT_FIND included:
+    the long-read kernel has its own str.find (long_kernel.hip.inc)."""
     scheme = BUILDIN_ADAPTERS.get(name, name)
     st = planmod.CutadaptConfig()
     for k, v in flags.items():
@@ -64,14 +123,13 @@ def test_text_path_equals_oracle_plus_record_logic(name, flags, paired):
     tp = util.compile_plan(scheme, st, paired, untrimmed_requested="INLINE" in name)
     names1 = [f"SIM:{i}/1 1:N:0:X".encode() if i % 3 else f"SIM:{i}.1".encode() for i in range(n)]
     names2 = [f"SIM:{i}/2 2:N:0:X".encode() if i % 3 else f"SIM:{i}.2".encode() for i in range(n)] if paired else None
-    want, want_counts = expected_streams(tp, batch, names1, names2)
+    want = oracle_streams(tp, batch, names1, names2)
     text1 = fastq_text(names1, batch.seq1, batch.qual1, batch.len1)
     text2 = fastq_text(names2, batch.seq2, batch.qual2, batch.len2) if paired else None
-    got, counts = run_text(tp, text1, text2, n, batch.stride)
-    assert counts == want_counts
-    for route in range(3):
-        for m in range(2 if paired else 1):
-            assert got[route][m] == want[route][m], (textpath.ROUTES[route], m)
+    n_long = []
+    for stride in (batch.stride, 100, 4):
+        n_long.append(check_text_path(tp, batch, text1, text2, stride, want, name).n_long)
+    assert n_long[0] == [0, 0] and 0 < n_long[1][0] < n and n_long[2][0] > n_long[1][0]
 
 
 @pytest.mark.parametrize("eol,final_newline", [(b"\n", False), (b"\r\n", True), (b"\r\n", False)])

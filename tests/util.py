@@ -186,3 +186,58 @@ def write_fastq(path: str, names: Sequence[bytes], batch_seq: np.ndarray, batch_
     with open(path, "wb") as fh:
         for lo in range(0, max(len(recs), 1), step):
             fh.write(gzip.compress(b"".join(recs[lo:lo + step]), 1))
+
+
+ODD_PRESETS_EXTRA = ["ACACGACGCTCTTCCGATCT(ATCACG)NNNNNNNNXX<XXXNNNN(CGATGT)AGATCGGAAGAGCACACGTC",
+                     "ACGTACGTACGTAC(GATTACA)NN>XNN(TGCA)GGCCTTAAGGCCAATT",
+                     "AAGCAGTGGTATCAACGCAGAGTACXXXXXX-NNNNNNNNCTGTCTCTTATACACATCT"]
+ODD_ALPHABETS = ["ACGT", "ACGTN", "ACGTacgt", "ACGTNRYKMSWBDHV", "ACGT.", "AAAAAAAC", "TTTTTTTG"]
+
+
+def odd_alphabet_cases(seed: int, rounds: int = 8, pairs: int = 1200):
+    """Reads nobody should feed a trimmer but somebody will: lower case, IUPAC codes, dots, every printable quality
+    character, lengths from 0 up, adapters planted with random damage, under randomly drawn presets and flags
+    (case-sensitive plans, SHORTCUT_FIND, schemes whose adapters hold N: uncoded plans).  Deterministic in ``seed``.
+    -> yields (scheme, settings, paired, reads1, reads2, untrimmed_requested); reads as [(seq, qual)] strings, reads2
+    drawn (and returned) for single-end cases too."""
+    from cutseq_amd.common import BUILDIN_ADAPTERS
+    rng = random.Random(1000 + seed)
+    presets = sorted(BUILDIN_ADAPTERS) + ODD_PRESETS_EXTRA
+    for _round in range(rounds):
+        name = rng.choice(presets)
+        scheme = BUILDIN_ADAPTERS.get(name, name)
+        bc = BarcodeConfig(scheme)
+        st = planmod.CutadaptConfig()
+        st.trim_polyA = rng.random() < 0.7
+        st.trim_polyA_wo_direction = rng.random() < 0.3
+        st.conditional_cutter = rng.random() < 0.7
+        st.force_anywhere = rng.random() < 0.3
+        st.ensure_inline_barcode = rng.random() < 0.5
+        st.min_length = rng.choice([0, 1, 20, 35, 151])
+        st.min_quality = rng.choice([0, 2, 20, 30, 41, 93])
+        st.force_trim_min_length = rng.choice([0, 50, 120, 10000])
+        st.select_rule = rng.choice([0, 1])
+        st.indel_tie = rng.choice([abi.CS_TIE_INSERTION, abi.CS_TIE_DELETION])
+        st.case_rule = abi.CS_CASE_SENSITIVE if rng.random() < 0.25 else abi.CS_CASE_FOLD
+        st.shortcut = abi.CS_SHORTCUT_FIND if rng.random() < 0.25 else abi.CS_SHORTCUT_NONE
+        paired = rng.random() < 0.7
+        pieces = [bc.p5.fw, bc.p7.fw, bc.p5.rc, bc.p7.rc, "A" * 30, "T" * 30]
+        reads1, reads2 = [], []
+        for _ in range(pairs):
+            pair = []
+            for _mate in range(2):
+                alpha = rng.choice(ODD_ALPHABETS)
+                parts = []
+                for _ in range(rng.randint(0, 4)):
+                    if rng.random() < 0.5:
+                        parts.append(random_dna(rng, rng.randint(0, 60), alpha))
+                    else:
+                        piece = rng.choice(pieces)
+                        piece = piece[rng.randint(0, len(piece) // 2):][: rng.randint(1, len(piece))]
+                        parts.append(mutate(rng, piece, rng.randint(0, 3), alpha))
+                seq = "".join(parts)[: rng.choice([0, 1, 7, 19, 20, 21, 50, 149, 150, 151, 155])]
+                qual = "".join(chr(rng.randint(33, 126)) for _ in seq)
+                pair.append((seq, qual))
+            reads1.append(pair[0])
+            reads2.append(pair[1])
+        yield scheme, st, paired, reads1, reads2, rng.random() < 0.3
