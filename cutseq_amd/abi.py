@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-CS_ABI_VERSION = 6
+CS_ABI_VERSION = 7
 CS_MAX_ADAPTER = 128
 CS_MAX_OPS = 24
 CS_MAX_STRIDE = 1536
@@ -43,6 +43,8 @@ CS_F_QTRIMMED = 0x10
 CS_F_TOO_SHORT = 0x20
 CS_F_UNTRIMMED = 0x40
 CS_F_AMBIGUOUS = 0x80
+
+CS_X_TOO_MANY_N = 0x01  # cs_reads.xflags
 
 CS_OK = 0
 CS_ERR_ARG, CS_ERR_HIP, CS_ERR_NO_GPU, CS_ERR_NOMEM, CS_ERR_STATE = -1, -2, -3, -4, -5
@@ -112,6 +114,7 @@ class cs_stats(C.Structure):
         ("n_exact_dp", C.c_uint64),
         ("n_refiltered", C.c_uint64),
         ("op_matched", C.c_uint64 * CS_MAX_OPS),
+        ("n_too_many_n", C.c_uint64),
     ]
 
     def as_dict(self) -> dict:
@@ -128,6 +131,7 @@ class cs_reads(C.Structure):
         ("out", C.c_void_p),
         ("cap2", C.c_void_p),
         ("bc", C.c_void_p),
+        ("xflags", C.c_void_p),
     ]
 
 
@@ -156,7 +160,7 @@ class cs_text_result(C.Structure):
         ("max_len", C.c_uint32),
         ("n_records", C.c_uint32),
         ("route_count", C.c_uint32 * 3),
-        ("_pad", C.c_uint32),
+        ("n_too_many_n", C.c_uint32),
         ("route_bytes", (C.c_uint64 * 2) * 3),
         ("out_bytes", C.c_uint64 * 2),
         ("written_bp", C.c_uint64 * 2),
@@ -171,7 +175,7 @@ assert C.sizeof(cs_op) == 284, C.sizeof(cs_op)
 assert C.sizeof(cs_result) == 8
 assert C.sizeof(cs_cap2) == 4
 assert C.sizeof(cs_params) == 32
-assert C.sizeof(cs_stats) == 8 * (8 + CS_MAX_OPS)
+assert C.sizeof(cs_stats) == 8 * (8 + CS_MAX_OPS + 1)
 
 # numpy views of the result records
 import numpy as _np  # noqa: E402

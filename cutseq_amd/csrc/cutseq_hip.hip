@@ -57,6 +57,7 @@ struct Slot {
   cs_result *d_out[2] = {nullptr, nullptr};
   cs_cap2 *d_cap2 = nullptr;
   uint8_t *d_bc[2] = {nullptr, nullptr};
+  uint8_t *d_xf[2] = {nullptr, nullptr};  // cs_reads.xflags
   hipEvent_t done = nullptr;
   bool busy = false;
 };
@@ -130,6 +131,7 @@ struct cs_engine {
   bool paired = false;
   bool coded = false;
   bool wide = false;  // some adapter needs 64-bit bit-vectors
+  bool max_n = false;  // the plan has a TooManyN filter (cs_plan_set_max_n)
   int n_cus = 256;
   uint32_t n_table_ops = 1;
   uint32_t col_dwords = 0;   // per-wave DP scratch the plan needs (resolve kernel)
@@ -253,13 +255,17 @@ struct Geometry {
   uint32_t tile_rows, lds_stride_dw, col_dwords, lds_bytes, item_slots;
 };
 
-template <int MODE>
-const void *kernel_of(const cs_engine *eng) {
+template <int MODE, bool MAXN>
+const void *kernel_variant(const cs_engine *eng) {
   if (eng->coded)
-    return eng->wide ? reinterpret_cast<const void *>(csdev::trim_kernel<true, true, MODE>)
-                     : reinterpret_cast<const void *>(csdev::trim_kernel<true, false, MODE>);
-  return eng->wide ? reinterpret_cast<const void *>(csdev::trim_kernel<false, true, MODE>)
-                   : reinterpret_cast<const void *>(csdev::trim_kernel<false, false, MODE>);
+    return eng->wide ? reinterpret_cast<const void *>(csdev::trim_kernel<true, true, MODE, MAXN>)
+                     : reinterpret_cast<const void *>(csdev::trim_kernel<true, false, MODE, MAXN>);
+  return eng->wide ? reinterpret_cast<const void *>(csdev::trim_kernel<false, true, MODE, MAXN>)
+                   : reinterpret_cast<const void *>(csdev::trim_kernel<false, false, MODE, MAXN>);
+}
+template <int MODE>
+const void *kernel_of(const cs_engine *eng) {  // plans with TooManyN take the kernels that decide it
+  return eng->max_n ? kernel_variant<MODE, true>(eng) : kernel_variant<MODE, false>(eng);
 }
 const void *kernel_for(const cs_engine *eng, int mode) {
   if (mode == csdev::MODE_RESOLVE) return kernel_of<csdev::MODE_RESOLVE>(eng);
@@ -344,6 +350,7 @@ int launch(cs_engine *eng, hipStream_t stream, hipStream_t rstream, const cs_rea
     a.mate[m].out = rr[m]->out;
     a.mate[m].cap2 = rr[m]->cap2;
     a.mate[m].bc = rr[m]->bc;
+    a.mate[m].xflags = rr[m]->xflags;
   }
   Lane &ln = eng->lanes[eng->next_lane];
   eng->next_lane = (eng->next_lane + 1) % kLanes;
@@ -641,6 +648,14 @@ int cs_plan_create(const cs_op *ops_r1, int n1, const cs_op *ops_r2, int n2, con
 
 void cs_plan_destroy(cs_plan *plan) { delete plan; }
 
+int cs_plan_set_max_n(cs_plan *plan, double count) {
+  if (!plan) return fail(CS_ERR_ARG, "null plan");
+  if (!(count >= 0.0)) return fail(CS_ERR_ARG, "max_n %g: the count must not be negative or NaN", count);
+  plan->host.max_n_on = 1;
+  plan->host.max_n = count;
+  return CS_OK;
+}
+
 int cs_plan_set_demux(cs_plan *plan, int mate, int op_index, const uint16_t *table, size_t entries) {
   if (!plan || !table) return fail(CS_ERR_ARG, "null plan or table");
   if (mate < 1 || mate > 2 || op_index < 0 || op_index >= plan->host.n_ops[mate - 1])
@@ -866,6 +881,7 @@ void cs_engine_destroy(cs_engine *eng) {
       if (s.d_len[m]) (void)hipFree(s.d_len[m]);
       if (s.d_out[m]) (void)hipFree(s.d_out[m]);
       if (s.d_bc[m]) (void)hipFree(s.d_bc[m]);
+      if (s.d_xf[m]) (void)hipFree(s.d_xf[m]);
     }
     if (s.d_cap2) (void)hipFree(s.d_cap2);
     if (s.done) (void)hipEventDestroy(s.done);
@@ -912,6 +928,7 @@ int cs_engine_create(const cs_plan *plan, int device, uint32_t n_slots, uint32_t
   eng->device = device;
   eng->paired = plan->host.n_ops[1] > 0;
   eng->coded = plan->host.coded != 0;
+  eng->max_n = plan->host.max_n_on != 0;
   eng->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   eng->n_table_ops = (uint32_t)(plan->host.n_ops[0] > plan->host.n_ops[1] ? plan->host.n_ops[0] : plan->host.n_ops[1]);
   if (eng->n_table_ops < 1) eng->n_table_ops = 1;
@@ -1028,6 +1045,7 @@ int cs_engine_create(const cs_plan *plan, int device, uint32_t n_slots, uint32_t
       ENG_TRY(hipMalloc(&s.d_len[m], (size_t)max_reads * sizeof(uint16_t)));
       ENG_TRY(hipMalloc(&s.d_out[m], (size_t)max_reads * sizeof(cs_result)));
       ENG_TRY(hipMalloc(&s.d_bc[m], (size_t)max_reads));
+      if (eng->max_n) ENG_TRY(hipMalloc(&s.d_xf[m], (size_t)max_reads));  // (only a plan with TooManyN writes them)
     }
     ENG_TRY(hipMalloc(&s.d_cap2, (size_t)max_reads * sizeof(cs_cap2)));
     ENG_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
@@ -1125,6 +1143,7 @@ int cs_trim_batch(cs_engine *eng, uint32_t slot, const cs_reads *r1, const cs_re
     dev[m].out = s.d_out[m];
     dev[m].cap2 = (m == 0 && rr[m]->cap2) ? s.d_cap2 : nullptr;
     dev[m].bc = rr[m]->bc ? s.d_bc[m] : nullptr;
+    dev[m].xflags = (rr[m]->xflags && eng->max_n) ? s.d_xf[m] : nullptr;  // (only a plan with the filter writes them)
   }
   // H2D and scan kernel on the engine stream, resolve kernel and D2H on the resolve stream: the next slot's
   // copies and scan kernel overlap this slot's resolve kernel and write-back
@@ -1136,6 +1155,8 @@ int cs_trim_batch(cs_engine *eng, uint32_t slot, const cs_reads *r1, const cs_re
     if (m == 0 && rr[m]->cap2)
       HIP_TRY(hipMemcpyAsync(rr[m]->cap2, s.d_cap2, (size_t)n_reads * sizeof(cs_cap2), hipMemcpyDeviceToHost, rs));
     if (rr[m]->bc) HIP_TRY(hipMemcpyAsync(rr[m]->bc, s.d_bc[m], (size_t)n_reads, hipMemcpyDeviceToHost, rs));
+    if (rr[m]->xflags && eng->max_n)
+      HIP_TRY(hipMemcpyAsync(rr[m]->xflags, s.d_xf[m], (size_t)n_reads, hipMemcpyDeviceToHost, rs));
   }
   HIP_TRY(hipEventRecord(s.done, rs));
   s.busy = true;
@@ -1332,6 +1353,7 @@ struct TextSlot {
   cstext::TextMeta *d_meta = nullptr;
   cstext::TextMeta *h_meta = nullptr;      // pinned
   uint8_t *d_bc = nullptr;                 // demultiplexing plans: barcode index per record
+  uint8_t *d_xf[2] = {nullptr, nullptr};   // plans with TooManyN: cs_reads.xflags per record and mate
   RouteBlock *d_routes = nullptr, *h_routes = nullptr;  // ... and the sizes of their 3 + n_bins route streams
   hipEvent_t uploaded = nullptr, formatted = nullptr, fetched = nullptr;
   uint32_t n = 0;
@@ -1411,6 +1433,7 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
   t->tp.untrimmed_filter = params->untrimmed_filter ? 1 : 0;
   t->tp.reverse_complement = params->reverse_complement ? 1 : 0;
   t->tp.fasta_out = params->fasta_out ? 1 : 0;
+  t->tp.max_n = eng->max_n ? 1 : 0;
   t->tp.flag_too_short = CS_F_TOO_SHORT;
   t->tp.flag_untrimmed = CS_F_UNTRIMMED;
   const char *const *suf[2] = {params->suffix1, params->suffix2};
@@ -1526,6 +1549,9 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
     const size_t o_meta = reserve(sizeof(cstext::TextMeta));
     const size_t o_bc = t->tp.n_bins ? reserve(max_records) : 0;
     const size_t o_routes = t->tp.n_bins ? reserve(sizeof(RouteBlock)) : 0;
+    size_t o_xf[2] = {0, 0};
+    if (t->tp.max_n)
+      for (int m = 0; m < mates; ++m) o_xf[m] = reserve(max_records);
     TXT_TRY(hipMalloc(&s.d_arena, need));
     uint8_t *base = s.d_arena;
     TXT_TRY(hipMemsetAsync(base, 0, zero_bytes, t->h2d));
@@ -1552,6 +1578,8 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
       }
     }
     if (t->needs_cap2) s.d_cap2 = reinterpret_cast<cs_cap2 *>(base + o_cap2);
+    if (t->tp.max_n)
+      for (int m = 0; m < mates; ++m) s.d_xf[m] = base + o_xf[m];
     s.d_blk = reinterpret_cast<uint32_t *>(base + o_blk);
     s.d_totals = reinterpret_cast<unsigned long long *>(base + o_totals);
     s.d_meta = reinterpret_cast<cstext::TextMeta *>(base + o_meta);
@@ -1646,6 +1674,7 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
       rd[m].out = s.d_res[m];
       rd[m].cap2 = (m == 0) ? s.d_cap2 : nullptr;
       rd[m].bc = (t->tp.n_bins && m == eng->demux_mate) ? s.d_bc : nullptr;
+      rd[m].xflags = s.d_xf[m];
     }
     int rc = launch(eng, st, rs, &rd[0], mates == 2 ? &rd[1] : nullptr, n_records, t->stride, false, &s.d_meta->err);
     if (rc) return rc;
@@ -1663,6 +1692,7 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
       fa.long_of[m] = s.d_long_of[m];
       fa.lrec[m] = s.d_lrec[m];
       fa.lres[m] = s.d_lres[m];
+      fa.xf[m] = s.d_xf[m];
     }
     fa.cap2 = s.d_cap2;
     fa.n = n_records;
@@ -1758,6 +1788,7 @@ int cs_text_wait(cs_text *t, uint32_t slot, cs_text_result *res) {
     res->route_count[q] = m.route_count[q];
     for (int k = 0; k < 2; ++k) res->route_bytes[q][k] = m.route_bytes[q][k];
   }
+  res->n_too_many_n = m.n_too_many_n;
   res->out_bytes[0] = m.out_bytes[0];
   res->out_bytes[1] = m.out_bytes[1];
   if (t->compress && m.err == ~0ull) {  // what is fetched (and written) are the gzip members

@@ -396,16 +396,26 @@ static uint8_t *emit(uint8_t *o, const uint8_t *id, int32_t idl, const uint8_t *
   return o;
 }
 
+/* TooManyN (cs_reads.xflags bit 0, CS_X_TOO_MANY_N), pair filter "any": behind TooShort, in front of IsUntrimmedAny.
+ * xf1 / xf2 NULL: no such filter. */
+#define CSH_ROUTE_DISCARD (-1)
+static int route_of(const csh_format_params *fp, unsigned flags, unsigned xflags) {
+  if (flags & fp->flag_too_short) return 1;
+  if (xflags & 1u) return CSH_ROUTE_DISCARD;
+  return (fp->untrimmed_filter && (flags & fp->flag_untrimmed)) ? 2 : 0;
+}
+
 /* Format one chunk.  out[route][mate] are caller-allocated buffers (capacity: raw chunk bytes +
  * 260 per record is always enough); out_len[route][mate] receives the bytes written and
- * counts[route] the records (pairs).  Routes: 0 trimmed, 1 short, 2 untrimmed.
+ * counts[route] the records (pairs).  Routes: 0 trimmed, 1 short, 2 untrimmed.  xf1 / xf2 (may be NULL): per-read
+ * CS_X_* flags; the pairs TooManyN takes are written nowhere and counted in no route (n - the sum of counts[]).
  * Returns 0, or -(record index + 1) when the mates' ids differ. */
 int64_t csh_format_chunk(const csh_format_params *fp, int64_t n, uint32_t stride, const uint8_t *raw1,
                          const int64_t *name_off1, const int32_t *name_len1, const uint8_t *seq1,
                          const uint8_t *qual1, const csh_result *res1, const csh_cap2 *cap2, const uint8_t *raw2,
                          const int64_t *name_off2, const int32_t *name_len2, const uint8_t *seq2,
                          const uint8_t *qual2, const csh_result *res2, uint8_t *out[3][2], int64_t out_len[3][2],
-                         int64_t counts[3]) {
+                         int64_t counts[3], const uint8_t *xf1, const uint8_t *xf2) {
   if (!rc_ready) rc_init();
   uint8_t *w[3][2];
   for (int r = 0; r < 3; r++) {
@@ -413,6 +423,7 @@ int64_t csh_format_chunk(const csh_format_params *fp, int64_t n, uint32_t stride
     for (int m = 0; m < 2; m++) w[r][m] = out[r][m];
   }
   for (int64_t i = 0; i < n; i++) {
+    unsigned xflags = xf1 ? xf1[i] : 0u;
     const uint8_t *nm1 = raw1 + name_off1[i];
     int32_t nl1 = strip_suffixes(nm1, name_len1[i], fp->suffix1);
     int32_t id1o, id1l;
@@ -420,7 +431,8 @@ int64_t csh_format_chunk(const csh_format_params *fp, int64_t n, uint32_t stride
     const uint8_t *s1 = seq1 + (size_t)i * stride, *q1 = qual1 + (size_t)i * stride;
     unsigned flags = res1[i].flags;
     if (!fp->paired) {
-      int route = (flags & fp->flag_too_short) ? 1 : ((fp->untrimmed_filter && (flags & fp->flag_untrimmed)) ? 2 : 0);
+      int route = route_of(fp, flags, xflags);
+      if (route == CSH_ROUTE_DISCARD) continue;
       const uint8_t *t2 = cap2 ? s1 + cap2[i].off : NULL;
       w[route][0] = emit(w[route][0], nm1 + id1o, id1l, s1 + res1[i].cap_off, res1[i].cap_len, t2,
                          cap2 ? cap2[i].len : 0, fp->has_umi, s1, q1, res1[i].start, res1[i].stop,
@@ -435,7 +447,9 @@ int64_t csh_format_chunk(const csh_format_params *fp, int64_t n, uint32_t stride
     read_id(nm2, nl2, &id2o, &id2l);
     const uint8_t *s2 = seq2 + (size_t)i * stride, *q2 = qual2 + (size_t)i * stride;
     flags |= res2[i].flags;
-    int route = (flags & fp->flag_too_short) ? 1 : ((fp->untrimmed_filter && (flags & fp->flag_untrimmed)) ? 2 : 0);
+    if (xf2) xflags |= xf2[i];
+    int route = route_of(fp, flags, xflags);
+    if (route == CSH_ROUTE_DISCARD) continue;
     w[route][0] = emit(w[route][0], nm1 + id1o, id1l, s1 + res1[i].cap_off, res1[i].cap_len, s2 + res2[i].cap_off,
                        res2[i].cap_len, fp->has_umi, s1, q1, res1[i].start, res1[i].stop, 0);
     w[route][1] = emit(w[route][1], nm2 + id2o, id2l, s1 + res1[i].cap_off, res1[i].cap_len, s2 + res2[i].cap_off,
@@ -453,7 +467,8 @@ int64_t csh_format_chunk(const csh_format_params *fp, int64_t n, uint32_t stride
  * mate lie back to back in out_binned[mate] (capacity as for a route buffer), bin b at
  * [bin_off[mate * (n_bins + 1) + b], bin_off[.. + b + 1]).  Two passes: sizes, then bytes.  Records whose
  * bin is out of range (no barcode) are written to route 2 whatever their flags say.
- * bin_counts[b] receives the records (pairs) of bin b, counts[1], counts[2] those of the other routes. */
+ * bin_counts[b] receives the records (pairs) of bin b, counts[1], counts[2] those of the other routes.  xf1 / xf2 as
+ * for csh_format_chunk: TooManyN takes a pair before the untrimmed and barcode routes see it. */
 typedef struct {
   int route;
   int32_t id1o, id1l, id2o, id2l, nl1, nl2;
@@ -461,19 +476,21 @@ typedef struct {
 
 static int prep_record(const csh_format_params *fp, int64_t i, const uint8_t *raw1, const int64_t *name_off1,
                        const int32_t *name_len1, const csh_result *res1, const uint8_t *raw2, const int64_t *name_off2,
-                       const int32_t *name_len2, const csh_result *res2, csh_prep *p) {
+                       const int32_t *name_len2, const csh_result *res2, const uint8_t *xf1, const uint8_t *xf2,
+                       csh_prep *p) {
   const uint8_t *nm1 = raw1 + name_off1[i];
   p->nl1 = strip_suffixes(nm1, name_len1[i], fp->suffix1);
   read_id(nm1, p->nl1, &p->id1o, &p->id1l);
-  unsigned flags = res1[i].flags;
+  unsigned flags = res1[i].flags, xflags = xf1 ? xf1[i] : 0u;
   if (fp->paired) {
     const uint8_t *nm2 = raw2 + name_off2[i];
     p->nl2 = strip_suffixes(nm2, name_len2[i], fp->suffix2);
     if (!ids_match(nm1, p->nl1, nm2, p->nl2)) return -1;
     read_id(nm2, p->nl2, &p->id2o, &p->id2l);
     flags |= res2[i].flags;
+    if (xf2) xflags |= xf2[i];
   }
-  p->route = (flags & fp->flag_too_short) ? 1 : ((fp->untrimmed_filter && (flags & fp->flag_untrimmed)) ? 2 : 0);
+  p->route = route_of(fp, flags, xflags);
   return 0;
 }
 
@@ -483,7 +500,7 @@ int64_t csh_format_chunk_bins(const csh_format_params *fp, int64_t n, uint32_t s
                               const int64_t *name_off2, const int32_t *name_len2, const uint8_t *seq2,
                               const uint8_t *qual2, const csh_result *res2, const uint8_t *bin, int32_t n_bins,
                               uint8_t *out_binned[2], int64_t *bin_off, int64_t *bin_counts, uint8_t *out[3][2],
-                              int64_t out_len[3][2], int64_t counts[3]) {
+                              int64_t out_len[3][2], int64_t counts[3], const uint8_t *xf1, const uint8_t *xf2) {
   if (!rc_ready) rc_init();
   if (!bin || n_bins < 1 || n_bins > 255) return -(n + 1);
   const int mates = fp->paired ? 2 : 1;
@@ -494,7 +511,8 @@ int64_t csh_format_chunk_bins(const csh_format_params *fp, int64_t n, uint32_t s
   /* pass 1: bytes per bin and mate (accumulated at bin_off[.. + b + 1]) */
   for (int64_t i = 0; i < n; i++) {
     csh_prep p;
-    if (prep_record(fp, i, raw1, name_off1, name_len1, res1, raw2, name_off2, name_len2, res2, &p)) return -(i + 1);
+    if (prep_record(fp, i, raw1, name_off1, name_len1, res1, raw2, name_off2, name_len2, res2, xf1, xf2, &p))
+      return -(i + 1);
     if (p.route != 0 || bin[i] >= n_bins) continue;
     int32_t tag = 0;
     if (fp->has_umi) tag = 1 + res1[i].cap_len + (fp->paired ? res2[i].cap_len : (cap2 ? cap2[i].len : 0));
@@ -515,8 +533,9 @@ int64_t csh_format_chunk_bins(const csh_format_params *fp, int64_t n, uint32_t s
   for (int64_t j = 0; j < 2 * stride_off; j++) cur[j] = bin_off[j];
   for (int64_t i = 0; i < n; i++) {
     csh_prep p;
-    (void)prep_record(fp, i, raw1, name_off1, name_len1, res1, raw2, name_off2, name_len2, res2, &p);
+    (void)prep_record(fp, i, raw1, name_off1, name_len1, res1, raw2, name_off2, name_len2, res2, xf1, xf2, &p);
     int route = p.route;
+    if (route == CSH_ROUTE_DISCARD) continue;
     if (route == 0 && bin[i] >= n_bins) route = 2;
     const uint8_t *nm1 = raw1 + name_off1[i];
     const uint8_t *s1 = seq1 + (size_t)i * stride, *q1 = qual1 + (size_t)i * stride;

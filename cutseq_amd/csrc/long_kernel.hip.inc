@@ -26,6 +26,7 @@ struct LongRec {  // one long read of one mate
 struct LongRes {  // its result: cs_result + cs_cap2 with 32-bit positions
   uint32_t start, stop, cap_off, cap2_off;
   uint8_t cap_len, cap2_len, flags, bc;
+  uint8_t xflags, _pad[3];  // CS_X_* (TooManyN)
 };
 
 __device__ __forceinline__ uint32_t query_code(uint8_t c, bool coded, bool fold) {
@@ -323,6 +324,15 @@ __global__ void __launch_bounds__(64) long_kernel(LongArgs a) {
       }
     }
     if (e - s < (int)plan->params.min_length) flags |= CS_F_TOO_SHORT;
+    uint32_t xflags = 0;
+    if (plan->max_n_on) {  // TooManyN on the final interval: the read's own bytes, up to CS_MAX_READ of them
+      uint32_t nn = 0;
+      for (int i = s; i < e; ++i) nn += (seq[i] | 0x20u) == 'n' ? 1u : 0u;
+      if (csdev::too_many_n(nn, e - s, plan->max_n)) {
+        xflags = CS_X_TOO_MANY_N;
+        atomicAdd(&a.stats[csdev::ST_TOO_MANY_N], 1ull);
+      }
+    }
     LongRes r;
     r.start = (uint32_t)s;
     r.stop = (uint32_t)e;
@@ -332,6 +342,8 @@ __global__ void __launch_bounds__(64) long_kernel(LongArgs a) {
     r.cap2_len = (uint8_t)cap2_len;
     r.flags = (uint8_t)flags;
     r.bc = (uint8_t)bc;
+    r.xflags = (uint8_t)xflags;
+    r._pad[0] = r._pad[1] = r._pad[2] = 0;
     a.res[it] = r;
     atomicAdd(&a.stats[csdev::ST_READS], 1ull);
     atomicAdd(&a.stats[csdev::ST_IN_BP], (unsigned long long)lr.len);

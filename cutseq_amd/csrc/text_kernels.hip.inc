@@ -14,8 +14,8 @@
 //   text_restride         sequence and quality lines -> the [n][stride] rows the trimming kernels take (one lane per
 //                         destination dword: two aligned source dwords, one funnel shift)
 //   (scan + resolve kernels: trim_kernel.hip.inc, unchanged)
-//   format_sizes / format_scan / format_offsets   route of every record (TooShort -> IsUntrimmedAny -> sink, pair
-//                         filter "any") and the byte offset of its output record inside the route's stream: block
+//   format_sizes / format_scan / format_offsets   route of every record (TooShort -> TooManyN -> IsUntrimmedAny ->
+//                         sink, pair filter "any"; TooManyN discards the pair: no route, no bytes) and the byte offset of its output record inside the route's stream: block
 //                         sums, exclusive scan, block-local scans -- output order = input order
 //   format_copy           32 lanes per output record: '@' id ['_' UMI] '\n' seq[start:stop] "\n+\n" qual[start:stop] '\n'
 //
@@ -46,7 +46,8 @@ struct TextMeta {                    // what the host reads back per batch (one 
   uint32_t n_lines[2];
   uint32_t max_len;                  // longest read seen (the host grows the row stride when it exceeds it)
   uint32_t no_index;                 // bit m: mate m's text has the wrong line count, its newline index was not written
-  uint32_t _pad[2];
+  uint32_t n_too_many_n;             // pairs TooManyN discarded (plans with cs_plan_set_max_n)
+  uint32_t _pad;
   unsigned long long written_bp[2];  // bases of the records that reach the final sink (route 0), per mate
   uint32_t n_long[2];                // per mate: reads longer than the rows (long_kernel.hip.inc walks their chains)
   unsigned long long gz_route_bytes[3][2];  // compressed output (deflate_kernels.hip.inc): bytes of each gzip member
@@ -54,6 +55,8 @@ struct TextMeta {                    // what the host reads back per batch (one 
 };
 
 constexpr uint32_t kMaxRoutes = 3 + 255;  // trimmed / short / untrimmed + one route per barcode of a demultiplexing plan
+constexpr uint32_t kRouteDiscard = 0x1feu;  // TooManyN: the pair goes nowhere (below the 0x1ff of the lanes past the end)
+constexpr uint32_t kDiscarded = ~0u;        // FormatArgs.dst of a discarded record (no output offset is ever that)
 
 struct TextParams {  // constant per engine
   uint8_t paired, has_umi, untrimmed_filter, reverse_complement;
@@ -62,7 +65,9 @@ struct TextParams {  // constant per engine
   uint8_t suffix[2][2][kSuffixMax];  // [mate][which]: SuffixRemover literals, applied in order
   uint8_t suffix_len[2][2];
   uint8_t demux_mate;                // n_bins > 0: the mate (0 / 1) whose chain holds the demultiplexing op
-  uint8_t fasta_out, _pad[2];        // output records are ">id\nseq\n" (no qualities to write)
+  uint8_t fasta_out;                 // output records are ">id\nseq\n" (no qualities to write)
+  uint8_t max_n;                     // the plan has TooManyN: FormatArgs.xf holds its per-read flags
+  uint8_t _pad;
 };
 
 __device__ __forceinline__ void report(TextMeta *meta, uint32_t record, uint32_t code) {
@@ -347,6 +352,7 @@ struct FormatArgs {
   const uint32_t *long_of[2];        // per record: index into lrec / lres, or kNotLong
   const cslong::LongRec *lrec[2];
   const cslong::LongRes *lres[2];
+  const uint8_t *xf[2];    // TextParams.max_n: cs_reads.xflags of the tile kernels (long reads: LongRes.xflags)
   uint32_t n, stride;
   uint32_t *blk;           // [n_blocks][6] block sums, then their exclusive scan (column = route * 2 + mate)
   unsigned long long *totals;  // [6] column sums
@@ -403,6 +409,11 @@ __device__ __forceinline__ ReadView read_view(const FormatArgs &a, uint32_t m, u
   return v;
 }
 
+__device__ __forceinline__ uint32_t xflags_of(const FormatArgs &a, uint32_t m, uint32_t r) {
+  const uint32_t slot = a.long_of[m][r];
+  return slot != kNotLong ? a.lres[m][slot].xflags : a.xf[m][r];
+}
+
 __device__ __forceinline__ RecordShape record_shape(const FormatArgs &a, const TextParams &tp, uint32_t r) {
   RecordShape s;
   const ReadView r1 = read_view(a, 0, r);
@@ -414,6 +425,9 @@ __device__ __forceinline__ RecordShape record_shape(const FormatArgs &a, const T
   }
   if (tp.has_umi) tag = 1u + r1.cap_len + (tp.paired ? r2.cap_len : r1.cap2_len);
   s.route = (flags & tp.flag_too_short) ? 1u : ((tp.untrimmed_filter && (flags & tp.flag_untrimmed)) ? 2u : 0u);
+  // TooManyN (pair filter "any"), behind TooShort and in front of IsUntrimmedAny: cutadapt has no file for it
+  if (tp.max_n && s.route != 1u && ((xflags_of(a, 0, r) | (tp.paired ? xflags_of(a, 1, r) : 0u)) & CS_X_TOO_MANY_N))
+    s.route = kRouteDiscard;
   if (tp.n_bins && s.route == 0u) {
     const uint32_t slot = a.long_of[tp.demux_mate][r];  // (a read longer than the rows: its barcode is in the long kernel's result)
     const uint32_t bc = slot != kNotLong ? a.lres[tp.demux_mate][slot].bc : a.bc[r];
@@ -468,6 +482,8 @@ __global__ void __launch_bounds__(256) format_offsets(FormatArgs a, TextParams t
     (void)block_scan_256(s.route == q ? 1u : 0u, total, sh);
     counts[q] = total;
   }
+  uint32_t discarded = 0;
+  if (tp.max_n) (void)block_scan_256(r < a.n && s.route == kRouteDiscard ? 1u : 0u, discarded, sh);
   // cutadapt's written_bp: what reaches the final sink (report.account_chunk)
   uint32_t kept_bp[2] = {0, 0};
 #pragma unroll
@@ -480,12 +496,14 @@ __global__ void __launch_bounds__(256) format_offsets(FormatArgs a, TextParams t
     (void)block_scan_256(bp, kept_bp[m], sh);
   }
   if (r < a.n) {
-    a.dst[0][r] = mine[0] | (s.route << 30);
-    if (tp.paired) a.dst[1][r] = mine[1] | (s.route << 30);
+    const bool gone = s.route == kRouteDiscard;
+    a.dst[0][r] = gone ? kDiscarded : mine[0] | (s.route << 30);
+    if (tp.paired) a.dst[1][r] = gone ? kDiscarded : mine[1] | (s.route << 30);
   }
   if (threadIdx.x == 0) {
     for (uint32_t q = 0; q < 3; ++q)
       if (counts[q]) atomicAdd(&a.meta->route_count[q], counts[q]);
+    if (discarded) atomicAdd(&a.meta->n_too_many_n, discarded);
     for (uint32_t m = 0; m < 2; ++m)
       if (kept_bp[m]) atomicAdd(&a.meta->written_bp[m], (unsigned long long)kept_bp[m]);
     if (blockIdx.x == 0) {
@@ -509,8 +527,10 @@ __global__ void __launch_bounds__(256) format_sizes_bins(FormatArgs a, TextParam
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
   if (r < a.n) {
     const RecordShape s = record_shape(a, tp, r);
-    atomicAdd(&acc[s.route * 2u], s.len[0]);
-    if (tp.paired) atomicAdd(&acc[s.route * 2u + 1u], s.len[1]);
+    if (s.route != kRouteDiscard) {
+      atomicAdd(&acc[s.route * 2u], s.len[0]);
+      if (tp.paired) atomicAdd(&acc[s.route * 2u + 1u], s.len[1]);
+    }
   }
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < cols; i += 256u) a.blk[(size_t)blockIdx.x * cols + i] = acc[i];
@@ -521,12 +541,14 @@ __global__ void __launch_bounds__(256) format_offsets_bins(FormatArgs a, TextPar
   __shared__ uint32_t wsum[4][kMaxRoutes * 2];  // bytes per wave and route
   __shared__ uint32_t rcount[kMaxRoutes];
   __shared__ uint32_t sz[256][2];
+  __shared__ uint32_t n_gone;
   __shared__ uint32_t sh[8];
   if (a.meta->err != ~0ull) return;
   const uint32_t routes = 3u + tp.n_bins, cols = routes * 2u;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   for (uint32_t i = tid; i < cols; i += 256u) wsum[0][i] = wsum[1][i] = wsum[2][i] = wsum[3][i] = 0;
   for (uint32_t i = tid; i < routes; i += 256u) rcount[i] = 0;
+  if (tid == 0) n_gone = 0;
   if (tid < 2u) {  // the routes' streams lie back to back in route order: a running sum over the column totals
     unsigned long long run = 0;
     for (uint32_t q = 0; q < routes; ++q) {
@@ -539,9 +561,14 @@ __global__ void __launch_bounds__(256) format_offsets_bins(FormatArgs a, TextPar
   RecordShape s = {0x1ffu, {0u, 0u}};  // (lanes behind the last record: a route of their own)
   if (r < a.n) {
     s = record_shape(a, tp, r);
-    atomicAdd(&wsum[wave][s.route * 2u], s.len[0]);
-    if (tp.paired) atomicAdd(&wsum[wave][s.route * 2u + 1u], s.len[1]);
-    atomicAdd(&rcount[s.route], 1u);
+    if (s.route == kRouteDiscard) {
+      s.len[0] = s.len[1] = 0;
+      atomicAdd(&n_gone, 1u);
+    } else {
+      atomicAdd(&wsum[wave][s.route * 2u], s.len[0]);
+      if (tp.paired) atomicAdd(&wsum[wave][s.route * 2u + 1u], s.len[1]);
+      atomicAdd(&rcount[s.route], 1u);
+    }
   }
   sz[tid][0] = s.len[0];
   sz[tid][1] = s.len[1];
@@ -562,7 +589,10 @@ __global__ void __launch_bounds__(256) format_offsets_bins(FormatArgs a, TextPar
     mine[0] += sz[wave * 64u + j][0];
     mine[1] += sz[wave * 64u + j][1];
   }
-  if (r < a.n) {
+  if (r < a.n && s.route == kRouteDiscard) {
+    a.dst[0][r] = kDiscarded;
+    if (tp.paired) a.dst[1][r] = kDiscarded;
+  } else if (r < a.n) {
 #pragma unroll
     for (uint32_t m = 0; m < 2u; ++m) {
       uint32_t at = base[s.route * 2u + m] + mine[m];
@@ -574,7 +604,7 @@ __global__ void __launch_bounds__(256) format_offsets_bins(FormatArgs a, TextPar
 #pragma unroll
   for (uint32_t m = 0; m < 2; ++m) {
     uint32_t bp = 0;
-    if (r < a.n && (s.route == 0u || s.route >= 3u) && (m == 0 || tp.paired)) {
+    if (r < a.n && (s.route == 0u || (s.route >= 3u && s.route != kRouteDiscard)) && (m == 0 || tp.paired)) {
       const ReadView v = read_view(a, m, r);
       bp = v.stop - v.start;
     }
@@ -588,6 +618,7 @@ __global__ void __launch_bounds__(256) format_offsets_bins(FormatArgs a, TextPar
   if (tid == 0) {
     for (uint32_t m = 0; m < 2; ++m)
       if (kept_bp[m]) atomicAdd(&a.meta->written_bp[m], (unsigned long long)kept_bp[m]);
+    if (n_gone) atomicAdd(&a.meta->n_too_many_n, n_gone);
   }
   if (blockIdx.x == 0) {
     for (uint32_t i = tid; i < cols; i += 256u) a.route_bytes[i] = a.totals[i];
@@ -629,6 +660,7 @@ __global__ void __launch_bounds__(256) format_copy(FormatArgs a, TextParams tp) 
   for (unsigned long long it = ((unsigned long long)blockIdx.x * 256ull + threadIdx.x) >> 5; it < items;
        it += ((unsigned long long)gridDim.x * 256ull) >> 5) {
     const uint32_t m = tp.paired ? (uint32_t)(it & 1ull) : 0u, r = (uint32_t)(tp.paired ? it >> 1 : it);
+    if (tp.max_n && a.dst[m][r] == kDiscarded) continue;  // (TooManyN; uniform over the record's 32 lanes)
     const ReadView me = read_view(a, m, r);
     const ReadView r1 = m == 0 ? me : read_view(a, 0, r);
     const uint32_t idr = a.idr[m][r];

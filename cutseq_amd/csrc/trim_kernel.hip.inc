@@ -123,8 +123,9 @@ struct DevPlan {
   cs_params params;
   int32_t n_ops[2];
   int32_t coded;  // every adapter base is A/C/G/T: the tile is re-coded at staging
-  int32_t _pad;
+  int32_t max_n_on;  // cs_plan_set_max_n was called: TooManyN(max_n) on the final interval of every read
   DevOp ops[2][CS_MAX_OPS];
+  double max_n;
 };
 
 // Plans live in constant memory (scalar loads for everything wave-uniform); one slot per
@@ -139,6 +140,7 @@ struct MateArgs {
   cs_result *out;
   cs_cap2 *cap2;
   uint8_t *bc;
+  uint8_t *xflags;
 };
 
 // dynamic tile hand-out: counters per mate (one address sustains ~88 atomics/us; light plans need more)
@@ -2379,7 +2381,48 @@ __device__ __forceinline__ uint32_t atomic_add_later(uint32_t *p, uint32_t v) {
 
 // stats slots inside one mate's cs_stats (u64 words)
 enum { ST_READS = 0, ST_IN_BP, ST_OUT_BP, ST_QTRIM_BP, ST_TOO_SHORT, ST_UNTRIMMED, ST_EXACT_DP, ST_RESERVED, ST_OPS };
-constexpr int kStatWords = ST_OPS + CS_MAX_OPS;
+constexpr int ST_TOO_MANY_N = ST_OPS + CS_MAX_OPS;  // cs_stats.n_too_many_n, behind op_matched[]
+constexpr int kStatWords = ST_TOO_MANY_N + 1;
+static_assert(sizeof(cs_stats) == kStatWords * 8, "cs_stats layout");
+
+// ---- TooManyN (cs_plan_set_max_n, cutadapt --max-n): 'N' / 'n' bases in [s, e) of a row, and the filter's rule.
+// Raw bytes (ASCII rows in HBM, or a raw tile: its case folding only turns 'n' into 'N'): exact zero-byte test on
+// byte ^ 'N' with bit 5 cleared.
+__device__ __forceinline__ uint32_t count_n_bytes(const uint32_t *row, int s, int e) {
+  uint32_t n = 0;
+  if (e <= s) return 0;
+  const int d0 = s >> 2, d1 = (e - 1) >> 2;
+  for (int d = d0; d <= d1; ++d) {
+    uint32_t keep = 0x80808080u;
+    if (d == d0) keep &= 0x80808080u << ((s & 3) * 8);
+    if (d == d1) keep &= 0x80808080u >> ((3 - ((e - 1) & 3)) * 8);
+    const uint32_t x = (row[d] & 0xdfdfdfdfu) ^ 0x4e4e4e4eu;
+    n += (uint32_t)__popc(~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & keep);
+  }
+  return n;
+}
+// A coded tile of the FAST form (every byte vouched to be A, C, G, T or N): code 7 is 'N' and nothing else, eight
+// three-bit codes per dword -- the bits of a nibble ANDed together, one popcount.  (Not on exact-form tiles: IUPAC codes
+// and 'n' under CS_CASE_SENSITIVE land in 4..7 there.)
+__device__ __forceinline__ uint32_t count_n_nibbles(const uint32_t *row, int s, int e) {
+  uint32_t n = 0;
+  if (e <= s) return 0;
+  const int d0 = s >> 3, d1 = (e - 1) >> 3;
+  for (int d = d0; d <= d1; ++d) {
+    uint32_t keep = 0x11111111u;
+    if (d == d0) keep &= 0x11111111u << ((s & 7) * 4);
+    if (d == d1) keep &= 0x11111111u >> ((7 - ((e - 1) & 7)) * 4);
+    const uint32_t w = row[d];
+    n += (uint32_t)__popc(w & (w >> 1) & (w >> 2) & keep);
+  }
+  return n;
+}
+// cutadapt TooManyN: a count below 1 is a proportion of the read's length (IEEE double division, strict >; an empty
+// read is kept), any other count a number of bases
+__device__ __forceinline__ bool too_many_n(uint32_t n, int len, double count) {
+  if (count < 1.0) return len > 0 && (double)n / (double)len > count;
+  return (double)n > count;
+}
 
 // ---------------------------------------------------------------------------------
 // Two kernels, one body.
@@ -2407,7 +2450,7 @@ enum { MODE_SCAN = 0, MODE_RESOLVE = 1 };
 #ifndef CS_SCAN_WAVES
 #define CS_SCAN_WAVES 5  // diagnostic builds: -DCS_SCAN_WAVES=6 / 7 (tools/lean_probe.sh)
 #endif
-template <bool CODED, bool WIDE, int MODE>
+template <bool CODED, bool WIDE, int MODE, bool MAXN>
 __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) trim_kernel(KArgs a) {
   if (a.gate && *a.gate != ~0ull) return;  // (wave-uniform: one wave per block)
   const DevPlan *plan = &c_plans[a.plan_slot];
@@ -3357,6 +3400,28 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
     }
     if (ma.bc) ma.bc[gr] = (uint8_t)(meta >> 16);
   }
+
+  // ---- TooManyN on the final interval (cs_plan_set_max_n): kernels of their own (MAXN), so that a plan without the
+  // filter runs exactly the code it ran before (in the scan kernel's register budget any code here costs a spill)
+  if constexpr (MAXN) {
+    bool many = false;
+    if (fin) {
+      uint32_t nn;
+      // the fast form vouched for every byte of the tile exactly when the wave's staging has not failed (mode 1 only:
+      // mode 2 never stages again, whatever the bytes are)
+      if (SCAN && CODED && a.fast_recode == 1u && !fast_failed)
+        nn = count_n_nibbles(myrow, s, e);
+      else if (!CODED)
+        nn = count_n_bytes(myrow, s, e);
+      else  // an exact-form tile (or the resolve kernel's): the read's own bytes
+        nn = count_n_bytes(ma.seq + (size_t)gr * a.stride_dw, s, e);
+      many = too_many_n(nn, e - s, plan->max_n);
+    }
+    const uint32_t w_many = wave_count(many);
+    if (lane == 0 && w_many) atomicAdd(&sacc[ST_TOO_MANY_N], w_many);
+    if (fin && ma.xflags) ma.xflags[gr] = many ? (uint8_t)CS_X_TOO_MANY_N : (uint8_t)0;
+  }
+
 
   // ---- statistics of this tile (reads that finished here): wave sums -> LDS accumulators
   {

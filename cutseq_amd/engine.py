@@ -39,6 +39,8 @@ class TrimEngine:
                 from .plan import pack_ops
                 ops = pack_ops(op.barcode_ops(), limit=255)
                 capi.check(self.L.cs_plan_set_demux_ops(self._plan_h, mate, index, C.cast(ops, C.c_void_p), len(op.barcodes)))
+        if plan.max_n is not None:
+            capi.check(self.L.cs_plan_set_max_n(self._plan_h, float(plan.max_n)))
         self.n_slots, self.max_reads, self.max_stride = slots, max_reads, max_stride
         try:
             capi.check(self.L.cs_engine_create(self._plan_h, device, slots, max_reads, max_stride,
@@ -88,11 +90,13 @@ class TrimEngine:
         if n and int(lens.max()) > stride:
             raise ValueError(f"len{name}: a read is longer than the row stride {stride}")
 
-    def submit(self, slot: int, seq1, qual1, len1, seq2=None, qual2=None, len2=None, out=None, bc=None):
+    def submit(self, slot: int, seq1, qual1, len1, seq2=None, qual2=None, len2=None, out=None, bc=None, xflags=None):
         """Asynchronous: returns the (still being filled) result arrays; call ``wait(slot)``.
         ``out``: optional (res1, cap2 | None, res2 | None) arrays to fill (e.g. pinned memory).
         ``bc``: optional uint8 array [n] for the barcode index (plans with a demultiplexing op; filled from the mate
-        whose chain holds it)."""
+        whose chain holds it).
+        ``xflags``: optional (mate 1, mate 2 | None) uint8 arrays [n] for ``cs_reads.xflags`` (CS_X_TOO_MANY_N of a plan
+        with ``max_n``)."""
         if seq1.ndim != 2:
             raise ValueError("seq1: expected a 2-D array [n_reads, stride]")
         n, stride = seq1.shape
@@ -115,11 +119,19 @@ class TrimEngine:
         bc_mate = self.plan.demux_mate or 1
         if bc is not None and bc_mate == 1:
             r1.bc = bc.ctypes.data
+        xf1, xf2 = xflags if xflags is not None else (None, None)
+        for x in (xf1, xf2):
+            if x is not None and (x.dtype != np.uint8 or x.shape != (n,) or not x.flags.c_contiguous):
+                raise ValueError(f"xflags: expected C-contiguous uint8 arrays of shape ({n},)")
+        if xf1 is not None:
+            r1.xflags = xf1.ctypes.data
         r2p = None
         if seq2 is not None:
             r2 = self._reads(seq2, qual2, len2, out2)
             if bc is not None and bc_mate == 2:
                 r2.bc = bc.ctypes.data
+            if xf2 is not None:
+                r2.xflags = xf2.ctypes.data
             r2p = C.byref(r2)
         capi.check(self.L.cs_trim_batch(self._eng_h, slot, C.byref(r1), r2p, n, stride))
         return out1, cap2, out2

@@ -65,10 +65,10 @@ def _lib():
         L.csh_fastq_parse.restype = i64
         L.csh_fastq_parse.argtypes = [vp, i64, i64, C.c_uint32, vp, vp, vp, vp, vp]
         L.csh_format_chunk.restype = i64
-        L.csh_format_chunk.argtypes = [C.POINTER(_FormatParams), i64, C.c_uint32] + [vp] * 13 + [vp, vp, vp]
+        L.csh_format_chunk.argtypes = [C.POINTER(_FormatParams), i64, C.c_uint32] + [vp] * 13 + [vp, vp, vp] + [vp, vp]
         L.csh_format_chunk_bins.restype = i64
         L.csh_format_chunk_bins.argtypes = ([C.POINTER(_FormatParams), i64, C.c_uint32] + [vp] * 13 +
-                                            [vp, C.c_int32, vp, vp, vp] + [vp, vp, vp])
+                                            [vp, C.c_int32, vp, vp, vp] + [vp, vp, vp] + [vp, vp])
         _bound = L
     return L
 
@@ -168,6 +168,7 @@ class Chunk:
 
     _owned: tuple = ()  # (arena, buffer) pairs behind the arrays above
     bc: Optional[np.ndarray] = None  # demultiplexing runs: barcode index per record (filled by the device)
+    xflags: Optional[tuple] = None  # runs with --max-n: cs_reads.xflags of (mate 1, mate 2 | None), filled by the device
 
     @property
     def paired(self) -> bool:
@@ -452,9 +453,22 @@ class Lease:
         ARENA.give(self.arr)
 
 
+def _xflags_pointers(chunk: Chunk, xflags):
+    """``xflags``: None, or the (mate 1, mate 2 | None) uint8 arrays of ``cs_reads.xflags`` (TooManyN)."""
+    if xflags is None:
+        return None, None
+    xf1, xf2 = xflags
+    for x in (xf1, xf2):
+        if x is not None and (x.dtype != np.uint8 or x.shape != (chunk.n,) or not x.flags.c_contiguous):
+            raise ValueError(f"xflags: expected C-contiguous uint8 arrays of shape ({chunk.n},)")
+    return xf1.ctypes.data, (xf2.ctypes.data if xf2 is not None and chunk.paired else None)
+
+
 def format_chunk(chunk: Chunk, plan, res1: np.ndarray, cap2: Optional[np.ndarray], res2: Optional[np.ndarray],
-                 copy: bool = True, lease=None):
-    """-> (data[route][mate], counts[route]) with routes 0 trimmed, 1 short, 2 untrimmed.  ``data`` holds
+                 copy: bool = True, lease=None, xflags=None):
+    """-> (data[route][mate], counts[route]) with routes 0 trimmed, 1 short, 2 untrimmed.  ``xflags`` (the per-read
+    ``cs_reads.xflags`` of both mates, or None): pairs TooManyN takes are written nowhere and counted in no route
+    (``chunk.n - sum(counts)`` of them).  ``data`` holds
     ``bytes``; with ``copy=False`` it holds memoryviews into this thread's reusable buffers, valid
     until the thread formats its next chunk -- except the streams flagged in ``lease[route][mate]``,
     which are formatted straight into arena buffers and come back as :class:`Lease` objects."""
@@ -475,6 +489,7 @@ def format_chunk(chunk: Chunk, plan, res1: np.ndarray, cap2: Optional[np.ndarray
                 out_ptrs[r][m] = bufs[r][m].ctypes.data
     out_len = ((C.c_int64 * 2) * 3)()
     counts = (C.c_int64 * 3)()
+    xp1, xp2 = _xflags_pointers(chunk, xflags)
     rc = L.csh_format_chunk(
         C.byref(fp), chunk.n, chunk.stride, _raw_pointer(chunk.raw1), chunk.name_off1.ctypes.data,
         chunk.name_len1.ctypes.data, chunk.seq1.ctypes.data, chunk.qual1.ctypes.data, res1.ctypes.data,
@@ -482,7 +497,7 @@ def format_chunk(chunk: Chunk, plan, res1: np.ndarray, cap2: Optional[np.ndarray
         _raw_pointer(chunk.raw2) if chunk.paired else None,
         chunk.name_off2.ctypes.data if chunk.paired else None, chunk.name_len2.ctypes.data if chunk.paired else None,
         chunk.seq2.ctypes.data if chunk.paired else None, chunk.qual2.ctypes.data if chunk.paired else None,
-        res2.ctypes.data if res2 is not None else None, out_ptrs, out_len, counts)
+        res2.ctypes.data if res2 is not None else None, out_ptrs, out_len, counts, xp1, xp2)
     if rc < 0:
         for row in leased:
             for arr in row:
@@ -515,7 +530,7 @@ def _format_params(chunk: Chunk, plan) -> _FormatParams:
     return fp
 
 
-def format_chunk_bins(chunk: Chunk, plan, res1, cap2, res2, bc: np.ndarray, n_bins: int):
+def format_chunk_bins(chunk: Chunk, plan, res1, cap2, res2, bc: np.ndarray, n_bins: int, xflags=None):
     """Demultiplexed formatting: -> (binned[mate] uint8 array, bin_off[mate][n_bins + 1], bin_counts[n_bins],
     views[route][mate] (routes 1 and 2 in use), counts[route]).  The arrays in ``binned`` are arena buffers
     the caller gives back."""
@@ -533,6 +548,7 @@ def format_chunk_bins(chunk: Chunk, plan, res1, cap2, res2, bc: np.ndarray, n_bi
     bin_counts = np.zeros(n_bins, dtype=np.int64)
     out_len = ((C.c_int64 * 2) * 3)()
     counts = (C.c_int64 * 3)()
+    xp1, xp2 = _xflags_pointers(chunk, xflags)
     rc = L.csh_format_chunk_bins(
         C.byref(fp), chunk.n, chunk.stride, _raw_pointer(chunk.raw1), chunk.name_off1.ctypes.data,
         chunk.name_len1.ctypes.data, chunk.seq1.ctypes.data, chunk.qual1.ctypes.data, res1.ctypes.data,
@@ -541,7 +557,7 @@ def format_chunk_bins(chunk: Chunk, plan, res1, cap2, res2, bc: np.ndarray, n_bi
         chunk.name_off2.ctypes.data if chunk.paired else None, chunk.name_len2.ctypes.data if chunk.paired else None,
         chunk.seq2.ctypes.data if chunk.paired else None, chunk.qual2.ctypes.data if chunk.paired else None,
         res2.ctypes.data if res2 is not None else None, bc.ctypes.data, n_bins, binned_ptrs, bin_off.ctypes.data,
-        bin_counts.ctypes.data, out_ptrs, out_len, counts)
+        bin_counts.ctypes.data, out_ptrs, out_len, counts, xp1, xp2)
     if rc < 0:
         for arr in binned:
             ARENA.give(arr)
@@ -553,14 +569,15 @@ def format_chunk_bins(chunk: Chunk, plan, res1, cap2, res2, bc: np.ndarray, n_bi
 
 
 def finish_chunk(chunk: Chunk, plan, res1, cap2, res2, gz: Sequence[Sequence[Optional[bool]]], level: int = 1,
-                 n_bins: int = 0):
+                 n_bins: int = 0, xflags=None):
     """Worker-thread job of the CLI: format one chunk and turn each wanted stream into what goes to disk:
     one gzip member (bytes), or the plain text in an arena buffer (:class:`Lease`).  ``gz[route][mate]`` is
     True / False for compressed / plain outputs and None where no file is open.  With ``n_bins`` (a
     demultiplexing run, ``chunk.bc`` filled) the trimmed route is split by barcode: streams 3 .. 3 + n_bins - 1.
     -> (blobs[stream][mate], counts per stream)."""
     if n_bins:
-        binned, bin_off, bin_counts, views, counts = format_chunk_bins(chunk, plan, res1, cap2, res2, chunk.bc, n_bins)
+        binned, bin_off, bin_counts, views, counts = format_chunk_bins(chunk, plan, res1, cap2, res2, chunk.bc, n_bins,
+                                                                       xflags=xflags)
         blobs = [[None, None] for _ in range(3 + n_bins)]
         try:
             for r in (1, 2):
@@ -578,7 +595,7 @@ def finish_chunk(chunk: Chunk, plan, res1, cap2, res2, gz: Sequence[Sequence[Opt
                 ARENA.give(arr)
         return blobs, [0, counts[1], counts[2]] + [int(c) for c in bin_counts]
     lease = [[gz[r][m] is False for m in range(2)] for r in range(3)]
-    views, counts = format_chunk(chunk, plan, res1, cap2, res2, copy=False, lease=lease)
+    views, counts = format_chunk(chunk, plan, res1, cap2, res2, copy=False, lease=lease, xflags=xflags)
     blobs = [[None, None] for _ in range(3)]
     for r in range(3):
         for m in range(2):

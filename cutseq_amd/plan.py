@@ -47,6 +47,8 @@ class CutadaptConfig:
         self.indel_tie = abi.CS_TIE_INSERTION      # SURVEY appendix B.2 order
         # extension (BASELINE.json config 5): demultiplex on these inline barcodes (replaces the scheme's inline5)
         self.demux_barcodes = None
+        # cutadapt --max-n (the reference's TODO, run.py:452, 770): TooManyN(max_n) on both mates, None = off
+        self.max_n = None
 
 
 @dataclass
@@ -209,6 +211,7 @@ class TrimPlan:
     use_filter: bool = True
     case_rule: int = abi.CS_CASE_FOLD
     indel_tie: int = abi.CS_TIE_INSERTION
+    max_n: Optional[float] = None  # TooManyN(max_n) filter (cs_plan_set_max_n); None = no such filter
 
     @property
     def paired(self) -> bool:
@@ -428,6 +431,7 @@ def compile_single(barcode: BarcodeConfig, settings: CutadaptConfig, untrimmed_r
         select_rule=getattr(settings, "select_rule", abi.CS_SELECT_LEFTMOST),
         case_rule=getattr(settings, "case_rule", abi.CS_CASE_FOLD),
         indel_tie=getattr(settings, "indel_tie", abi.CS_TIE_INSERTION),
+        max_n=getattr(settings, "max_n", None),
     )
 
 
@@ -509,6 +513,7 @@ def compile_paired(barcode: BarcodeConfig, settings: CutadaptConfig, untrimmed_r
         select_rule=getattr(settings, "select_rule", abi.CS_SELECT_LEFTMOST),
         case_rule=getattr(settings, "case_rule", abi.CS_CASE_FOLD),
         indel_tie=getattr(settings, "indel_tie", abi.CS_TIE_INSERTION),
+        max_n=getattr(settings, "max_n", None),
     )
 
 

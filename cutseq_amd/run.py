@@ -87,6 +87,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Extension: one process per GPU (N processes, rank r on GPU r or on the r-th entry of "
                         "CUTSEQ_DEVICES); the input is split at record boundaries, the output parts are concatenated "
                         "in rank order. Output is identical to the one-process run.")
+    p.add_argument("--max-n", type=float, default=None, metavar="COUNT",
+                   help="Extension (cutadapt's option; a TODO of the reference): discard reads with more than COUNT 'N' "
+                        "bases. If COUNT is a number between 0 and 1, it is interpreted as a fraction of the read "
+                        "length. A pair is discarded if either read has too many N.")
     p.add_argument("--rank-spec", type=str, help=argparse.SUPPRESS)  # a child of --ranks: its share of the run
     p.add_argument("--demux-barcodes", type=str, metavar="FILE",
                    help="Extension: demultiplex on the 5' inline barcode. FILE lists 'name<TAB>sequence' per line (all as "
@@ -147,6 +151,9 @@ def resolve_args(args):
     if len(inputs) > 2:
         _fail("Input file can not be more than two.")
     args.adapter_scheme = resolve_scheme(args)
+    max_n = getattr(args, "max_n", None)
+    if max_n is not None and not max_n >= 0:  # (NaN fails the comparison too)
+        _fail(f"--max-n: the count must not be negative (got {max_n}).")
     if not inputs:
         # the reference dies with an IndexError here (run.py:1079-1083); same exit class, clearer message
         _fail("Input file is required.")
@@ -187,6 +194,7 @@ def settings_from_args(args) -> CutadaptConfig:
     st.force_trim_min_length = args.force_trim_min_length
     st.force_anywhere = args.force_anywhere
     st.select_rule = abi.CS_SELECT_LEFTMOST if args.cutadapt_selection == "4" else abi.CS_SELECT_SCORE
+    st.max_n = getattr(args, "max_n", None)
     if getattr(args, "demux", None) is not None:
         st.demux_barcodes = list(args.demux[1])
     return st
@@ -296,10 +304,18 @@ class _DeviceWorker(threading.Thread):
                 if self.tp.demux is not None:
                     owned.append(fastq.PINNED.take(chunk.n))
                     chunk.bc = owned[-1][: chunk.n]
+                if self.tp.max_n is not None:  # TooManyN flags of both mates
+                    owned.append(fastq.PINNED.take(chunk.n))
+                    xf1 = owned[-1][: chunk.n]
+                    xf2 = None
+                    if paired:
+                        owned.append(fastq.PINNED.take(chunk.n))
+                        xf2 = owned[-1][: chunk.n]
+                    chunk.xflags = (xf1, xf2)
                 chunk._owned = chunk._owned + tuple((fastq.PINNED, b) for b in owned)
                 slot = n % self.SLOTS
                 res = self.engine.submit(slot, chunk.seq1, chunk.qual1, chunk.len1, chunk.seq2, chunk.qual2,
-                                         chunk.len2, out=(out1, cap2, out2), bc=chunk.bc)
+                                         chunk.len2, out=(out1, cap2, out2), bc=chunk.bc, xflags=chunk.xflags)
                 inflight.append((k, slot, chunk, res))
                 n += 1
             while inflight:
@@ -387,9 +403,10 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
     def finish(chunk, r1, cap2, r2):
         """Pool job: records -> bytes on their way to disk; also this chunk's share of the report."""
         try:
-            blobs, counts = fastq.finish_chunk(chunk, tp, r1, cap2, r2, gz, n_bins=n_bins)
+            blobs, counts = fastq.finish_chunk(chunk, tp, r1, cap2, r2, gz, n_bins=n_bins, xflags=chunk.xflags)
             part = report.new_totals()
-            report.account_chunk(part, tp, chunk.len1, r1, chunk.len2 if paired else None, r2 if paired else None)
+            report.account_chunk(part, tp, chunk.len1, r1, chunk.len2 if paired else None, r2 if paired else None,
+                                 xflags=chunk.xflags)
             part["routes"] = counts
             return blobs, part
         finally:

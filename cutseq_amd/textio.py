@@ -820,6 +820,7 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
                 totals["routes"][q] += int(res.route_count[q])
         for m in range(2 if paired else 1):
             totals["written_bp"][m] += int(res.written_bp[m])
+        totals["too_many_n"] += int(res.n_too_many_n)
         sizes = item.sizes if item.sizes is not None else res.route_bytes
         jobs = []
         for m in range(2 if paired else 1):

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CS_ABI_VERSION 6
+#define CS_ABI_VERSION 7
 #define CS_MAX_ADAPTER 128 /* longest adapter sequence an op can carry          */
 #define CS_MAX_OPS 24      /* longest per-mate op chain                           */
 #define CS_MAX_STRIDE 1536 /* longest row the LDS tile can stage (64 rows/block) */
@@ -115,6 +115,11 @@ enum {
   CS_F_AMBIGUOUS = 0x80  /* CS_OP_DEMUX: more than one barcode matched this read   */
 };
 
+/* per-read extra flag bits (cs_reads.xflags; cs_result.flags has no free bit) */
+enum {
+  CS_X_TOO_MANY_N = 0x01 /* TooManyN(count) of cs_plan_set_max_n is true for this mate (cutadapt --max-n) */
+};
+
 typedef struct cs_op {
   uint8_t kind;          /* CS_OP_*                                                   */
   uint8_t align_flags;   /* ADAPTER: CS_WHERE_*                                       */
@@ -180,6 +185,7 @@ typedef struct cs_stats {
   uint64_t n_exact_dp;   /* reads that needed the exact DP (diagnostic)        */
   uint64_t n_refiltered; /* reads the existence-only scan of a rare adapter op could not clear (diagnostic)   */
   uint64_t op_matched[CS_MAX_OPS]; /* AdapterCutter.with_adapters per op         */
+  uint64_t n_too_many_n; /* reads of this mate with CS_X_TOO_MANY_N (a per-mate count, not a pair count) */
 } cs_stats;
 
 /* one mate's device- or host-resident arrays */
@@ -190,6 +196,8 @@ typedef struct cs_reads {
   cs_result *out;
   cs_cap2 *cap2; /* may be NULL */
   uint8_t *bc;   /* may be NULL; CS_OP_DEMUX: index of the barcode that matched, CS_DEMUX_NONE otherwise */
+  uint8_t *xflags; /* may be NULL; CS_X_* bits per read (0 where none applies); not written by a plan without
+                      cs_plan_set_max_n (its kernels are the ones without the filter) */
 } cs_reads;
 
 typedef struct cs_plan cs_plan;
@@ -221,6 +229,13 @@ int cs_plan_set_demux(cs_plan *plan, int mate, int op_index, const uint16_t *tab
  * the device runs the ops of those candidates on the read and merges the outcomes by the rule of the table entries
  * above.  Reads of such a plan all pass through the resolve kernel: slower than the table form, same results. */
 int cs_plan_set_demux_ops(cs_plan *plan, int mate, int op_index, const cs_op *ops, int n_ops);
+
+/* cutadapt's --max-n filter, TooManyN(count), on both mates (reference TODO, cutseq/run.py:452, 770): a read whose
+ * final interval seq[start:stop] holds too many 'N' / 'n' bases gets CS_X_TOO_MANY_N.  count < 1 is a proportion:
+ * stop > start and n / (stop - start) > count (IEEE double); count >= 1 is a number: n > count.  INFINITY never fires.
+ * The text path discards such a pair (pair filter "any") after TooShort and before IsUntrimmedAny.  Called before
+ * cs_engine_create, like cs_plan_set_demux; never called: no filter.  CS_ERR_ARG for a negative or NaN count. */
+int cs_plan_set_max_n(cs_plan *plan, double count);
 
 /* One engine per GPU (one per process in the multi-GPU layout; replaces
  * make_runner(inpaths, cores=threads), run.py:436,753). Uploads the op tables, owns a
@@ -319,7 +334,7 @@ typedef struct cs_text_result {
   uint32_t max_len;           /* longest read of the batch                                                      */
   uint32_t n_records;
   uint32_t route_count[3];    /* records (pairs) per route (n_bins > 0: [0] = all barcodes together; likewise below) */
-  uint32_t _pad;
+  uint32_t n_too_many_n;      /* pairs discarded by TooManyN (cs_plan_set_max_n), in no route                    */
   uint64_t route_bytes[3][2]; /* [route][mate]                                                                  */
   uint64_t out_bytes[2];      /* per mate: sum over the routes = what cs_text_fetch copies                      */
   uint64_t written_bp[2];     /* per mate: bases of the records of route 0 (cutadapt's written_bp)              */
