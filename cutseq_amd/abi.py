@@ -149,7 +149,8 @@ class cs_text_params(C.Structure):
         ("suffix2", C.c_char_p * 2),
         ("n_bins", C.c_uint32),
         ("fasta_out", C.c_uint8),
-        ("_reserved", C.c_uint8 * 3),
+        ("fasta_routes", C.c_uint8),
+        ("_reserved", C.c_uint8 * 2),
     ]
 
 

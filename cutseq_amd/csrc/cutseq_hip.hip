@@ -1370,6 +1370,7 @@ struct cs_text {
   uint32_t seg_blocks = 0, fmt_blocks = 0;
   bool needs_cap2 = false;
   bool compress = false;      // the output streams leave the device as gzip members
+  bool mixed_formats = false; // the streams differ in format (tp.fasta_routes): format_copy decides per record
   bool literal_only = false;  // ... from literal-only blocks (CUTSEQ_GPU_LZ=0: no run / record-name matches)
   uint32_t max_chunks = 0;
   uint32_t n_routes = 3;      // 3 + cs_text_params.n_bins
@@ -1432,7 +1433,19 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
   t->tp.has_umi = params->has_umi ? 1 : 0;
   t->tp.untrimmed_filter = params->untrimmed_filter ? 1 : 0;
   t->tp.reverse_complement = params->reverse_complement ? 1 : 0;
-  t->tp.fasta_out = params->fasta_out ? 1 : 0;
+  {
+    // which (route class, mate) streams exist at all: a bit for one that does not is the caller's mistake
+    const uint8_t exist = (uint8_t)((eng->paired ? 0xffu : 0x55u) & (params->n_bins ? 0xffu : 0x3fu));
+    if (params->fasta_routes & ~exist) {
+      delete t;
+      return fail(CS_ERR_ARG, "fasta_routes = 0x%02x names a stream this plan does not have (mate 2 of a single-end plan, "
+                  "or the barcode class without bins)", params->fasta_routes);
+    }
+    const uint8_t mask = params->fasta_out ? exist : params->fasta_routes;
+    // one format over all streams: every bit set or none, and format_copy keeps its uniform instance
+    t->mixed_formats = mask != 0 && mask != exist;
+    t->tp.fasta_routes = mask == exist ? 0xffu : mask;
+  }
   t->tp.max_n = eng->max_n ? 1 : 0;
   t->tp.flag_too_short = CS_F_TOO_SHORT;
   t->tp.flag_untrimmed = CS_F_UNTRIMMED;
@@ -1717,7 +1730,11 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
     }
     const unsigned long long items = (unsigned long long)n_records * mates;
     const unsigned long long want = (items * 32ull + 255ull) / 256ull;
-    hipLaunchKernelGGL(cstext::format_copy, dim3((uint32_t)(want > 32768ull ? 32768ull : want)), dim3(256), 0, rs, fa, t->tp);
+    const dim3 copy_grid((uint32_t)(want > 32768ull ? 32768ull : want));
+    if (t->mixed_formats)
+      hipLaunchKernelGGL(cstext::format_copy<true>, copy_grid, dim3(256), 0, rs, fa, t->tp);
+    else
+      hipLaunchKernelGGL(cstext::format_copy<false>, copy_grid, dim3(256), 0, rs, fa, t->tp);
     HIP_TRY(hipGetLastError());
     if (t->compress) {
       for (int m = 0; m < mates; ++m) {
@@ -1729,8 +1746,8 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
         da.info = s.d_chunk[m];
         da.max_chunks = t->max_chunks;
         da.gate = &s.d_meta->err;
-        da.marker = t->tp.fasta_out ? '>' : '@';
-        da.lines = t->tp.fasta_out ? 2u : 4u;
+        da.fasta_classes = 0;
+        for (uint32_t c = 0; c < 4u; ++c) da.fasta_classes |= ((t->tp.fasta_routes >> (2u * c + m)) & 1u) << c;
         da.literal_only = t->literal_only ? 1u : 0u;
         hipLaunchKernelGGL(csdefl::deflate_chunks, dim3(t->max_chunks), dim3(256), 0, rs, da);
         csdefl::LayoutArgs la;

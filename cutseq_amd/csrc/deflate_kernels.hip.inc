@@ -399,7 +399,9 @@ struct DeflateArgs {
   ChunkInfo *info;
   uint32_t max_chunks;
   const unsigned long long *gate;
-  uint32_t marker, lines;              // a record starts with this byte and has this many lines ('@' 4, FASTA: '>' 2)
+  uint32_t fasta_classes;              // bit c: the streams of route class c (0 .. 2, 3 = every barcode's) are FASTA.  It
+                                       // says where a record starts and how far back its predecessor's name lies:
+                                       // '>' and 2 lines, else '@' and 4 (every chunk belongs to one route)
   uint32_t literal_only;               // 1: no LZ77 stage (CUTSEQ_GPU_LZ=0: round 3's blocks)
 };
 
@@ -461,6 +463,8 @@ __global__ void __launch_bounds__(256) deflate_chunks(DeflateArgs a) {
     }
   }
   if (route == kNone) return;  // beyond the last chunk
+  const bool fasta = (a.fasta_classes >> min(route, 3u)) & 1u;
+  const uint32_t marker = fasta ? '>' : '@', lines = fasta ? 2u : 4u;
   const uint32_t raw_len = (uint32_t)min((unsigned long long)kChunk, rbytes - (unsigned long long)b * kChunk);
   const uint8_t *stream = a.text + base;  // the route's stream: matches may reach back into the chunk in front
   const long long chunk0 = (long long)b * kChunk;
@@ -530,7 +534,7 @@ __global__ void __launch_bounds__(256) deflate_chunks(DeflateArgs a) {
   Mask128 covered = {0, 0};
   if (lz) {
     // (block-uniform branch: the line index needs every thread at its barriers)
-    const SliceMasks m = slice_masks(w, prev_byte == 0x100u ? (~w[0] & 0xffu) : prev_byte, n_valid, a.marker);
+    const SliceMasks m = slice_masks(w, prev_byte == 0x100u ? (~w[0] & 0xffu) : prev_byte, n_valid, marker);
     uint32_t all_lines;
     const uint32_t lines_before = cstext::block_scan_256((uint32_t)__popcll(m.nl.lo) + (uint32_t)__popcll(m.nl.hi), all_lines, sh);
     {
@@ -540,7 +544,7 @@ __global__ void __launch_bounds__(256) deflate_chunks(DeflateArgs a) {
     __syncthreads();
     const bool chunk_starts_line = chunk0 == 0 || src[-1] == '\n';
     if (n_valid)
-      find_matches(src, lo, n_valid, m, prev_byte == 0x100u || prev_byte == '\n', lines_before, u.nl_pos, a.lines, chunk_starts_line,
+      find_matches(src, lo, n_valid, m, prev_byte == 0x100u || prev_byte == '\n', lines_before, u.nl_pos, lines, chunk_starts_line,
                    [&](uint32_t at, uint32_t len, uint32_t dist) {
                      my_matches[n_matches++] = at | ((len - 3u) << 7) | ((dist - 1u) << 15);
                      const Mask128 r = m128_range(at, len);

@@ -65,7 +65,8 @@ struct TextParams {  // constant per engine
   uint8_t suffix[2][2][kSuffixMax];  // [mate][which]: SuffixRemover literals, applied in order
   uint8_t suffix_len[2][2];
   uint8_t demux_mate;                // n_bins > 0: the mate (0 / 1) whose chain holds the demultiplexing op
-  uint8_t fasta_out;                 // output records are ">id\nseq\n" (no qualities to write)
+  uint8_t fasta_routes;              // bit 2 * class + mate: that stream's records are ">id\nseq\n" (class = route, 3 for
+                                     // every barcode's route).  cs_text_create folds cs_text_params.fasta_out into it
   uint8_t max_n;                     // the plan has TooManyN: FormatArgs.xf holds its per-read flags
   uint8_t _pad;
 };
@@ -356,7 +357,7 @@ struct FormatArgs {
   uint32_t n, stride;
   uint32_t *blk;           // [n_blocks][6] block sums, then their exclusive scan (column = route * 2 + mate)
   unsigned long long *totals;  // [6] column sums
-  uint32_t *dst[2];        // per mate: byte offset of every record's output inside the mate's buffer | route << 30
+  uint32_t *dst[2];        // per mate: byte offset of every record's output inside the mate's buffer | route class << 30
   uint8_t *out[2];
   TextMeta *meta;
   // demultiplexing plans (TextParams.n_bins > 0): routes 0 .. 2 + n_bins
@@ -414,6 +415,13 @@ __device__ __forceinline__ uint32_t xflags_of(const FormatArgs &a, uint32_t m, u
   return slot != kNotLong ? a.lres[m][slot].xflags : a.xf[m][r];
 }
 
+// the class of a route as TextParams.fasta_routes counts them
+__device__ __forceinline__ uint32_t route_class(uint32_t route) { return route < 3u ? route : 3u; }
+
+__device__ __forceinline__ bool fasta_stream(const TextParams &tp, uint32_t cls, uint32_t m) {
+  return (tp.fasta_routes >> (2u * cls + m)) & 1u;
+}
+
 __device__ __forceinline__ RecordShape record_shape(const FormatArgs &a, const TextParams &tp, uint32_t r) {
   RecordShape s;
   const ReadView r1 = read_view(a, 0, r);
@@ -434,9 +442,11 @@ __device__ __forceinline__ RecordShape record_shape(const FormatArgs &a, const T
     if (bc != CS_DEMUX_NONE) s.route = 3u + bc;
   }
   // '@' id tag '\n' seq "\n+\n" qual '\n'   or, without qualities,   '>' id tag '\n' seq '\n'
-  const uint32_t per_base = tp.fasta_out ? 1u : 2u, fixed = tp.fasta_out ? 3u : 6u;
-  s.len[0] = (a.idr[0][r] >> 16) + tag + per_base * (r1.stop - r1.start) + fixed;
-  s.len[1] = tp.paired ? (a.idr[1][r] >> 16) + tag + per_base * (r2.stop - r2.start) + fixed : 0u;
+  // -- which of the two goes by the file the (route, mate) stream is written to
+  const uint32_t cls = route_class(s.route);  // (kRouteDiscard counts as 3 here: nobody looks at its sizes)
+  const bool fa1 = fasta_stream(tp, cls, 0), fa2 = fasta_stream(tp, cls, 1);
+  s.len[0] = (a.idr[0][r] >> 16) + tag + (fa1 ? 1u : 2u) * (r1.stop - r1.start) + (fa1 ? 3u : 6u);
+  s.len[1] = tp.paired ? (a.idr[1][r] >> 16) + tag + (fa2 ? 1u : 2u) * (r2.stop - r2.start) + (fa2 ? 3u : 6u) : 0u;
   return s;
 }
 
@@ -597,7 +607,7 @@ __global__ void __launch_bounds__(256) format_offsets_bins(FormatArgs a, TextPar
     for (uint32_t m = 0; m < 2u; ++m) {
       uint32_t at = base[s.route * 2u + m] + mine[m];
       for (uint32_t w = 0; w < wave; ++w) at += wsum[w][s.route * 2u + m];
-      if (m == 0 || tp.paired) a.dst[m][r] = at;
+      if (m == 0 || tp.paired) a.dst[m][r] = at | (route_class(s.route) << 30);  // (cs_text_create keeps a mate's output below 1 GiB)
     }
   }
   uint32_t kept_bp[2] = {0, 0};
@@ -651,7 +661,10 @@ __device__ __forceinline__ uint8_t complement(uint8_t c) {
   }
 }
 
-// 32 lanes per output record: byte j of the record -> the source byte it copies
+// 32 lanes per output record: byte j of the record -> the source byte it copies.  kMixed: the output files name
+// different formats, so FASTA or FASTQ is a property of the record (its route class, from the top bits of its dst,
+// and its mate); otherwise the one format of the whole grid, a scalar as before streams had formats of their own.
+template <bool kMixed>
 __global__ void __launch_bounds__(256) format_copy(FormatArgs a, TextParams tp) {
   if (a.meta->err != ~0ull) return;
   const uint32_t lane = threadIdx.x & 31u;
@@ -683,12 +696,14 @@ __global__ void __launch_bounds__(256) format_copy(FormatArgs a, TextParams tp) 
     const uint32_t L = me.stop - me.start;
     const uint8_t *seq = me.seq, *qual = me.qual;
     const bool rc = tp.reverse_complement && !tp.paired;
-    uint8_t *out = a.out[m] + (a.dst[m][r] & 0x3fffffffu);
+    const uint32_t dst = a.dst[m][r];
+    const bool fasta = kMixed ? fasta_stream(tp, dst >> 30, m) : tp.fasta_routes != 0;
+    uint8_t *out = a.out[m] + (dst & 0x3fffffffu);
     // segment ends: '@' | id | tag | '\n' | seq | "\n+\n" | qual | '\n'
     // (FASTA output: the record ends with the line end behind the sequence -- byte e_seq, which the '+' branch below
     // writes as '\n')
     const uint32_t e_id = 1u + id_len, e_tag = e_id + tag, e_seq = e_tag + 1u + L, e_plus = e_seq + 3u;
-    const uint32_t total = tp.fasta_out ? e_seq + 1u : e_plus + L + 1u;
+    const uint32_t total = fasta ? e_seq + 1u : e_plus + L + 1u;
     // Stretch by stretch (round 5): the id, the bases and the qualities are copied four bytes per lane and step --
     // unaligned dword loads and stores, uniform control flow --, the UMI tag and the fixed bytes by single lanes.  (A byte
     // per lane and step, every byte picked by an eight-way chain of comparisons, moved 134 MB per batch of 262 144 pairs
@@ -723,11 +738,11 @@ __global__ void __launch_bounds__(256) format_copy(FormatArgs a, TextParams tp) 
     Held h_seq{0u, 0u, 0u}, h_qual{0u, 0u, 0u};
     if (!rc) {
       h_seq = load(seq + me.start, L);
-      if (!tp.fasta_out) h_qual = load(qual + me.start, L);
+      if (!fasta) h_qual = load(qual + me.start, L);
     }
     uint8_t tag_byte = (uint8_t)'_';  // (tags of up to 32 bytes: one per lane; longer ones finish in the loop below)
     if (lane > 0 && lane < tag) tag_byte = lane <= t1 ? tag1[lane - 1u] : tag2[lane - 1u - t1];
-    if (lane == 0) out[0] = tp.fasta_out ? '>' : '@';
+    if (lane == 0) out[0] = fasta ? '>' : '@';
     store(out + 1u, id, id_len, h_id);
     if (lane < tag) out[e_id + lane] = tag_byte;
     for (uint32_t t = lane + 32u; t < tag; t += 32u) out[e_id + t] = t <= t1 ? tag1[t - 1u] : tag2[t - 1u - t1];
@@ -737,7 +752,7 @@ __global__ void __launch_bounds__(256) format_copy(FormatArgs a, TextParams tp) 
     } else {
       for (uint32_t t = lane; t < L; t += 32u) out[e_tag + 1u + t] = complement(seq[me.stop - 1u - t]);
     }
-    if (tp.fasta_out) {
+    if (fasta) {
       if (lane == 2) out[e_seq] = '\n';
     } else {
       if (lane >= 2 && lane <= 4) out[e_seq + lane - 2u] = lane == 3 ? (uint8_t)'+' : (uint8_t)'\n';

@@ -339,6 +339,17 @@ class RankFailure(RuntimeError):
         self.code = code
 
 
+def part_name(name, r):
+    """The file rank ``r`` writes for the output file ``name``: rank 0 the final file itself, the others a part beside
+    it that keeps the format's and the container's ending (every file's records go by its own name,
+    ``textio.output_formats``, so a part must say what its file says)."""
+    if not name or r == 0:
+        return name
+    from .textio import format_endings
+    kind, ending = format_endings(name)
+    return f"{name}.rank{r}.part{kind}{ending}"
+
+
 def _run_ranks(argv: List[str], args, world: int, shares, t0: float, how: str) -> dict:
     want = os.environ.get("CUTSEQ_DEVICES")
     devices = [int(x) for x in want.split(",")] if want else list(range(world))
@@ -352,12 +363,6 @@ def _run_ranks(argv: List[str], args, world: int, shares, t0: float, how: str) -
     # every rank gets its share of the host threads (N pools of all cores each would oversubscribe the host N times)
     per_rank = max(1, _host_threads(args) // world)
     child_argv = _strip_option(_strip_option(_strip_option(argv, "--ranks"), "--threads"), "-t") + ["-t", str(per_rank)]
-
-    def part_name(name, r):  # rank 0 writes the final files themselves; a part keeps the container's ending
-        if not name or r == 0:
-            return name
-        ending = next((e for e in (".gz", ".bz2", ".xz", ".zst") if name.endswith(e)), "")
-        return f"{name}.rank{r}.part{ending}"
 
     try:
         for r in range(world):

@@ -590,10 +590,10 @@ class TextWorker(threading.Thread):
     SLOTS = 3
 
     def __init__(self, tp, device: int, done: "queue.Queue", chunk_reads: int, compress: bool = False, bins: int = 0,
-                 fasta: bool = False):
+                 fasta_routes: int = 0):
         super().__init__(daemon=True, name=f"cutseq-gpu{device}")
         self.tp, self.device, self.done, self.chunk_reads, self.compress = tp, device, done, chunk_reads, compress
-        self.fasta = fasta  # the records leave as FASTA
+        self.fasta_routes = fasta_routes  # bit 2 * class + mate: that stream's records leave as FASTA
         self.bins = bins  # demultiplexing: one route per barcode behind the three ordinary ones
         self.inbox: "queue.Queue" = queue.Queue(maxsize=self.SLOTS)
         self.engine = self.text = None
@@ -622,7 +622,7 @@ class TextWorker(threading.Thread):
         self.capacity = max(self.capacity, int(text_bytes * 1.25) + (1 << 20))
         self.text = textpath.TextEngine(self.engine, slots=self.SLOTS, max_text_bytes=self.capacity,
                                         max_records=self.chunk_reads, stride=self.stride, compress=self.compress,
-                                        bins=self.bins, fasta=self.fasta)
+                                        bins=self.bins, fasta_routes=self.fasta_routes)
         self.submitted = 0
 
     def _submit(self, inflight: deque, k: int, b1: TextBlock, b2: Optional[TextBlock]):
@@ -710,19 +710,21 @@ _FASTA_EXT = (".fasta", ".fa", ".fna", ".csfasta", ".csfa")
 _FASTQ_EXT = (".fastq", ".fq")
 
 
+def format_endings(name: str):
+    """-> (format extension, compression suffix) of an output file's name as they are written in it, "" where the
+    name has none: "x.FA.gz" -> (".FA", ".gz")."""
+    low = name.lower()
+    container = next((ext for ext in (".gz", ".bz2", ".xz", ".zst") if low.endswith(ext)), "")
+    stem = low[: len(low) - len(container)]
+    kind = next((ext for ext in _FASTA_EXT + _FASTQ_EXT if stem.endswith(ext)), "")
+    return name[len(stem) - len(kind):len(stem)], name[len(stem):]
+
+
 def format_of_name(name: str) -> Optional[str]:
     """dnaio's rule for output files: the format goes by the extension in front of a compression suffix; None when
     the name says nothing (the input's format then decides)."""
-    low = name.lower()
-    for ext in (".gz", ".bz2", ".xz", ".zst"):
-        if low.endswith(ext):
-            low = low[: -len(ext)]
-            break
-    if low.endswith(_FASTA_EXT):
-        return "fasta"
-    if low.endswith(_FASTQ_EXT):
-        return "fastq"
-    return None
+    kind = format_endings(name)[0].lower()
+    return "fasta" if kind in _FASTA_EXT else ("fastq" if kind in _FASTQ_EXT else None)
 
 
 def output_format(names, has_qualities: bool) -> bool:
@@ -737,6 +739,42 @@ def output_format(names, has_qualities: bool) -> bool:
     if len(kinds) > 1:
         raise ValueError("the output files name different formats (FASTA and FASTQ): one format per run")
     return kinds == {"fasta"}
+
+
+def output_formats(groups, has_qualities: bool) -> int:
+    """-> ``cs_text_params.fasta_routes``: every output file in the format ITS name asks for, as the reference's
+    ``OutputFiles.open_record_writer`` hands each name to dnaio on its own (cutseq/run.py:437-441, 449, 465, 754-758).
+
+    ``groups``: the files by the stream they receive -- [trimmed, too short, untrimmed, barcode 0, barcode 1, ...],
+    each a list of names by mate (None / "": no such file), AFTER any swap of the mates' files: the format goes with
+    the file.  Bit ``2 * class + mate`` of the result is set when that stream leaves as FASTA; every barcode's files are
+    class 3 and must agree per mate (their names come from one template).  Per file the rule of
+    :func:`output_format`: a FASTA / FASTQ extension decides, any other name follows the input; a FASTQ file of an
+    input without qualities is an error that names the file.
+
+    A stream without a file is formatted and dropped.  It follows the input like a name that says nothing, unless
+    every file there is asks for FASTA: then it is FASTA too, so that a run whose files agree stays a run of one
+    format on the device (and the dropped records are the shorter ones)."""
+    follow = "fastq" if has_qualities else "fasta"
+    named = {format_of_name(n) or follow for group in groups for n in list(group)[:2] if n}
+    absent = "fasta" if named == {"fasta"} else follow
+    mask = 0
+    bins = [None, None]  # class 3: the format the first barcode's file of a mate asked for
+    for q, group in enumerate(groups):
+        for m, name in enumerate(list(group)[:2]):
+            kind = (format_of_name(name) or follow) if name else absent
+            if kind == "fastq" and not has_qualities:
+                raise fastq.FastqFormatError(
+                    "Output format cannot be FASTQ since no quality values are available: the input is FASTA "
+                    f"and the output file {name!r} is named as FASTQ (name it .fasta / .fa)")
+            if q >= 3 and name:
+                if bins[m] is not None and bins[m] != kind:
+                    raise ValueError(f"the barcodes' output files of mate {m + 1} name different formats "
+                                     f"({name!r} is {kind.upper()}): all bins of a mate share one format")
+                bins[m] = kind
+            if kind == "fasta":
+                mask |= 1 << (2 * min(q, 3) + m)
+    return mask
 
 
 def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
@@ -767,7 +805,15 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         compress = bool(names_all) and all(n != "-" and codec.container_of_name(n) == "gzip" for n in names_all) and os.environ.get("CUTSEQ_GPU_DEFLATE", "1") != "0"
         if r2 is not None and r1.fasta != r2.fasta:
             raise fastq.FastqFormatError("the two input files are in different formats (one FASTA, one FASTQ)")
-        fasta_out = output_format(names_all, has_qualities=not r1.fasta)
+        # the files by the stream they receive: paired --auto-rc on a '-' library swaps the mates' trimmed files
+        swap = paired and tp.swap_outputs
+        trimmed_names = list(args.output_file) if not n_bins else [None] * len(args.output_file)
+        name_groups = [trimmed_names[::-1] if swap else trimmed_names, list(args.short_file or []),
+                       list(args.untrimmed_file or [])] + [list(names)[::-1] if swap else list(names) for names in bin_files]
+        name_groups = [(g + [None, None])[:2 if paired else 1] for g in name_groups]  # one entry per stream there is
+        # (a demultiplexing plan without files for its barcodes: their streams are dropped, and are of class 3 all the same)
+        no_bin_files = [[None] * (2 if paired else 1)] if n_bins and not bin_files else []
+        fasta_routes = output_formats(name_groups + no_bin_files, has_qualities=not r1.fasta)
 
         def mk(names):
             group = []
@@ -777,13 +823,7 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
                     opened.append(group[-1])
             return group
 
-        trimmed = mk(args.output_file) if not n_bins else [None] * len(args.output_file)
-        if paired and tp.swap_outputs:
-            trimmed = trimmed[::-1]
-        outs = [trimmed, mk(args.short_file), mk(args.untrimmed_file)]
-        for names in bin_files:
-            files = mk(names)
-            outs.append(files[::-1] if paired and tp.swap_outputs else files)
+        outs = [mk(names) for names in name_groups]
     except BaseException:
         r1.close()
         if r2 is not None:
@@ -800,7 +840,7 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         from .run import _phase
         _phase("readers and writers open")
     done: "queue.Queue" = queue.Queue()
-    workers = [TextWorker(tp, dev, done, chunk_reads, compress, n_bins, fasta_out) for dev in devices]
+    workers = [TextWorker(tp, dev, done, chunk_reads, compress, n_bins, fasta_routes) for dev in devices]
     if n_bins:
         totals["routes"] += [0] * n_bins
     budget = threading.Semaphore(2 * len(workers) * TextWorker.SLOTS + 2)  # batches between reader and disk

@@ -325,7 +325,13 @@ typedef struct cs_text_params {
   uint8_t fasta_out;          /* records leave as FASTA (">id\nsequence\n"): the input had no qualities -- what
                                  runner.input_file_format().has_qualities() tells OutputFiles, cutseq/run.py:437-441,
                                  754-758 -- or the output files are named .fasta / .fa                              */
-  uint8_t _reserved[3];
+  uint8_t fasta_routes;       /* per-stream form of fasta_out, for output files that name different formats: bit
+                                 2 * class + mate (mate 0 / 1) set = that stream's records leave as FASTA.  class 0 =
+                                 trimmed, 1 = too short, 2 = untrimmed, 3 = the routes of all barcodes (n_bins > 0).  A
+                                 stream is FASTA when fasta_out is set or its bit is; 0 = fasta_out alone decides.  A
+                                 bit of a stream the plan does not have (mate 2 of a single-end plan, class 3 without
+                                 bins) is CS_ERR_ARG                                                                 */
+  uint8_t _reserved[2];
 } cs_text_params;
 
 typedef struct cs_text_result {
