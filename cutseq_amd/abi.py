@@ -136,6 +136,8 @@ class cs_reads(C.Structure):
 
 
 CS_TEXT_OK, CS_TEXT_ERR_MALFORMED, CS_TEXT_ERR_TOO_LONG, CS_TEXT_ERR_IDS_DIFFER, CS_TEXT_ERR_LINE_COUNT = 0, 1, 2, 3, 4
+CS_TEXT_ERR_INFO_MISMATCH, CS_TEXT_ERR_INFO_OVERFLOW = 5, 6
+CS_INFO_ON, CS_INFO_GZIP, CS_INFO_NO_QUAL = 1, 2, 4  # cs_text_params.info
 
 
 class cs_text_params(C.Structure):
@@ -150,7 +152,8 @@ class cs_text_params(C.Structure):
         ("n_bins", C.c_uint32),
         ("fasta_out", C.c_uint8),
         ("fasta_routes", C.c_uint8),
-        ("_reserved", C.c_uint8 * 2),
+        ("info", C.c_uint8),
+        ("_reserved", C.c_uint8 * 1),
     ]
 
 

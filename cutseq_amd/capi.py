@@ -19,6 +19,7 @@ EXPORTS = (
     "cs_stats_fetch", "cs_last_kernel_ms", "cs_last_kernel_split_ms", "cs_kernel_time_totals", "cs_alloc_pinned", "cs_alloc_pinned_huge", "cs_free_pinned", "cs_alloc_device",
     "cs_free_device", "cs_copy_to_device", "cs_copy_to_host",
     "cs_text_create", "cs_text_destroy", "cs_text_submit", "cs_text_wait", "cs_text_routes", "cs_text_fetch",
+    "cs_text_info", "cs_text_fetch_info",
 )
 
 
@@ -113,6 +114,10 @@ def load() -> C.CDLL:
     L.cs_text_routes.argtypes = [vp, u32, vp, vp, vp]
     L.cs_text_fetch.restype = i32
     L.cs_text_fetch.argtypes = [vp, u32, vp, vp]
+    L.cs_text_info.restype = i32
+    L.cs_text_info.argtypes = [vp, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.cs_text_fetch_info.restype = i32
+    L.cs_text_fetch_info.argtypes = [vp, u32, vp]
     if L.cs_abi_version() != abi.CS_ABI_VERSION:
         raise HipUnavailable(f"ABI mismatch: library {L.cs_abi_version()} vs python {abi.CS_ABI_VERSION}")
     _lib = L

@@ -22,6 +22,7 @@
 #include "long_kernel.hip.inc"
 #include "text_kernels.hip.inc"
 #include "deflate_kernels.hip.inc"
+#include "info_kernels.hip.inc"
 
 namespace {
 
@@ -138,6 +139,9 @@ struct cs_engine {
   uint32_t waves_per_simd[2] = {4, 4};  // scan / resolve kernel, from their register counts
   bool long_demux = false;  // a CS_OP_DEMUX op with the barcodes' own ops (cs_plan_set_demux_ops)
   int demux_mate = -1;      // 0 / 1: the mate whose chain holds a CS_OP_DEMUX op
+  // mate 1's adapter ops as the info table (cs_text_params.info) needs them: how many, the longest, and the CS_F_* bits
+  // that exactly one of them sets
+  uint32_t info_adapters = 0, info_max_m = 0, info_uniq_flags = 0;
   uint32_t demux_bins = 0;  // ... and how many barcodes its table names
   std::vector<Slot> slots;
   uint32_t max_dynamic_lds[2] = {0, 0};
@@ -946,6 +950,17 @@ int cs_engine_create(const cs_plan *plan, int device, uint32_t n_slots, uint32_t
         if (64u * (d.op.m + 1u) > eng->col_dwords) eng->col_dwords = 64u * (d.op.m + 1u);
       }
       if (d.op.kind != CS_OP_ADAPTER) continue;
+      if (mt == 0) {
+        ++eng->info_adapters;
+        if (d.op.m > eng->info_max_m) eng->info_max_m = d.op.m;
+        uint32_t sharers = 0;
+        for (int j = 0; j < plan->host.n_ops[0]; ++j) {
+          const cs_op &o = plan->host.ops[0][j].op;
+          if (o.kind == CS_OP_ADAPTER && (o.match_flag & d.op.match_flag)) ++sharers;
+        }
+        // (a flag of one bit that no other adapter op of the chain touches)
+        if (sharers == 1 && d.op.match_flag && !(d.op.match_flag & (d.op.match_flag - 1))) eng->info_uniq_flags |= d.op.match_flag;
+      }
       if (d.filter_mode == csdev::FILTER_MYERS64) eng->wide = true;
       const uint32_t need = (d.acgt_only && d.op.m <= 32) ? 16u * (d.op.m + 1u) : 2u * (d.op.m + 1u);
       if (need > eng->col_dwords) eng->col_dwords = need;
@@ -1355,6 +1370,15 @@ struct TextSlot {
   uint8_t *d_bc = nullptr;                 // demultiplexing plans: barcode index per record
   uint8_t *d_xf[2] = {nullptr, nullptr};   // plans with TooManyN: cs_reads.xflags per record and mate
   RouteBlock *d_routes = nullptr, *h_routes = nullptr;  // ... and the sizes of their 3 + n_bins route streams
+  // cs_text_params.info: the matches of every record of mate 1, the table, and its gzip member
+  csinfo::InfoMatch *d_imatch = nullptr;
+  csinfo::InfoRec *d_irec = nullptr;
+  uint32_t *d_idst = nullptr, *d_iblk = nullptr;
+  unsigned long long *d_itotal = nullptr;
+  uint8_t *d_info = nullptr, *d_igzstage = nullptr, *d_igz = nullptr;
+  csdefl::ChunkInfo *d_ichunk = nullptr;
+  uint32_t *d_ichunk_dst = nullptr;
+  csinfo::InfoMeta *d_imeta = nullptr, *h_imeta = nullptr;
   hipEvent_t uploaded = nullptr, formatted = nullptr, fetched = nullptr;
   uint32_t n = 0;
   bool busy = false, waited = false;
@@ -1374,6 +1398,9 @@ struct cs_text {
   bool literal_only = false;  // ... from literal-only blocks (CUTSEQ_GPU_LZ=0: no run / record-name matches)
   uint32_t max_chunks = 0;
   uint32_t n_routes = 3;      // 3 + cs_text_params.n_bins
+  uint8_t info = 0;           // CS_INFO_* (cs_text_params.info)
+  uint64_t info_cap = 0;      // bytes of a batch's info table at most
+  uint32_t info_chunks = 0;   // ... and deflate chunks
   hipStream_t h2d = nullptr, d2h = nullptr;
   std::vector<TextSlot> slots;
 };
@@ -1395,6 +1422,7 @@ void free_text(cs_text *t) {
     if (s.d_arena) (void)hipFree(s.d_arena);  // (every device array of the slot is a piece of it)
     if (s.h_meta) (void)hipHostFree(s.h_meta);
     if (s.h_routes) (void)hipHostFree(s.h_routes);
+    if (s.h_imeta) (void)hipHostFree(s.h_imeta);
     for (hipEvent_t ev : {s.uploaded, s.formatted, s.fetched})
       if (ev) (void)hipEventDestroy(ev);
   }
@@ -1478,6 +1506,28 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
     t->n_routes = 3u + params->n_bins;
   }
   t->max_chunks = (uint32_t)((out_cap + csdefl::kChunk - 1) / csdefl::kChunk) + t->n_routes;
+  if (params->info) {
+    if (!(params->info & CS_INFO_ON) || (params->info & ~(CS_INFO_ON | CS_INFO_GZIP | CS_INFO_NO_QUAL))) {
+      delete t;
+      return fail(CS_ERR_ARG, "info = 0x%02x: CS_INFO_ON with CS_INFO_GZIP / CS_INFO_NO_QUAL, or 0", params->info);
+    }
+    if (eng->demux_mate >= 0) {
+      delete t;
+      return fail(CS_ERR_ARG, "info: a plan with a demultiplexing op has no info table (its table form has no error count)");
+    }
+    // Every row shows its read once as bases and once as qualities next to the name, and a record has at most one row
+    // per adapter op of mate 1's chain (one if there is none): rows <= the record's own text plus the UMI tag and
+    // 11 tabs, the line end, "errors rstart rstop name" in decimal (3 + 8 + 8 + 2 digits at most).
+    const uint64_t rows = eng->info_adapters ? eng->info_adapters : 1u;
+    t->info = params->info;
+    t->info_cap = rows * (max_text_bytes + (uint64_t)max_records * (params->max_tag + 40u)) + 64u;
+    if (t->info_cap >= (1ull << 32)) {
+      delete t;
+      return fail(CS_ERR_ARG, "info: the table of a batch could reach %llu bytes (4 GiB at most): smaller blocks, please",
+                  (unsigned long long)t->info_cap);
+    }
+    t->info_chunks = (uint32_t)((t->info_cap + csdefl::kChunk - 1) / csdefl::kChunk) + 1u;
+  }
   t->seg_blocks = (uint32_t)((max_text_bytes + cstext::kSeg - 1) / cstext::kSeg);
   t->fmt_blocks = (max_records + 255u) / 256u;
 #define TXT_TRY(expr)                                                                       \
@@ -1490,7 +1540,7 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
     }                                                                                       \
   } while (0)
   TXT_TRY(hipSetDevice(eng->device));
-  if (t->compress) {
+  if (t->compress || (t->info & CS_INFO_GZIP)) {
     // constants of the CRC-32 combination (zlib's x2n_table; shifts by whole 128-byte slices)
     auto mult = [](uint32_t a, uint32_t b) {
       uint32_t m = 1u << 31, p = 0;
@@ -1565,6 +1615,23 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
     size_t o_xf[2] = {0, 0};
     if (t->tp.max_n)
       for (int m = 0; m < mates; ++m) o_xf[m] = reserve(max_records);
+    size_t o_imatch = 0, o_irec = 0, o_idst = 0, o_iblk = 0, o_itotal = 0, o_info = 0, o_imeta = 0, o_igzstage = 0, o_igz = 0,
+           o_ichunk = 0, o_ichunk_dst = 0;
+    if (t->info) {
+      o_imatch = reserve((size_t)max_records * (eng->info_adapters ? eng->info_adapters : 1u) * sizeof(csinfo::InfoMatch));
+      o_irec = reserve((size_t)max_records * sizeof(csinfo::InfoRec));
+      o_idst = reserve((size_t)max_records * sizeof(uint32_t));
+      o_iblk = reserve(((size_t)t->fmt_blocks + 1) * sizeof(uint32_t));
+      o_itotal = reserve(sizeof(unsigned long long));
+      o_info = reserve(t->info_cap);
+      o_imeta = reserve(sizeof(csinfo::InfoMeta));
+      if (t->info & CS_INFO_GZIP) {
+        o_igzstage = reserve((size_t)t->info_chunks * csdefl::kSlot);
+        o_igz = reserve((size_t)t->info_chunks * csdefl::kSlot + 64);
+        o_ichunk = reserve((size_t)t->info_chunks * sizeof(csdefl::ChunkInfo));
+        o_ichunk_dst = reserve((size_t)t->info_chunks * sizeof(uint32_t));
+      }
+    }
     TXT_TRY(hipMalloc(&s.d_arena, need));
     uint8_t *base = s.d_arena;
     TXT_TRY(hipMemsetAsync(base, 0, zero_bytes, t->h2d));
@@ -1600,6 +1667,23 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
       s.d_bc = base + o_bc;
       s.d_routes = reinterpret_cast<RouteBlock *>(base + o_routes);
       TXT_TRY(hipHostMalloc(&s.h_routes, sizeof(RouteBlock), hipHostMallocPortable));
+    }
+    if (t->info) {
+      s.d_imatch = reinterpret_cast<csinfo::InfoMatch *>(base + o_imatch);
+      s.d_irec = reinterpret_cast<csinfo::InfoRec *>(base + o_irec);
+      s.d_idst = reinterpret_cast<uint32_t *>(base + o_idst);
+      s.d_iblk = reinterpret_cast<uint32_t *>(base + o_iblk);
+      s.d_itotal = reinterpret_cast<unsigned long long *>(base + o_itotal);
+      s.d_info = base + o_info;
+      s.d_imeta = reinterpret_cast<csinfo::InfoMeta *>(base + o_imeta);
+      if (t->info & CS_INFO_GZIP) {
+        s.d_igzstage = base + o_igzstage;
+        s.d_igz = base + o_igz;
+        s.d_ichunk = reinterpret_cast<csdefl::ChunkInfo *>(base + o_ichunk);
+        s.d_ichunk_dst = reinterpret_cast<uint32_t *>(base + o_ichunk_dst);
+      }
+      TXT_TRY(hipHostMalloc(&s.h_imeta, sizeof(csinfo::InfoMeta), hipHostMallocPortable));
+      memset(s.h_imeta, 0, sizeof(csinfo::InfoMeta));
     }
     TXT_TRY(hipHostMalloc(&s.h_meta, sizeof(cstext::TextMeta), hipHostMallocPortable));
     TXT_TRY(hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming));
@@ -1714,6 +1798,30 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
     fa.totals = s.d_totals + 2;
     fa.meta = s.d_meta;
     const uint32_t fb = (n_records + 255u) / 256u;
+    csinfo::InfoArgs ia;
+    memset(&ia, 0, sizeof ia);
+    if (t->info) {
+      // the match recorder, in front of the format kernels: a record on which it disagrees with the trimming kernels
+      // stops the batch (TextMeta.err) before anything is formatted
+      ia.match = s.d_imatch;
+      ia.rec = s.d_irec;
+      ia.blk = s.d_iblk;
+      ia.total = s.d_itotal;
+      ia.dst = s.d_idst;
+      ia.out = s.d_info;
+      ia.imeta = s.d_imeta;
+      ia.n_adapters = eng->info_adapters ? eng->info_adapters : 1u;
+      ia.plan_slot = (uint32_t)eng->plan_slot;
+      ia.uniq_flags = eng->info_uniq_flags;
+      ia.no_qual = (t->info & CS_INFO_NO_QUAL) ? 1u : 0u;
+      ia.cap = t->info_cap;
+      HIP_TRY(hipMemsetAsync(s.d_imeta, 0, sizeof(csinfo::InfoMeta), rs));
+      const dim3 rec_grid((n_records + 63u) / 64u);
+      if (eng->info_max_m <= 48u)
+        hipLaunchKernelGGL(csinfo::info_record<48>, rec_grid, dim3(64), 0, rs, fa, t->tp, ia);
+      else
+        hipLaunchKernelGGL(csinfo::info_record<CS_MAX_ADAPTER>, rec_grid, dim3(64), 0, rs, fa, t->tp, ia);
+    }
     if (t->tp.n_bins) {  // one route per barcode: LDS sums per route instead of a block scan per route
       fa.bc = s.d_bc;
       fa.route_bytes = &s.d_routes->bytes[0][0];
@@ -1736,6 +1844,46 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
     else
       hipLaunchKernelGGL(cstext::format_copy<false>, copy_grid, dim3(256), 0, rs, fa, t->tp);
     HIP_TRY(hipGetLastError());
+    if (t->info) {
+      hipLaunchKernelGGL(csinfo::info_sizes, dim3(fb), dim3(256), 0, rs, fa, ia);
+      hipLaunchKernelGGL(cstext::text_scan_blocks, dim3(1), dim3(1024), 0, rs, s.d_iblk, fb, 1u, s.d_itotal);
+      hipLaunchKernelGGL(csinfo::info_offsets, dim3(fb), dim3(256), 0, rs, fa, ia);
+      const unsigned long long iwant = ((unsigned long long)n_records * 32ull + 255ull) / 256ull;
+      hipLaunchKernelGGL(csinfo::info_copy, dim3((uint32_t)(iwant > 32768ull ? 32768ull : iwant)), dim3(256), 0, rs, fa, t->tp, ia);
+      if (t->info & CS_INFO_GZIP) {  // one more stream for the deflate kernels: one gzip member per batch, like a route
+        csdefl::DeflateArgs da;
+        da.text = s.d_info;
+        da.route_bytes = &s.d_imeta->bytes;
+        da.n_routes = 1;
+        da.stage = s.d_igzstage;
+        da.info = s.d_ichunk;
+        da.max_chunks = t->info_chunks;
+        da.gate = &s.d_meta->err;
+        da.fasta_classes = 0;
+        da.literal_only = t->literal_only ? 1u : 0u;
+        hipLaunchKernelGGL(csdefl::deflate_chunks, dim3(t->info_chunks), dim3(256), 0, rs, da);
+        csdefl::LayoutArgs la;
+        la.info = s.d_ichunk;
+        la.route_bytes = da.route_bytes;
+        la.n_routes = 1;
+        la.chunk_dst = s.d_ichunk_dst;
+        la.gz = s.d_igz;
+        la.gz_route_bytes = &s.d_imeta->gz_bytes;
+        la.gz_total = &s.d_imeta->gz_total;
+        la.gate = da.gate;
+        hipLaunchKernelGGL(csdefl::deflate_layout, dim3(1), dim3(256), 0, rs, la);
+        csdefl::CompactArgs ca;
+        ca.info = s.d_ichunk;
+        ca.chunk_dst = s.d_ichunk_dst;
+        ca.stage = s.d_igzstage;
+        ca.gz = s.d_igz;
+        ca.route_bytes = da.route_bytes;
+        ca.n_routes = 1;
+        ca.gate = da.gate;
+        hipLaunchKernelGGL(csdefl::deflate_compact, dim3(t->info_chunks), dim3(256), 0, rs, ca);
+      }
+      HIP_TRY(hipGetLastError());
+    }
     if (t->compress) {
       for (int m = 0; m < mates; ++m) {
         csdefl::DeflateArgs da;
@@ -1775,8 +1923,10 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
   } else {
     HIP_TRY(hipEventRecord(s.fetched, st));  // order the resolve stream behind the (empty) batch's meta
     HIP_TRY(hipStreamWaitEvent(rs, s.fetched, 0));
+    if (t->info) HIP_TRY(hipMemsetAsync(s.d_imeta, 0, sizeof(csinfo::InfoMeta), rs));
   }
   HIP_TRY(hipMemcpyAsync(s.h_meta, s.d_meta, sizeof(cstext::TextMeta), hipMemcpyDeviceToHost, rs));
+  if (t->info) HIP_TRY(hipMemcpyAsync(s.h_imeta, s.d_imeta, sizeof(csinfo::InfoMeta), hipMemcpyDeviceToHost, rs));
   if (t->tp.n_bins) {
     if (!n_records) HIP_TRY(hipMemsetAsync(s.d_routes, 0, sizeof(RouteBlock), rs));
     HIP_TRY(hipMemcpyAsync(s.h_routes, s.d_routes, sizeof(RouteBlock), hipMemcpyDeviceToHost, rs));
@@ -1873,6 +2023,35 @@ int cs_text_fetch(cs_text *t, uint32_t slot, void *dst1, void *dst2) {
   HIP_TRY(hipEventRecord(s.fetched, t->d2h));
   HIP_TRY(hipEventSynchronize(s.fetched));
   s.busy = false;
+  return CS_OK;
+}
+
+int cs_text_info(cs_text *t, uint32_t slot, uint64_t *bytes, uint64_t *text_bytes, uint64_t *rows) {
+  if (!t) return fail(CS_ERR_ARG, "null text engine");
+  if (slot >= t->slots.size()) return fail(CS_ERR_ARG, "slot %u out of range", slot);
+  if (!t->info) return fail(CS_ERR_STATE, "this cs_text was created without info");
+  TextSlot &s = t->slots[slot];
+  if (!s.busy || !s.waited) return fail(CS_ERR_STATE, "slot %u: between cs_text_wait and cs_text_fetch", slot);
+  const csinfo::InfoMeta &m = *s.h_imeta;
+  if (bytes) *bytes = (t->info & CS_INFO_GZIP) ? m.gz_total : m.bytes;
+  if (text_bytes) *text_bytes = m.bytes;
+  if (rows) *rows = m.rows;
+  return CS_OK;
+}
+
+int cs_text_fetch_info(cs_text *t, uint32_t slot, void *dst) {
+  if (!t) return fail(CS_ERR_ARG, "null text engine");
+  if (slot >= t->slots.size()) return fail(CS_ERR_ARG, "slot %u out of range", slot);
+  if (!t->info) return fail(CS_ERR_STATE, "this cs_text was created without info");
+  TextSlot &s = t->slots[slot];
+  if (!s.busy || !s.waited) return fail(CS_ERR_STATE, "slot %u: between cs_text_wait and cs_text_fetch", slot);
+  HIP_TRY(hipSetDevice(t->eng->device));
+  const bool gz = (t->info & CS_INFO_GZIP) != 0;
+  const size_t bytes = (size_t)(gz ? s.h_imeta->gz_total : s.h_imeta->bytes);
+  if (!bytes) return CS_OK;
+  if (!dst) return fail(CS_ERR_ARG, "%zu bytes of info table and no buffer", bytes);
+  HIP_TRY(hipMemcpyAsync(dst, gz ? s.d_igz : s.d_info, bytes, hipMemcpyDeviceToHost, t->d2h));
+  HIP_TRY(hipStreamSynchronize(t->d2h));
   return CS_OK;
 }
 

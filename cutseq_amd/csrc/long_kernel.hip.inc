@@ -34,15 +34,18 @@ __device__ __forceinline__ uint32_t query_code(uint8_t c, bool coded, bool fold)
   return coded ? csdev::base_code(c) : (uint32_t)c;
 }
 
-// cutadapt Aligner.locate on query = text[q0 + s, q0 + e) (walked backwards for the rightmost variant)
-__device__ bool locate(const DevOp &d, bool coded, bool fold, int rule, bool tie_ins, const uint8_t *q, int n, int &qs,
-                       int &qe) {
+// cutadapt Aligner.locate on query = text[q0 + s, q0 + e) (walked backwards for the rightmost variant).  kMaxM bounds
+// the adapter length the three columns are sized for (the caller vouches for op.m <= kMaxM); `errors` receives the
+// cost of the selected candidate (Match.errors).
+template <int kMaxM>
+__device__ __forceinline__ bool locate_sized(const DevOp &d, bool coded, bool fold, int rule, bool tie_ins, const uint8_t *q,
+                                             int n, int &qs, int &qe, int &errors) {
   const cs_op &op = d.op;
   const int m = op.m, k = op.k, flags = op.align_flags, min_overlap = op.min_overlap;
   const bool RS = flags & CS_REF_START, QS = flags & CS_QUERY_START;
   const bool RE = flags & CS_REF_END, QSTOP = flags & CS_QUERY_STOP;
   const bool reversed = op.reversed;
-  int ccost[CS_MAX_ADAPTER + 1], cscore[CS_MAX_ADAPTER + 1], corigin[CS_MAX_ADAPTER + 1];
+  int ccost[kMaxM + 1], cscore[kMaxM + 1], corigin[kMaxM + 1];
   int min_n, max_n;
   csdev::column_range(flags, m, k, n, min_n, max_n);
   for (int i = 0; i <= m; ++i) {
@@ -141,7 +144,14 @@ __device__ bool locate(const DevOp &d, bool coded, bool fold, int rule, bool tie
   if (!have) return false;
   qs = b_origin >= 0 ? b_origin : 0;
   qe = b_qstop;
+  errors = b_cost;
   return true;
+}
+
+__device__ bool locate(const DevOp &d, bool coded, bool fold, int rule, bool tie_ins, const uint8_t *q, int n, int &qs,
+                       int &qe) {
+  int errors;
+  return locate_sized<CS_MAX_ADAPTER>(d, coded, fold, rule, tie_ins, q, n, qs, qe, errors);
 }
 
 struct LongArgs {

@@ -185,6 +185,19 @@ class DemuxOp:
 Op = Union[AdapterOp, CutOp, QTrimOp, DemuxOp]
 
 
+def info_adapter_names(ops: Sequence["Op"]) -> dict:
+    """``--info-file`` column 8: {op index: adapter name} for the adapter ops of a mate's chain -- the 1-based position
+    among them, as ``report.json_report`` names the first one of ``"adapters_read1"``.  (cutadapt numbers its adapters
+    in construction order across both mates: recalled, not pinned -- DESIGN.md section 0.  The recorder on the device
+    counts the same way, ``info_kernels.hip.inc``.)"""
+    names, at = {}, 0
+    for i, op in enumerate(ops):
+        if isinstance(op, AdapterOp):
+            at += 1
+            names[i] = str(at)
+    return names
+
+
 @dataclass
 class MateChain:
     ops: List[Op] = field(default_factory=list)

@@ -297,7 +297,8 @@ def run_parent(argv: List[str], args, tp) -> Optional[dict]:
     to one process."""
     world = int(args.ranks)
     paths = list(args.input_file)
-    names_all = [n for names in (args.output_file, args.short_file, args.untrimmed_file) for n in names if n]
+    names_all = [n for names in (args.output_file, args.short_file, args.untrimmed_file,
+                                 [getattr(args, "info_file", None)]) for n in names if n]
     if "-" in paths or "-" in names_all:
         logging.warning(f"--ranks {world} ignored: standard input / output cannot be shared between ranks.")
         return None
@@ -350,14 +351,23 @@ def part_name(name, r):
     return f"{name}.rank{r}.part{kind}{ending}"
 
 
-def _run_ranks(argv: List[str], args, world: int, shares, t0: float, how: str) -> dict:
-    want = os.environ.get("CUTSEQ_DEVICES")
-    devices = [int(x) for x in want.split(",")] if want else list(range(world))
+def output_groups(args) -> dict:
+    """{key of a rank's spec: the output files under it}: every rank writes a part of each (``part_name``) and the
+    parts are concatenated in rank order."""
     groups = {"output_file": args.output_file, "short_file": args.short_file, "untrimmed_file": args.untrimmed_file}
     for b, names in enumerate(getattr(args, "demux_files", None) or []):  # demultiplexing: a pair of files per barcode
         groups[f"demux_files:{b}"] = names
+    if getattr(args, "info_file", None):  # every rank's table of its share; concatenated in rank order like the records
+        groups["info_file"] = [args.info_file]
     if getattr(args, "demux_files", None):
         groups["output_file"] = [None] * len(args.output_file)  # (nothing is written under the common trimmed names)
+    return groups
+
+
+def _run_ranks(argv: List[str], args, world: int, shares, t0: float, how: str) -> dict:
+    want = os.environ.get("CUTSEQ_DEVICES")
+    devices = [int(x) for x in want.split(",")] if want else list(range(world))
+    groups = output_groups(args)
     work = tempfile.mkdtemp(prefix="cutseq_ranks_")
     children, specs = [], []
     # every rank gets its share of the host threads (N pools of all cores each would oversubscribe the host N times)

@@ -157,7 +157,7 @@ def _host_threads() -> int:
 
 
 def json_report(tp: TrimPlan, totals: dict, barcode, input1, input2, output1, output2, short1, short2,
-                untrimmed1, untrimmed2) -> dict:
+                untrimmed1, untrimmed2, info_file=None) -> dict:
     """Same header block as the reference's ``json_report`` (run.py:262-283) followed by the
     ``Statistics.as_json()`` sections; engine-specific counters live under ``"engine"``."""
     paired = tp.paired
@@ -221,6 +221,8 @@ def json_report(tp: TrimPlan, totals: dict, barcode, input1, input2, output1, ou
         "poly_a_trimmed_read2": None,
         "engine": engine,
     }
+    if info_file:  # (a run without --info-file keeps the block it always had)
+        d["output"]["info_file"] = info_file
     return d
 
 

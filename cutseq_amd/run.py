@@ -91,6 +91,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Extension (cutadapt's option; a TODO of the reference): discard reads with more than COUNT 'N' "
                         "bases. If COUNT is a number between 0 and 1, it is interpreted as a fraction of the read "
                         "length. A pair is discarded if either read has too many N.")
+    p.add_argument("--info-file", type=str, default=None, metavar="FILE",
+                   help="Extension (cutadapt's option; a TODO of the reference): write a tab-separated table of the "
+                        "adapter matches of read 1 to FILE, one row per match, in input order; reads without a match "
+                        "get one row with -1. A .gz / .bz2 / .xz / .zst name compresses the table.")
     p.add_argument("--rank-spec", type=str, help=argparse.SUPPRESS)  # a child of --ranks: its share of the run
     p.add_argument("--demux-barcodes", type=str, metavar="FILE",
                    help="Extension: demultiplex on the 5' inline barcode. FILE lists 'name<TAB>sequence' per line (all as "
@@ -154,6 +158,12 @@ def resolve_args(args):
     max_n = getattr(args, "max_n", None)
     if max_n is not None and not max_n >= 0:  # (NaN fails the comparison too)
         _fail(f"--max-n: the count must not be negative (got {max_n}).")
+    if getattr(args, "info_file", None):
+        if args.demux_barcodes:
+            _fail("--info-file cannot be combined with --demux-barcodes: the table form of the demultiplexing op has "
+                  "no error count to report.")
+        if os.environ.get("CUTSEQ_TEXT_PATH", "1") == "0":
+            _fail("--info-file needs the text path: the table is written on the GPU (CUTSEQ_TEXT_PATH=0 is set).")
     if not inputs:
         # the reference dies with an IndexError here (run.py:1079-1083); same exit class, clearer message
         _fail("Input file is required.")
@@ -522,6 +532,8 @@ def run_cutseq(args, argv=None):
         for key, names in spec["outputs"].items():
             if key.startswith("demux_files:"):
                 args.demux_files[int(key.split(":")[1])] = names
+            elif key == "info_file":
+                args.info_file = names[0]
             else:
                 setattr(args, key, names)
         try:
@@ -552,7 +564,8 @@ def run_cutseq(args, argv=None):
             tp, totals, barcode, args.input_file[0], args.input_file[1] if paired else None,
             args.output_file[0], args.output_file[1] if paired else None,
             args.short_file[0], args.short_file[1] if paired else None,
-            args.untrimmed_file[0], args.untrimmed_file[1] if paired else None)
+            args.untrimmed_file[0], args.untrimmed_file[1] if paired else None,
+            info_file=getattr(args, "info_file", None))
         report.write_json(args.json_file, rep)
     print(report.minimal_report(tp, totals), file=sys.stderr)
     return totals

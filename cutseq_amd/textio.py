@@ -578,10 +578,11 @@ class StreamWriter:
 
 
 class _Done:
-    __slots__ = ("k", "n", "res", "out", "sizes", "counts")
+    __slots__ = ("k", "n", "res", "out", "sizes", "counts", "info", "info_bytes")
 
-    def __init__(self, k, n, res, out, sizes=None, counts=None):
+    def __init__(self, k, n, res, out, sizes=None, counts=None, info=None, info_bytes=0):
         self.k, self.n, self.res, self.out, self.sizes, self.counts = k, n, res, out, sizes, counts
+        self.info, self.info_bytes = info, info_bytes  # --info-file: the batch's table (a pinned buffer) and its size
 
 
 class TextWorker(threading.Thread):
@@ -590,8 +591,9 @@ class TextWorker(threading.Thread):
     SLOTS = 3
 
     def __init__(self, tp, device: int, done: "queue.Queue", chunk_reads: int, compress: bool = False, bins: int = 0,
-                 fasta_routes: int = 0):
+                 fasta_routes: int = 0, info: int = 0):
         super().__init__(daemon=True, name=f"cutseq-gpu{device}")
+        self.info = info  # abi.CS_INFO_* bits: the batches also yield the --info-file table
         self.tp, self.device, self.done, self.chunk_reads, self.compress = tp, device, done, chunk_reads, compress
         self.fasta_routes = fasta_routes  # bit 2 * class + mate: that stream's records leave as FASTA
         self.bins = bins  # demultiplexing: one route per barcode behind the three ordinary ones
@@ -622,7 +624,7 @@ class TextWorker(threading.Thread):
         self.capacity = max(self.capacity, int(text_bytes * 1.25) + (1 << 20))
         self.text = textpath.TextEngine(self.engine, slots=self.SLOTS, max_text_bytes=self.capacity,
                                         max_records=self.chunk_reads, stride=self.stride, compress=self.compress,
-                                        bins=self.bins, fasta_routes=self.fasta_routes)
+                                        bins=self.bins, fasta_routes=self.fasta_routes, info=self.info)
         self.submitted = 0
 
     def _submit(self, inflight: deque, k: int, b1: TextBlock, b2: Optional[TextBlock]):
@@ -659,13 +661,18 @@ class TextWorker(threading.Thread):
         if self.bins:
             sizes, _, counts = self.text.routes(slot)
         out = [fastq.PINNED.take(max(int(res.out_bytes[m]), 1)) for m in range(2 if b2 is not None else 1)]
+        info_buf, info_bytes = None, 0
+        if self.info:
+            info_bytes = self.text.info(slot)[0]
+            info_buf = fastq.PINNED.take(max(info_bytes, 1))
+            self.text.fetch_info(slot, info_buf)
         t0 = _tick("take", t0)
         self.text.fetch(slot, out[0], out[1] if b2 is not None else None)
         _tick("fetch", t0)
         b1.release()
         if b2 is not None:
             b2.release()
-        self.done.put(_Done(k, b1.n, res, out, sizes, counts))
+        self.done.put(_Done(k, b1.n, res, out, sizes, counts, info_buf, info_bytes))
 
     def run(self):
         inflight: deque = deque()
@@ -824,6 +831,15 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
             return group
 
         outs = [mk(names) for names in name_groups]
+        # --info-file: one more stream per batch.  The container goes by the file's name like a record output's; a
+        # ".gz" table leaves the device as gzip members (CUTSEQ_GPU_DEFLATE=0: deflated in the host pool instead).
+        info_name = getattr(args, "info_file", None)
+        info_flags, info_out = 0, None
+        if info_name:
+            info_gz = info_name != "-" and codec.container_of_name(info_name) == "gzip" and os.environ.get("CUTSEQ_GPU_DEFLATE", "1") != "0"
+            info_flags = abi.CS_INFO_ON | (abi.CS_INFO_GZIP if info_gz else 0) | (abi.CS_INFO_NO_QUAL if r1.fasta else 0)
+            info_out = StreamWriter(info_name, precompressed=info_gz)
+            opened.append(info_out)
     except BaseException:
         r1.close()
         if r2 is not None:
@@ -840,7 +856,7 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         from .run import _phase
         _phase("readers and writers open")
     done: "queue.Queue" = queue.Queue()
-    workers = [TextWorker(tp, dev, done, chunk_reads, compress, n_bins, fasta_routes) for dev in devices]
+    workers = [TextWorker(tp, dev, done, chunk_reads, compress, n_bins, fasta_routes, info_flags) for dev in devices]
     if n_bins:
         totals["routes"] += [0] * n_bins
     budget = threading.Semaphore(2 * len(workers) * TextWorker.SLOTS + 2)  # batches between reader and disk
@@ -871,7 +887,9 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
                 if nbytes and fh is not None:
                     jobs.append((fh, memoryview(item.out[m])[at:at + nbytes]))
                 at += nbytes
-        shared = _Shared(item.out, len(jobs), budget.release)
+        if info_out is not None and item.info_bytes:
+            jobs.append((info_out, memoryview(item.info)[:item.info_bytes]))
+        shared = _Shared(item.out + ([item.info] if item.info is not None else []), len(jobs), budget.release)
         for fh, view in jobs:
             fh.put(view, shared)
 
@@ -898,7 +916,7 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
                 if isinstance(item, TextWorker):
                     alive -= 1
                 else:
-                    for b in item.out:
+                    for b in item.out + ([item.info] if item.info is not None else []):
                         fastq.PINNED.give(b)
                     budget.release()
 
@@ -951,7 +969,7 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         for w in workers:
             w.join()
         collector.join()
-        for group in outs:
+        for group in outs + [[info_out]]:
             for fh in group:
                 if fh is None:
                     continue

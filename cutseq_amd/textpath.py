@@ -28,6 +28,10 @@ class TextFormatError(ValueError):
         self.code, self.record = code, record
 
 
+class InfoMismatch(RuntimeError):
+    """``CS_TEXT_ERR_INFO_MISMATCH`` / ``CS_TEXT_ERR_INFO_OVERFLOW``: an engine fault, never the input's."""
+
+
 class ReadTooLong(ValueError):
     """A read beyond CS_MAX_READ (the text path's positions are 32-bit, its long-read kernel serial per read)."""
 
@@ -66,8 +70,9 @@ class TextEngine:
 
     def __init__(self, engine: TrimEngine, slots: int = 3, max_text_bytes: int = 64 << 20, max_records: int = 1 << 18,
                  stride: int = 152, compress: bool = False, bins: int = 0, fasta: bool = False,
-                 fasta_routes: int = 0):
-        """``compress``: every route's output leaves the device as one gzip member (``res.route_bytes`` then counts
+                 fasta_routes: int = 0, info: int = 0):
+        """``info``: ``abi.CS_INFO_*`` bits -- the batch also yields cutadapt's ``--info-file`` table for read 1
+        (:meth:`info`, :meth:`fetch_info`).  ``compress``: every route's output leaves the device as one gzip member (``res.route_bytes`` then counts
         compressed bytes): what ``.gz`` output files take as they are.  ``bins``: the plan demultiplexes (table form)
         into that many barcodes; the trimmed records of barcode b are route 3 + b (:meth:`routes`).  ``fasta``: every
         record leaves as ``>id\nsequence\n``; ``fasta_routes``: the same per stream, bit ``2 * class + mate`` (class 0
@@ -85,6 +90,8 @@ class TextEngine:
         p.fasta_routes = int(fasta_routes)
         self.compress = bool(compress)
         p.n_bins = int(bins)
+        p.info = int(info)
+        self.info_flags = int(info)
         self.n_routes = 3 + int(bins)
         p.max_tag = max_tag(plan)
         self._keep = []  # the literals must outlive the call
@@ -132,7 +139,25 @@ class TextEngine:
             raise TextFormatError(res.error, first_record,
                                   f"the text block does not hold the announced number of records ({res.n_records} records, "
                                   f"{res.n_lines[0]} / {res.n_lines[1]} line ends)")
+        if res.error == abi.CS_TEXT_ERR_INFO_MISMATCH:
+            raise InfoMismatch(f"--info-file: the match recorder and the trimming kernels disagree on record "
+                               f"{first_record + res.error_record + 1}; no table is written for a batch that "
+                               "contradicts its records")
+        if res.error == abi.CS_TEXT_ERR_INFO_OVERFLOW:
+            raise InfoMismatch("--info-file: the table of a block outgrew the buffer sized for it "
+                               f"(records {first_record + 1}..{first_record + res.n_records})")
         return res
+
+    def info(self, slot: int):
+        """Behind :meth:`wait`, before :meth:`fetch`: (bytes as :meth:`fetch_info` delivers them, text bytes, rows) of
+        the batch's info table."""
+        got, raw, rows = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        capi.check(self.L.cs_text_info(self._h, slot, C.byref(got), C.byref(raw), C.byref(rows)))
+        return int(got.value), int(raw.value), int(rows.value)
+
+    def fetch_info(self, slot: int, dst) -> None:
+        """The info table (a gzip member with ``CS_INFO_GZIP``) into ``dst``; the slot stays taken until :meth:`fetch`."""
+        capi.check(self.L.cs_text_fetch_info(self._h, slot, _address(dst) or None))
 
     def routes(self, slot: int):
         """Behind :meth:`wait`: (bytes[route, mate] as fetched, text_bytes[route, mate], count[route]) of every route."""

@@ -305,7 +305,25 @@ enum {
   CS_TEXT_ERR_MALFORMED = 1,   /* no '@' / '+' line, sequence and quality lengths differ: record `error_record` */
   CS_TEXT_ERR_TOO_LONG = 2,    /* a read is longer than CS_MAX_READ                                            */
   CS_TEXT_ERR_IDS_DIFFER = 3,  /* PairedEndRenamer: "Input read IDs not identical" at record `error_record`    */
-  CS_TEXT_ERR_LINE_COUNT = 4   /* the text does not hold 4 * n_records lines                                   */
+  CS_TEXT_ERR_LINE_COUNT = 4,  /* the text does not hold 4 * n_records lines                                   */
+  CS_TEXT_ERR_INFO_MISMATCH = 5, /* cs_text_params.info: the match recorder's final interval or flags of record
+                                   `error_record` differ from what the trimming kernels produced: an engine fault,
+                                   reported instead of a table that contradicts the records                          */
+  CS_TEXT_ERR_INFO_OVERFLOW = 6  /* cs_text_params.info: the table of the batch is larger than the bound cs_text_create
+                                   derived for it (an engine fault too: the bound covers every possible table); nothing
+                                   of it was written                                                                 */
+};
+
+/* cs_text_params.info: cutadapt's --info-file for read 1 (a TODO of the reference, cutseq/run.py "report info"):
+ * per batch one more stream, the tab-separated table of every adapter match in input order.  A read with k >= 1
+ * matches has k rows of 12 columns, in chain order -- name as the record outputs carry it, errors, rstart, rstop,
+ * sequence left of / in / right of the match (together: the read as that op saw it), the 1-based position of the op
+ * among the adapter ops of mate 1's chain, the qualities cut the same way, an empty column --, a read without one a
+ * row of 5: name, -1, final sequence, final qualities, an empty column.  Every record has rows, whatever its route. */
+enum {
+  CS_INFO_ON = 1,      /* record the matches and format the table                                               */
+  CS_INFO_GZIP = 2,    /* the table leaves the device as ONE gzip member per batch (like a route with compress)  */
+  CS_INFO_NO_QUAL = 4  /* the input had no qualities (FASTA): the quality columns stay empty                    */
 };
 
 typedef struct cs_text_params {
@@ -331,7 +349,9 @@ typedef struct cs_text_params {
                                  stream is FASTA when fasta_out is set or its bit is; 0 = fasta_out alone decides.  A
                                  bit of a stream the plan does not have (mate 2 of a single-end plan, class 3 without
                                  bins) is CS_ERR_ARG                                                                 */
-  uint8_t _reserved[2];
+  uint8_t info;               /* CS_INFO_* bits; 0 = no table (the kernels launched are then exactly those of a
+                                 cs_text without the member).  CS_ERR_ARG on a plan with a CS_OP_DEMUX op            */
+  uint8_t _reserved[1];
 } cs_text_params;
 
 typedef struct cs_text_result {
@@ -369,6 +389,13 @@ int cs_text_routes(cs_text *t, uint32_t slot, uint64_t *bytes, uint64_t *text_by
 /* Copies the output text (res->out_bytes[m] bytes per mate) into the caller's buffers and blocks until it is
  * there; the slot is free for the next cs_text_submit afterwards.  dst2 == NULL for single-end. */
 int cs_text_fetch(cs_text *t, uint32_t slot, void *dst1, void *dst2);
+/* The info table of the slot's batch (cs_text_params.info): *bytes as cs_text_fetch_info delivers it (the gzip member
+ * with CS_INFO_GZIP), *text_bytes uncompressed, *rows table rows.  Any pointer may be NULL.  Both calls are valid between
+ * cs_text_wait and cs_text_fetch; cs_text_fetch frees the slot, cs_text_fetch_info does not.  CS_ERR_STATE on a cs_text
+ * created without info. */
+int cs_text_info(cs_text *t, uint32_t slot, uint64_t *bytes, uint64_t *text_bytes, uint64_t *rows);
+/* Copies the table (*bytes of cs_text_info) into dst and blocks until it is there. */
+int cs_text_fetch_info(cs_text *t, uint32_t slot, void *dst);
 
 void *cs_alloc_pinned(size_t bytes);
 /* The same on transparent huge pages (an anonymous mapping, touched, hipHostRegister-ed): 2-3x quicker to get --
