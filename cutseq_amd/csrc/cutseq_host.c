@@ -315,7 +315,8 @@ typedef struct csh_format_params {
   const char *suffix2[2];
 } csh_format_params;
 
-static int is_space(uint8_t c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\v' || c == '\f'; }
+/* str.split()'s white space on 7-bit input (the reference splits a str, not bytes): " \t\n\v\f\r" and \x1c .. \x1f */
+static int is_space(uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r') || (c >= 0x1c && c <= 0x1f); }
 
 /* SuffixRemover chain on the whole header */
 static int32_t strip_suffixes(const uint8_t *name, int32_t n, const char *const suf[2]) {

@@ -213,7 +213,8 @@ __global__ void __launch_bounds__(kSegThreads) text_write_nl(const uint8_t *text
 
 // ---- records ---------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ bool is_space(uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r'); }  // " \t\n\v\f\r"
+// str.split()'s white space on 7-bit input (the reference splits a str, not bytes): " \t\n\v\f\r" and \x1c .. \x1f
+__device__ __forceinline__ bool is_space(uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r') || (c >= 0x1c && c <= 0x1f); }
 
 constexpr uint32_t kNotLong = 0xffffffffu;
 
@@ -296,7 +297,11 @@ __global__ void __launch_bounds__(256) text_parse_records(const uint8_t *text, c
 __global__ void __launch_bounds__(256) text_check_pairs(const uint8_t *text1, const Rec *rec1, const uint8_t *text2,
                                                         const Rec *rec2, uint32_t n, TextMeta *meta) {
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  if (r >= n || meta->err != ~0ull) return;  // (a malformed record somewhere: its error comes first anyway)
+  // Leave only for a key of a record at or in front of this one (a malformed record of the parse kernels, the line-count
+  // key on record 0, whose records are empty): the word is also written by the other blocks of THIS launch, and a
+  // later record's key seen there must not keep this record's smaller one from being reported.  (~0 >> 8 is beyond
+  // every record.)
+  if (r >= n || (meta->err >> 8) <= r) return;
   const uint8_t *n1 = text1 + rec1[r].hdr_off, *n2 = text2 + rec2[r].hdr_off;
   const uint32_t l1 = rec1[r].hdr_len, l2 = rec2[r].hdr_len;
   uint32_t a = 0, b = 0;

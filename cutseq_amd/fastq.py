@@ -506,8 +506,10 @@ def format_chunk(chunk: Chunk, plan, res1: np.ndarray, cap2: Optional[np.ndarray
         i = int(-rc - 1)
         n1 = bytes(chunk.raw1[chunk.name_off1[i]: chunk.name_off1[i] + chunk.name_len1[i]]).decode(errors="replace")
         n2 = bytes(chunk.raw2[chunk.name_off2[i]: chunk.name_off2[i] + chunk.name_len2[i]]).decode(errors="replace")
-        raise ValueError(f"Input read IDs not identical: '{n1.split()[0] if n1.split() else n1}' != "
+        err = ValueError(f"Input read IDs not identical: '{n1.split()[0] if n1.split() else n1}' != "
                          f"'{n2.split()[0] if n2.split() else n2}'")
+        err.record = i  # index of the first such pair inside the chunk
+        raise err
     views = [[(Lease(leased[r][m], int(out_len[r][m])) if leased[r][m] is not None
                else memoryview(bufs[r][m])[: out_len[r][m]]) for m in range(2)] for r in range(3)]
     if copy:

@@ -15,6 +15,8 @@ from cutseq_amd import abi
 ROUTE_TRIMMED, ROUTE_SHORT, ROUTE_UNTRIMMED = 0, 1, 2
 ROUTE_NAMES = ("trimmed", "short", "untrimmed")
 
+_STR_SPACE = b" \t\n\v\f\r\x1c\x1d\x1e\x1f"  # what str.split() splits on below 0x80
+
 _COMPLEMENT = bytes.maketrans(b"ACGTUMRWSYKVHDBNacgtumrwsykvhdbn", b"TGCAAKYWSRMBDHVNtgcaakywsrmbdhvn")
 
 
@@ -28,9 +30,18 @@ def strip_suffixes(name: bytes, suffixes: Sequence[bytes]) -> bytes:
 
 def read_id(name: bytes) -> bytes:
     """Renamer.parse_name: ``name.split(maxsplit=1)[0]``; a header without a second field
-    (including an empty or all-blank header) is its own id."""
-    fields = name.split(None, 1)
-    return fields[0] if len(fields) == 2 else name
+    (including an empty or all-blank header) is its own id.  The reference splits a ``str``: on 7-bit input its white
+    space is ``" \\t\\n\\v\\f\\r"`` and ``\\x1c`` .. ``\\x1f`` (``bytes.split`` knows the first six only)."""
+    a = 0
+    while a < len(name) and name[a] in _STR_SPACE:
+        a += 1
+    b = a
+    while b < len(name) and name[b] not in _STR_SPACE:
+        b += 1
+    c = b
+    while c < len(name) and name[c] in _STR_SPACE:
+        c += 1
+    return name[a:b] if b > a and c < len(name) else name
 
 
 def pair_id(name: bytes) -> bytes:

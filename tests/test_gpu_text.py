@@ -34,13 +34,14 @@ def oracle_streams(tp, batch, names1, names2):
     logic, and its per-mate statistics."""
     (o1, cap2, ost1), m2 = util.oracle_run(tp, batch, threads=8)
     recs = util.format_batch(tp, batch, names1, names2, o1, cap2, m2[0] if m2 else None)
-    streams = [[b"", b""] for _ in range(3)]
+    parts = [[[], []] for _ in range(3)]  # (joined once: tens of thousands of records per batch in test_gpu_text_names)
     counts = [0, 0, 0]
     for route, r1, r2 in recs:
-        streams[route][0] += r1
+        parts[route][0].append(r1)
         if r2 is not None:
-            streams[route][1] += r2
+            parts[route][1].append(r2)
         counts[route] += 1
+    streams = [[b"".join(p) for p in row] for row in parts]
     return streams, counts, (ost1, m2[2] if m2 else None)
 
 
