@@ -1344,6 +1344,14 @@ struct RouteBlock {  // demultiplexing plans: per route what TextMeta holds for 
   uint32_t _pad[2];
 };
 
+struct GzStream {  // compressed output of one stream (a mate's routes, the info table)
+  uint8_t *stage = nullptr;  // one slot per 32 KB chunk ...
+  uint8_t *gz = nullptr;     // ... laid out as gzip members
+  csdefl::ChunkInfo *chunk = nullptr;
+  uint32_t *chunk_dst = nullptr;
+  uint32_t chunks = 0;
+};
+
 struct TextSlot {
   uint8_t *d_arena = nullptr;  // the slot's one device allocation
   uint8_t *d_text[2] = {nullptr, nullptr};
@@ -1359,10 +1367,7 @@ struct TextSlot {
   cslong::LongRec *d_lrec[2] = {nullptr, nullptr};  // reads longer than the rows: their place in the text ...
   cslong::LongRes *d_lres[2] = {nullptr, nullptr};  // ... and their results
   uint32_t *d_long_of[2] = {nullptr, nullptr};      // per record: index into the two, or kNotLong
-  uint8_t *d_gzstage[2] = {nullptr, nullptr};       // compressed output: one slot per 32 KB chunk ...
-  uint8_t *d_gz[2] = {nullptr, nullptr};            // ... laid out as gzip members
-  csdefl::ChunkInfo *d_chunk[2] = {nullptr, nullptr};
-  uint32_t *d_chunk_dst[2] = {nullptr, nullptr};
+  GzStream gz[2];                                   // cs_text_params.compress: the mates' gzip members
   uint32_t *d_blk = nullptr;              // block sums of the newline passes (per mate) and of the format passes
   unsigned long long *d_totals = nullptr;  // [2] line totals, [6] format column sums
   cstext::TextMeta *d_meta = nullptr;
@@ -1375,9 +1380,8 @@ struct TextSlot {
   csinfo::InfoRec *d_irec = nullptr;
   uint32_t *d_idst = nullptr, *d_iblk = nullptr;
   unsigned long long *d_itotal = nullptr;
-  uint8_t *d_info = nullptr, *d_igzstage = nullptr, *d_igz = nullptr;
-  csdefl::ChunkInfo *d_ichunk = nullptr;
-  uint32_t *d_ichunk_dst = nullptr;
+  uint8_t *d_info = nullptr;
+  GzStream info_gz;
   csinfo::InfoMeta *d_imeta = nullptr, *h_imeta = nullptr;
   hipEvent_t uploaded = nullptr, formatted = nullptr, fetched = nullptr;
   uint32_t n = 0;
@@ -1413,6 +1417,61 @@ __global__ void text_init_meta(cstext::TextMeta *m) {
     m->err = ~0ull;
   }
 }
+
+// One stream through the deflate kernels: its chunks into their slots, the gzip members laid out, the slots compacted
+// into them.  `route_bytes` / `gz_route_bytes`: the [route][mate] sizes of the stream's mate, raw (in) and gzip (out).
+void launch_deflate(hipStream_t rs, const GzStream &z, const uint8_t *text, const unsigned long long *route_bytes,
+                    unsigned long long *gz_route_bytes, uint32_t n_routes, unsigned long long *gz_total,
+                    uint32_t fasta_classes, bool literal_only, const unsigned long long *gate) {
+  csdefl::DeflateArgs da;
+  da.text = text;
+  da.route_bytes = route_bytes;
+  da.n_routes = n_routes;
+  da.stage = z.stage;
+  da.info = z.chunk;
+  da.max_chunks = z.chunks;
+  da.gate = gate;
+  da.fasta_classes = fasta_classes;
+  da.literal_only = literal_only ? 1u : 0u;
+  hipLaunchKernelGGL(csdefl::deflate_chunks, dim3(z.chunks), dim3(256), 0, rs, da);
+  csdefl::LayoutArgs la;
+  la.info = z.chunk;
+  la.route_bytes = route_bytes;
+  la.n_routes = n_routes;
+  la.chunk_dst = z.chunk_dst;
+  la.gz = z.gz;
+  la.gz_route_bytes = gz_route_bytes;
+  la.gz_total = gz_total;
+  la.gate = gate;
+  hipLaunchKernelGGL(csdefl::deflate_layout, dim3(1), dim3(256), 0, rs, la);
+  csdefl::CompactArgs ca;
+  ca.info = z.chunk;
+  ca.chunk_dst = z.chunk_dst;
+  ca.stage = z.stage;
+  ca.gz = z.gz;
+  ca.route_bytes = route_bytes;
+  ca.n_routes = n_routes;
+  ca.gate = gate;
+  hipLaunchKernelGGL(csdefl::deflate_compact, dim3(z.chunks), dim3(256), 0, rs, ca);
+}
+
+// Hands out 256-byte aligned pieces of a slot's one allocation.  Without a base it only measures.
+struct Carver {
+  uint8_t *base;
+  size_t at = 0;
+  template <class T>
+  void take(T *&p, size_t count) {
+    if (base) p = reinterpret_cast<T *>(base + at);
+    at += (count * sizeof(T) + 255) & ~(size_t)255;
+  }
+  void take(GzStream &z, uint32_t chunks) {
+    z.chunks = chunks;
+    take(z.stage, (size_t)chunks * csdefl::kSlot);
+    take(z.gz, (size_t)chunks * csdefl::kSlot + 64);
+    take(z.chunk, chunks);
+    take(z.chunk_dst, chunks);
+  }
+};
 
 void free_text(cs_text *t) {
   if (!t) return;
@@ -1570,118 +1629,61 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
   const size_t rows = (size_t)max_records * stride;
   for (TextSlot &s : t->slots) {
     // ONE device allocation per slot, carved up (a hundred separate hipMalloc calls cost a short run more than its
-    // kernels).  The part in front is zeroed -- a batch that is rejected half-way leaves some of those arrays unwritten,
-    // and whatever a later kernel of that batch still reads through them must stay inside the allocations -- the
-    // "not a long read" markers behind it are set to all ones.
-    size_t need = 0;
-    auto reserve = [&](size_t bytes) {
-      const size_t at = need;
-      need += (bytes + 255) & ~(size_t)255;
-      return at;
+    // kernels): `carve` names every array once, and runs twice -- to measure, then over the allocation.
+    // Its ORDER is a rule.  First the arrays that are zeroed: a batch that is rejected half-way leaves some of them
+    // unwritten, and whatever a later kernel of that batch still reads through them must stay inside the allocations.
+    // Then the "not a long read" markers, set to all ones for the same reason.  Then everything else.
+    size_t zero_bytes = 0, ones_bytes = 0;
+    auto carve = [&](uint8_t *base) {
+      Carver c{base};
+      for (int m = 0; m < mates; ++m) {
+        c.take(s.d_nl[m], (size_t)max_records * 4 + 8);
+        c.take(s.d_rec[m], max_records);
+        c.take(s.d_idr[m], max_records);
+      }
+      zero_bytes = c.at;
+      for (int m = 0; m < mates; ++m) c.take(s.d_long_of[m], max_records);
+      ones_bytes = c.at - zero_bytes;
+      for (int m = 0; m < mates; ++m) {
+        c.take(s.d_text[m], max_text_bytes + 64);
+        c.take(s.d_seq[m], rows);
+        c.take(s.d_qual[m], rows);
+        c.take(s.d_len[m], max_records);
+        c.take(s.d_res[m], max_records);
+        c.take(s.d_dst[m], max_records);
+        c.take(s.d_out[m], out_cap);
+        c.take(s.d_lrec[m], max_records);
+        c.take(s.d_lres[m], max_records);
+        if (t->compress) c.take(s.gz[m], t->max_chunks);
+      }
+      if (t->needs_cap2) c.take(s.d_cap2, max_records);
+      c.take(s.d_blk, (size_t)2 * (t->seg_blocks + 1) + (size_t)2 * t->n_routes * (t->fmt_blocks + 1));
+      c.take(s.d_totals, 2 + 2 * (size_t)t->n_routes);
+      c.take(s.d_meta, 1);
+      if (t->tp.n_bins) {
+        c.take(s.d_bc, max_records);
+        c.take(s.d_routes, 1);
+      }
+      if (t->tp.max_n)
+        for (int m = 0; m < mates; ++m) c.take(s.d_xf[m], max_records);
+      if (t->info) {
+        c.take(s.d_imatch, (size_t)max_records * (eng->info_adapters ? eng->info_adapters : 1u));
+        c.take(s.d_irec, max_records);
+        c.take(s.d_idst, max_records);
+        c.take(s.d_iblk, (size_t)t->fmt_blocks + 1);
+        c.take(s.d_itotal, 1);
+        c.take(s.d_info, t->info_cap);
+        c.take(s.d_imeta, 1);
+        if (t->info & CS_INFO_GZIP) c.take(s.info_gz, t->info_chunks);
+      }
+      return c.at;
     };
-    size_t o_nl[2], o_rec[2], o_idr[2], o_long_of[2], o_text[2], o_seq[2], o_qual[2], o_len[2], o_res[2], o_dst[2], o_out[2],
-        o_lrec[2], o_lres[2], o_gzstage[2] = {0, 0}, o_gz[2] = {0, 0}, o_chunk[2] = {0, 0}, o_chunk_dst[2] = {0, 0};
-    for (int m = 0; m < mates; ++m) {
-      o_nl[m] = reserve(((size_t)max_records * 4 + 8) * sizeof(uint32_t));
-      o_rec[m] = reserve((size_t)max_records * sizeof(cstext::Rec));
-      o_idr[m] = reserve((size_t)max_records * sizeof(uint32_t));
-    }
-    const size_t zero_bytes = need;
-    for (int m = 0; m < mates; ++m) o_long_of[m] = reserve((size_t)max_records * sizeof(uint32_t));
-    const size_t ones_bytes = need - zero_bytes;
-    for (int m = 0; m < mates; ++m) {
-      o_text[m] = reserve(max_text_bytes + 64);
-      o_seq[m] = reserve(rows);
-      o_qual[m] = reserve(rows);
-      o_len[m] = reserve((size_t)max_records * sizeof(uint16_t));
-      o_res[m] = reserve((size_t)max_records * sizeof(cs_result));
-      o_dst[m] = reserve((size_t)max_records * sizeof(uint32_t));
-      o_out[m] = reserve(out_cap);
-      o_lrec[m] = reserve((size_t)max_records * sizeof(cslong::LongRec));
-      o_lres[m] = reserve((size_t)max_records * sizeof(cslong::LongRes));
-      if (t->compress) {
-        o_gzstage[m] = reserve((size_t)t->max_chunks * csdefl::kSlot);
-        o_gz[m] = reserve((size_t)t->max_chunks * csdefl::kSlot + 64);
-        o_chunk[m] = reserve((size_t)t->max_chunks * sizeof(csdefl::ChunkInfo));
-        o_chunk_dst[m] = reserve((size_t)t->max_chunks * sizeof(uint32_t));
-      }
-    }
-    const size_t o_cap2 = t->needs_cap2 ? reserve((size_t)max_records * sizeof(cs_cap2)) : 0;
-    const size_t o_blk = reserve(((size_t)2 * (t->seg_blocks + 1) + (size_t)2 * t->n_routes * (t->fmt_blocks + 1)) * sizeof(uint32_t));
-    const size_t o_totals = reserve((2 + 2 * (size_t)t->n_routes) * sizeof(unsigned long long));
-    const size_t o_meta = reserve(sizeof(cstext::TextMeta));
-    const size_t o_bc = t->tp.n_bins ? reserve(max_records) : 0;
-    const size_t o_routes = t->tp.n_bins ? reserve(sizeof(RouteBlock)) : 0;
-    size_t o_xf[2] = {0, 0};
-    if (t->tp.max_n)
-      for (int m = 0; m < mates; ++m) o_xf[m] = reserve(max_records);
-    size_t o_imatch = 0, o_irec = 0, o_idst = 0, o_iblk = 0, o_itotal = 0, o_info = 0, o_imeta = 0, o_igzstage = 0, o_igz = 0,
-           o_ichunk = 0, o_ichunk_dst = 0;
+    TXT_TRY(hipMalloc(&s.d_arena, carve(nullptr)));
+    carve(s.d_arena);
+    TXT_TRY(hipMemsetAsync(s.d_arena, 0, zero_bytes, t->h2d));
+    TXT_TRY(hipMemsetAsync(s.d_arena + zero_bytes, 0xff, ones_bytes, t->h2d));
+    if (t->tp.n_bins) TXT_TRY(hipHostMalloc(&s.h_routes, sizeof(RouteBlock), hipHostMallocPortable));
     if (t->info) {
-      o_imatch = reserve((size_t)max_records * (eng->info_adapters ? eng->info_adapters : 1u) * sizeof(csinfo::InfoMatch));
-      o_irec = reserve((size_t)max_records * sizeof(csinfo::InfoRec));
-      o_idst = reserve((size_t)max_records * sizeof(uint32_t));
-      o_iblk = reserve(((size_t)t->fmt_blocks + 1) * sizeof(uint32_t));
-      o_itotal = reserve(sizeof(unsigned long long));
-      o_info = reserve(t->info_cap);
-      o_imeta = reserve(sizeof(csinfo::InfoMeta));
-      if (t->info & CS_INFO_GZIP) {
-        o_igzstage = reserve((size_t)t->info_chunks * csdefl::kSlot);
-        o_igz = reserve((size_t)t->info_chunks * csdefl::kSlot + 64);
-        o_ichunk = reserve((size_t)t->info_chunks * sizeof(csdefl::ChunkInfo));
-        o_ichunk_dst = reserve((size_t)t->info_chunks * sizeof(uint32_t));
-      }
-    }
-    TXT_TRY(hipMalloc(&s.d_arena, need));
-    uint8_t *base = s.d_arena;
-    TXT_TRY(hipMemsetAsync(base, 0, zero_bytes, t->h2d));
-    TXT_TRY(hipMemsetAsync(base + zero_bytes, 0xff, ones_bytes, t->h2d));
-    for (int m = 0; m < mates; ++m) {
-      s.d_nl[m] = reinterpret_cast<uint32_t *>(base + o_nl[m]);
-      s.d_rec[m] = reinterpret_cast<cstext::Rec *>(base + o_rec[m]);
-      s.d_idr[m] = reinterpret_cast<uint32_t *>(base + o_idr[m]);
-      s.d_long_of[m] = reinterpret_cast<uint32_t *>(base + o_long_of[m]);
-      s.d_text[m] = base + o_text[m];
-      s.d_seq[m] = base + o_seq[m];
-      s.d_qual[m] = base + o_qual[m];
-      s.d_len[m] = reinterpret_cast<uint16_t *>(base + o_len[m]);
-      s.d_res[m] = reinterpret_cast<cs_result *>(base + o_res[m]);
-      s.d_dst[m] = reinterpret_cast<uint32_t *>(base + o_dst[m]);
-      s.d_out[m] = base + o_out[m];
-      s.d_lrec[m] = reinterpret_cast<cslong::LongRec *>(base + o_lrec[m]);
-      s.d_lres[m] = reinterpret_cast<cslong::LongRes *>(base + o_lres[m]);
-      if (t->compress) {
-        s.d_gzstage[m] = base + o_gzstage[m];
-        s.d_gz[m] = base + o_gz[m];
-        s.d_chunk[m] = reinterpret_cast<csdefl::ChunkInfo *>(base + o_chunk[m]);
-        s.d_chunk_dst[m] = reinterpret_cast<uint32_t *>(base + o_chunk_dst[m]);
-      }
-    }
-    if (t->needs_cap2) s.d_cap2 = reinterpret_cast<cs_cap2 *>(base + o_cap2);
-    if (t->tp.max_n)
-      for (int m = 0; m < mates; ++m) s.d_xf[m] = base + o_xf[m];
-    s.d_blk = reinterpret_cast<uint32_t *>(base + o_blk);
-    s.d_totals = reinterpret_cast<unsigned long long *>(base + o_totals);
-    s.d_meta = reinterpret_cast<cstext::TextMeta *>(base + o_meta);
-    if (t->tp.n_bins) {
-      s.d_bc = base + o_bc;
-      s.d_routes = reinterpret_cast<RouteBlock *>(base + o_routes);
-      TXT_TRY(hipHostMalloc(&s.h_routes, sizeof(RouteBlock), hipHostMallocPortable));
-    }
-    if (t->info) {
-      s.d_imatch = reinterpret_cast<csinfo::InfoMatch *>(base + o_imatch);
-      s.d_irec = reinterpret_cast<csinfo::InfoRec *>(base + o_irec);
-      s.d_idst = reinterpret_cast<uint32_t *>(base + o_idst);
-      s.d_iblk = reinterpret_cast<uint32_t *>(base + o_iblk);
-      s.d_itotal = reinterpret_cast<unsigned long long *>(base + o_itotal);
-      s.d_info = base + o_info;
-      s.d_imeta = reinterpret_cast<csinfo::InfoMeta *>(base + o_imeta);
-      if (t->info & CS_INFO_GZIP) {
-        s.d_igzstage = base + o_igzstage;
-        s.d_igz = base + o_igz;
-        s.d_ichunk = reinterpret_cast<csdefl::ChunkInfo *>(base + o_ichunk);
-        s.d_ichunk_dst = reinterpret_cast<uint32_t *>(base + o_ichunk_dst);
-      }
       TXT_TRY(hipHostMalloc(&s.h_imeta, sizeof(csinfo::InfoMeta), hipHostMallocPortable));
       memset(s.h_imeta, 0, sizeof(csinfo::InfoMeta));
     }
@@ -1851,72 +1853,18 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
       const unsigned long long iwant = ((unsigned long long)n_records * 32ull + 255ull) / 256ull;
       hipLaunchKernelGGL(csinfo::info_copy, dim3((uint32_t)(iwant > 32768ull ? 32768ull : iwant)), dim3(256), 0, rs, fa, t->tp, ia);
       if (t->info & CS_INFO_GZIP) {  // one more stream for the deflate kernels: one gzip member per batch, like a route
-        csdefl::DeflateArgs da;
-        da.text = s.d_info;
-        da.route_bytes = &s.d_imeta->bytes;
-        da.n_routes = 1;
-        da.stage = s.d_igzstage;
-        da.info = s.d_ichunk;
-        da.max_chunks = t->info_chunks;
-        da.gate = &s.d_meta->err;
-        da.fasta_classes = 0;
-        da.literal_only = t->literal_only ? 1u : 0u;
-        hipLaunchKernelGGL(csdefl::deflate_chunks, dim3(t->info_chunks), dim3(256), 0, rs, da);
-        csdefl::LayoutArgs la;
-        la.info = s.d_ichunk;
-        la.route_bytes = da.route_bytes;
-        la.n_routes = 1;
-        la.chunk_dst = s.d_ichunk_dst;
-        la.gz = s.d_igz;
-        la.gz_route_bytes = &s.d_imeta->gz_bytes;
-        la.gz_total = &s.d_imeta->gz_total;
-        la.gate = da.gate;
-        hipLaunchKernelGGL(csdefl::deflate_layout, dim3(1), dim3(256), 0, rs, la);
-        csdefl::CompactArgs ca;
-        ca.info = s.d_ichunk;
-        ca.chunk_dst = s.d_ichunk_dst;
-        ca.stage = s.d_igzstage;
-        ca.gz = s.d_igz;
-        ca.route_bytes = da.route_bytes;
-        ca.n_routes = 1;
-        ca.gate = da.gate;
-        hipLaunchKernelGGL(csdefl::deflate_compact, dim3(t->info_chunks), dim3(256), 0, rs, ca);
+        launch_deflate(rs, s.info_gz, s.d_info, &s.d_imeta->bytes, &s.d_imeta->gz_bytes, 1, &s.d_imeta->gz_total, 0,
+                       t->literal_only, &s.d_meta->err);
       }
       HIP_TRY(hipGetLastError());
     }
     if (t->compress) {
       for (int m = 0; m < mates; ++m) {
-        csdefl::DeflateArgs da;
-        da.text = s.d_out[m];
-        da.route_bytes = t->tp.n_bins ? &s.d_routes->bytes[0][m] : &s.d_meta->route_bytes[0][m];
-        da.n_routes = t->n_routes;
-        da.stage = s.d_gzstage[m];
-        da.info = s.d_chunk[m];
-        da.max_chunks = t->max_chunks;
-        da.gate = &s.d_meta->err;
-        da.fasta_classes = 0;
-        for (uint32_t c = 0; c < 4u; ++c) da.fasta_classes |= ((t->tp.fasta_routes >> (2u * c + m)) & 1u) << c;
-        da.literal_only = t->literal_only ? 1u : 0u;
-        hipLaunchKernelGGL(csdefl::deflate_chunks, dim3(t->max_chunks), dim3(256), 0, rs, da);
-        csdefl::LayoutArgs la;
-        la.info = s.d_chunk[m];
-        la.route_bytes = da.route_bytes;
-        la.n_routes = t->n_routes;
-        la.chunk_dst = s.d_chunk_dst[m];
-        la.gz = s.d_gz[m];
-        la.gz_route_bytes = t->tp.n_bins ? &s.d_routes->gz_bytes[0][m] : &s.d_meta->gz_route_bytes[0][m];
-        la.gz_total = &s.d_meta->gz_bytes[m];
-        la.gate = da.gate;
-        hipLaunchKernelGGL(csdefl::deflate_layout, dim3(1), dim3(256), 0, rs, la);
-        csdefl::CompactArgs ca;
-        ca.info = s.d_chunk[m];
-        ca.chunk_dst = s.d_chunk_dst[m];
-        ca.stage = s.d_gzstage[m];
-        ca.gz = s.d_gz[m];
-        ca.route_bytes = da.route_bytes;
-        ca.n_routes = t->n_routes;
-        ca.gate = da.gate;
-        hipLaunchKernelGGL(csdefl::deflate_compact, dim3(t->max_chunks), dim3(256), 0, rs, ca);
+        uint32_t fasta_classes = 0;
+        for (uint32_t c = 0; c < 4u; ++c) fasta_classes |= ((t->tp.fasta_routes >> (2u * c + m)) & 1u) << c;
+        launch_deflate(rs, s.gz[m], s.d_out[m], t->tp.n_bins ? &s.d_routes->bytes[0][m] : &s.d_meta->route_bytes[0][m],
+                       t->tp.n_bins ? &s.d_routes->gz_bytes[0][m] : &s.d_meta->gz_route_bytes[0][m], t->n_routes,
+                       &s.d_meta->gz_bytes[m], fasta_classes, t->literal_only, &s.d_meta->err);
       }
       HIP_TRY(hipGetLastError());
     }
@@ -2018,7 +1966,7 @@ int cs_text_fetch(cs_text *t, uint32_t slot, void *dst1, void *dst2) {
     const size_t bytes = (size_t)(t->compress ? s.h_meta->gz_bytes[m] : s.h_meta->out_bytes[m]);
     if (!bytes) continue;
     if (!dst[m]) return fail(CS_ERR_ARG, "mate %d: %zu bytes of output and no buffer", m + 1, bytes);
-    HIP_TRY(hipMemcpyAsync(dst[m], t->compress ? s.d_gz[m] : s.d_out[m], bytes, hipMemcpyDeviceToHost, t->d2h));
+    HIP_TRY(hipMemcpyAsync(dst[m], t->compress ? s.gz[m].gz : s.d_out[m], bytes, hipMemcpyDeviceToHost, t->d2h));
   }
   HIP_TRY(hipEventRecord(s.fetched, t->d2h));
   HIP_TRY(hipEventSynchronize(s.fetched));
@@ -2050,7 +1998,7 @@ int cs_text_fetch_info(cs_text *t, uint32_t slot, void *dst) {
   const size_t bytes = (size_t)(gz ? s.h_imeta->gz_total : s.h_imeta->bytes);
   if (!bytes) return CS_OK;
   if (!dst) return fail(CS_ERR_ARG, "%zu bytes of info table and no buffer", bytes);
-  HIP_TRY(hipMemcpyAsync(dst, gz ? s.d_igz : s.d_info, bytes, hipMemcpyDeviceToHost, t->d2h));
+  HIP_TRY(hipMemcpyAsync(dst, gz ? s.info_gz.gz : s.d_info, bytes, hipMemcpyDeviceToHost, t->d2h));
   HIP_TRY(hipStreamSynchronize(t->d2h));
   return CS_OK;
 }

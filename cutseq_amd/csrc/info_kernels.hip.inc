@@ -6,9 +6,9 @@
 // match, every input record, input order.  The trimming kernels keep the surviving interval and eight flag bits per
 // read; where an op matched and with how many errors is lost.  Nothing here runs unless cs_text_params.info asks:
 //
-//   info_record    one lane per record of mate 1: the op chain once more, straight from the uploaded text (any read
-//                  length), with Aligner.locate as the long-read kernel restates it -- its columns sized by the plan's
-//                  longest adapter -- and every match written down: (adapter ordinal, rstart, rstop, errors, interval
+//   info_record    one lane per record of mate 1: the long-read kernel's walk of the op chain (cslong::walk_chain),
+//                  straight from the uploaded text (any read length) -- the aligner's columns sized by the plan's
+//                  longest adapter -- with every match written down: (adapter ordinal, rstart, rstop, errors, interval
 //                  at match time).  An adapter op whose flag bit no other op of the chain sets, and which the trimming
 //                  kernels' result shows unset, did not match: its alignment is skipped.  The walk's final interval
 //                  and flags must be what the trimming kernels produced for the record; anything else is reported as
@@ -106,110 +106,63 @@ __device__ __forceinline__ NameView name_view(const FormatArgs &a, const TextPar
   return n;
 }
 
+struct Recorder {  // what info_record keeps of a walk: every match, and the bytes of the rows they make
+  static constexpr bool kDemux = false;  // (cs_text_create refuses info on a plan with a CS_OP_DEMUX op)
+  InfoMatch *mine;
+  uint32_t n_adapters, uniq_flags, trimmed_flags, per_base;
+  int max_m;  // the adapter length the walk's columns are sized for
+  uint32_t ordinal = 0, row_bytes = 0;
+
+  __device__ __forceinline__ bool adapter_runs(const cs_op &op) {
+    ++ordinal;
+    // the trimming kernels say "this op did not match" where the flag is the op's alone
+    const bool known_miss = (op.match_flag & uniq_flags) && !(trimmed_flags & op.match_flag);
+    return !known_miss && (int)op.m <= max_m;  // (info_max_m selects the instantiation: the host never lets m exceed it)
+  }
+  __device__ __forceinline__ void adapter_matched(const cs_op &, const cslong::Walk &w, int rstart, int rstop, int errors) {
+    if ((uint32_t)w.n_matches < n_adapters) {
+      InfoMatch m;
+      m.s = (uint32_t)w.s;
+      m.e = (uint32_t)w.e;
+      m.rstart = (uint32_t)rstart;
+      m.rstop = (uint32_t)rstop;
+      m.errors = (uint16_t)errors;
+      m.name = (uint8_t)ordinal;
+      m._pad = 0;
+      mine[w.n_matches] = m;
+    }
+    row_bytes += 12u + dec_width((uint32_t)errors) + dec_width((uint32_t)rstart) + dec_width((uint32_t)rstop) +
+                 dec_width(ordinal) + per_base * (uint32_t)(w.e - w.s);
+  }
+  __device__ __forceinline__ void cut(const cs_op &, int, int) {}
+  __device__ __forceinline__ void quality_trimmed(int) {}
+};
+
 template <int kMaxM>
 __global__ void __launch_bounds__(64) info_record(FormatArgs a, TextParams tp, InfoArgs ia) {
   if (a.meta->err != ~0ull) return;
   const uint32_t r = blockIdx.x * 64u + threadIdx.x;
   if (r >= a.n) return;
   const DevPlan *plan = &csdev::c_plans[ia.plan_slot];
-  const int n_ops = plan->n_ops[0];
-  const int rule = plan->params.select_rule;
-  const bool tie_ins = plan->params.indel_tie == CS_TIE_INSERTION;
-  const bool fold = plan->params.case_rule == CS_CASE_FOLD;
-  const bool coded = plan->coded != 0;
+  const cslong::Env env(plan);
   const cstext::Rec rc = a.rec[0][r];
   const uint32_t slot = a.long_of[0][r];
-  const uint8_t *seq = a.text[0] + rc.seq_off, *qual = a.text[0] + rc.qual_off;
   const ReadView v = cstext::read_view(a, 0, r);  // what the trimming kernels made of the record
-  InfoMatch *mine = ia.match + (size_t)r * ia.n_adapters;
-  int s = 0, e = (int)(slot != cstext::kNotLong ? a.lrec[0][slot].len : (uint32_t)rc.len), n_matches = 0;
-  uint32_t flags = 0, ordinal = 0, row_bytes = 0;
   const uint32_t per_base = ia.no_qual ? 1u : 2u;
-  for (int t = 0; t < n_ops; ++t) {
-    const DevOp &d = plan->ops[0][t];
-    const cs_op &op = d.op;
-    const int n = e - s;
-    if (op.kind == CS_OP_ADAPTER) {
-      ++ordinal;
-      int qs = 0, qe = 0, errors = 0;
-      bool hit = false;
-      // the trimming kernels say "this op did not match" where the flag is the op's alone
-      const bool known_miss = (op.match_flag & ia.uniq_flags) && !(v.flags & op.match_flag);
-      if (!known_miss && (int)op.m <= kMaxM) {
-        if (op.shortcut == CS_SHORTCUT_FIND) {
-          for (int p = 0; p + (int)op.m <= n && !hit; ++p) {
-            int i = 0;
-            for (; i < (int)op.m; ++i)
-              if (cslong::query_code(seq[s + (op.reversed ? n - 1 - (p + i) : p + i)], coded, fold) != (uint32_t)op.seq[i]) break;
-            if (i == (int)op.m) {
-              hit = true;
-              qs = p;
-              qe = p + op.m;
-            }
-          }
-        }
-        if (!hit) hit = cslong::locate_sized<kMaxM>(d, coded, fold, rule, tie_ins, seq + s, n, qs, qe, errors);
-      }
-      if (hit) {
-        int rstart = qs, rstop = qe;
-        if (op.reversed) {  // RightmostFrontAdapter.match_to: back to forward coordinates
-          rstart = n - qe;
-          rstop = n - qs;
-        }
-        if ((uint32_t)n_matches < ia.n_adapters) {
-          InfoMatch m;
-          m.s = (uint32_t)s;
-          m.e = (uint32_t)e;
-          m.rstart = (uint32_t)rstart;
-          m.rstop = (uint32_t)rstop;
-          m.errors = (uint16_t)errors;
-          m.name = (uint8_t)ordinal;
-          m._pad = 0;
-          mine[n_matches] = m;
-        }
-        row_bytes += 12u + dec_width((uint32_t)errors) + dec_width((uint32_t)rstart) + dec_width((uint32_t)rstop) +
-                     dec_width(ordinal) + per_base * (uint32_t)n;
-        ++n_matches;
-        flags |= op.match_flag;
-        if (op.remove == CS_REMOVE_BEFORE)
-          s += rstop;
-        else
-          e = s + rstart;
-      } else if (op.required) {
-        flags |= CS_F_UNTRIMMED;
-      }
-    } else if (op.kind == CS_OP_CUT) {
-      if (op.conditional && n_matches == 0 && n < (int)op.force_min_len) continue;
-      if (op.cut_len > 0)
-        s += min((int)op.cut_len, n);
-      else if (op.cut_len < 0)
-        e -= min(-(int)op.cut_len, n);
-    } else if (op.kind == CS_OP_QTRIM) {
-      int sum = 0, best = 0, stop = n;
-      for (int i = n - 1; i >= 0; --i) {
-        sum += (int)op.q_cutoff - ((int)qual[s + i] - (int)op.q_base);
-        if (sum < 0) break;
-        if (sum > best) {
-          best = sum;
-          stop = i;
-        }
-      }
-      if (stop < n) flags |= CS_F_QTRIMMED;
-      e = s + stop;
-    }
-    // (CS_OP_DEMUX: cs_text_create refuses info on such a plan)
-  }
-  if (e - s < (int)plan->params.min_length) flags |= CS_F_TOO_SHORT;
+  Recorder ev{ia.match + (size_t)r * ia.n_adapters, ia.n_adapters, ia.uniq_flags, v.flags, per_base, kMaxM};
+  const cslong::Walk w = cslong::walk_chain<kMaxM>(plan, 0, env, a.text[0] + rc.seq_off, a.text[0] + rc.qual_off,
+                                                   (int)(slot != cstext::kNotLong ? a.lrec[0][slot].len : (uint32_t)rc.len), ev);
   // the table must not disagree with the records next to it
-  if ((uint32_t)s != v.start || (uint32_t)e != v.stop || flags != v.flags) cstext::report(a.meta, r, ERR_INFO_MISMATCH);
+  if ((uint32_t)w.s != v.start || (uint32_t)w.e != v.stop || w.flags != v.flags) cstext::report(a.meta, r, ERR_INFO_MISMATCH);
   const NameView nm = name_view(a, tp, r, v);
-  if (n_matches == 0)
-    row_bytes = 7u + per_base * (uint32_t)(e - s);  // name "\t-1\t" seq '\t' qual "\t\n"
-  row_bytes += (uint32_t)max(n_matches, 1) * nm.len();
+  uint32_t row_bytes = ev.row_bytes;
+  if (w.n_matches == 0)
+    row_bytes = 7u + per_base * (uint32_t)(w.e - w.s);  // name "\t-1\t" seq '\t' qual "\t\n"
+  row_bytes += (uint32_t)max(w.n_matches, 1) * nm.len();
   InfoRec out;
-  out.start = (uint32_t)s;
-  out.stop = (uint32_t)e;
-  out.n_matches = (uint32_t)n_matches;
+  out.start = (uint32_t)w.s;
+  out.stop = (uint32_t)w.e;
+  out.n_matches = (uint32_t)w.n_matches;
   out.bytes = row_bytes;
   ia.rec[r] = out;
 }

@@ -10,6 +10,10 @@
 // SURVEY.md appendix B.2 statement for statement; cutters, demultiplexing, quality trimming and the filters as in
 // trim_kernel.  Long reads are rare in the libraries cutseq is used on: this kernel is exact, not fast
 // (a 20 kb read costs its lane a few million instructions per adapter op).
+//
+// walk_chain is that scalar walk, once: long_kernel calls it for the long reads of either mate, info_record
+// (info_kernels.hip.inc) for every record of mate 1.  What a caller does beyond the interval and the flags -- statistics,
+// captures and demultiplexing here, the match table there -- lives in the events object it passes in.
 
 namespace cslong {
 
@@ -29,6 +33,14 @@ struct LongRes {  // its result: cs_result + cs_cap2 with 32-bit positions
   uint8_t xflags, _pad[3];  // CS_X_* (TooManyN)
 };
 
+struct Env {  // the plan's aligner settings
+  int rule;
+  bool tie_ins, fold, coded;
+  __device__ explicit Env(const DevPlan *plan)
+      : rule(plan->params.select_rule), tie_ins(plan->params.indel_tie == CS_TIE_INSERTION),
+        fold(plan->params.case_rule == CS_CASE_FOLD), coded(plan->coded != 0) {}
+};
+
 __device__ __forceinline__ uint32_t query_code(uint8_t c, bool coded, bool fold) {
   if (fold && c >= 'a' && c <= 'z') c = (uint8_t)(c - 32);
   return coded ? csdev::base_code(c) : (uint32_t)c;
@@ -38,9 +50,11 @@ __device__ __forceinline__ uint32_t query_code(uint8_t c, bool coded, bool fold)
 // the adapter length the three columns are sized for (the caller vouches for op.m <= kMaxM); `errors` receives the
 // cost of the selected candidate (Match.errors).
 template <int kMaxM>
-__device__ __forceinline__ bool locate_sized(const DevOp &d, bool coded, bool fold, int rule, bool tie_ins, const uint8_t *q,
-                                             int n, int &qs, int &qe, int &errors) {
+__device__ __forceinline__ bool locate_sized(const DevOp &d, const Env &v, const uint8_t *q, int n, int &qs, int &qe,
+                                             int &errors) {
   const cs_op &op = d.op;
+  const int rule = v.rule;
+  const bool tie_ins = v.tie_ins;
   const int m = op.m, k = op.k, flags = op.align_flags, min_overlap = op.min_overlap;
   const bool RS = flags & CS_REF_START, QS = flags & CS_QUERY_START;
   const bool RE = flags & CS_REF_END, QSTOP = flags & CS_QUERY_STOP;
@@ -73,7 +87,7 @@ __device__ __forceinline__ bool locate_sized(const DevOp &d, bool coded, bool fo
       corigin[0] = j;
     else
       ccost[0] = j;
-    const uint32_t qc = query_code(q[reversed ? n - j : j - 1], coded, fold);
+    const uint32_t qc = query_code(q[reversed ? n - j : j - 1], v.coded, v.fold);
     for (int i = 1; i <= last; ++i) {
       int cost, score, origin;
       if ((uint32_t)op.seq[i - 1] == qc) {
@@ -148,10 +162,122 @@ __device__ __forceinline__ bool locate_sized(const DevOp &d, bool coded, bool fo
   return true;
 }
 
-__device__ bool locate(const DevOp &d, bool coded, bool fold, int rule, bool tie_ins, const uint8_t *q, int n, int &qs,
-                       int &qe) {
-  int errors;
-  return locate_sized<CS_MAX_ADAPTER>(d, coded, fold, rule, tie_ins, q, n, qs, qe, errors);
+// cutadapt <= 2.x (CS_SHORTCUT_FIND): str.find on the query as the aligner sees it
+__device__ __forceinline__ bool find_exact(const cs_op &op, const Env &v, const uint8_t *q, int n, int &qs, int &qe) {
+  for (int p = 0; p + (int)op.m <= n; ++p) {
+    int i = 0;
+    for (; i < (int)op.m; ++i)
+      if (query_code(q[op.reversed ? n - 1 - (p + i) : p + i], v.coded, v.fold) != (uint32_t)op.seq[i]) break;
+    if (i == (int)op.m) {
+      qs = p;
+      qe = p + op.m;
+      return true;
+    }
+  }
+  return false;
+}
+
+// cutadapt quality_trim_index (cutoff_front = 0) on qual[0, n): BWA running sum from the 3' end, first strict maximum
+__device__ __forceinline__ int quality_stop(const cs_op &op, const uint8_t *qual, int n) {
+  int sum = 0, best = 0, stop = n;
+  for (int i = n - 1; i >= 0; --i) {
+    sum += (int)op.q_cutoff - ((int)qual[i] - (int)op.q_base);
+    if (sum < 0) break;
+    if (sum > best) {
+      best = sum;
+      stop = i;
+    }
+  }
+  return stop;
+}
+
+// Where a demultiplexing table keeps the first `depth` bases of q[0, n) -- read from the 5' end, or backwards from the
+// 3' end -- : the block of the prefixes of min(n, depth) bases, then the prefix in base 5 (A, C, G, T, anything else).
+__device__ __forceinline__ uint32_t prefix_index(const uint8_t *q, int n, int depth, bool from_end, bool fold) {
+  const int take = min(n, depth);
+  uint32_t idx = 0, pw = 1, block = 0;
+  for (int u = 0; u < depth; ++u) {
+    if (u < take) {
+      uint8_t ch = q[from_end ? n - 1 - u : u];
+      if (fold && ch >= 'a' && ch <= 'z') ch = (uint8_t)(ch - 32);
+      const uint32_t digit = (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T') ? (((uint32_t)ch >> 1) & 3u) : 4u;
+      idx += digit * pw;
+      block += pw;
+    }
+    pw *= 5u;
+  }
+  return block + idx;
+}
+
+struct Walk {  // a read on its way through the chain
+  int s, e;  // the interval that is left of it
+  uint32_t flags;
+  int n_matches;
+};
+
+// One mate's op chain on one read, straight from its text.  kMaxM sizes the aligner's columns.  `ev` is the caller's:
+//   bool adapter_runs(op)      in front of an adapter op; false: the caller knows it does not match, nothing is aligned
+//   adapter_matched(op, w, rstart, rstop, errors)   the match, `w` still as the op found it
+//   cut(op, off, c)            a cutter took c bases at off
+//   quality_trimmed(k)         the quality trimmer took k bases
+//   demux(d, v, seq, w)        a CS_OP_DEMUX op, the caller's to apply (Events::kDemux; compiled out where false)
+template <int kMaxM, class Events>
+__device__ __forceinline__ Walk walk_chain(const DevPlan *plan, int mate, const Env &v, const uint8_t *seq, const uint8_t *qual,
+                                           int len, Events &ev) {
+  Walk w = {0, len, 0u, 0};
+  const int n_ops = plan->n_ops[mate];
+  for (int t = 0; t < n_ops; ++t) {
+    const DevOp &d = plan->ops[mate][t];
+    const cs_op &op = d.op;
+    const int n = w.e - w.s;
+    if (op.kind == CS_OP_ADAPTER) {
+      int qs = 0, qe = 0, errors = 0;
+      bool hit = false;
+      if (ev.adapter_runs(op)) {
+        hit = op.shortcut == CS_SHORTCUT_FIND && find_exact(op, v, seq + w.s, n, qs, qe);
+        if (!hit) hit = locate_sized<kMaxM>(d, v, seq + w.s, n, qs, qe, errors);
+      }
+      if (hit) {
+        int rstart = qs, rstop = qe;
+        if (op.reversed) {  // RightmostFrontAdapter.match_to: back to forward coordinates
+          rstart = n - qe;
+          rstop = n - qs;
+        }
+        ev.adapter_matched(op, w, rstart, rstop, errors);
+        ++w.n_matches;
+        w.flags |= op.match_flag;
+        if (op.remove == CS_REMOVE_BEFORE)
+          w.s += rstop;
+        else
+          w.e = w.s + rstart;
+      } else if (op.required) {
+        w.flags |= CS_F_UNTRIMMED;
+      }
+    } else if (op.kind == CS_OP_CUT) {
+      if (op.conditional && w.n_matches == 0 && n < (int)op.force_min_len) continue;
+      if (op.cut_len == 0) continue;
+      int c, off;
+      if (op.cut_len > 0) {
+        c = min((int)op.cut_len, n);
+        off = w.s;
+        w.s += c;
+      } else {
+        c = min(-(int)op.cut_len, n);
+        off = w.e - c;
+        w.e -= c;
+      }
+      ev.cut(op, off, c);
+    } else if (op.kind == CS_OP_DEMUX) {
+      if constexpr (Events::kDemux) ev.demux(d, v, seq, w);
+    } else if (op.kind == CS_OP_QTRIM) {
+      const int stop = quality_stop(op, qual + w.s, n);
+      if (stop < n) w.flags |= CS_F_QTRIMMED;
+      ev.quality_trimmed(n - stop);
+      w.e = w.s + stop;
+    }
+  }
+  if (w.e - w.s < (int)plan->params.min_length) w.flags |= CS_F_TOO_SHORT;
+  return w;
 }
 
 struct LongArgs {
@@ -166,201 +292,120 @@ struct LongArgs {
   const unsigned long long *gate;
 };
 
+struct LongEvents {  // what long_kernel keeps of a walk besides the interval and the flags
+  static constexpr bool kDemux = true;
+  unsigned long long *stats;
+  uint32_t bc = CS_DEMUX_NONE, cap_off = 0, cap_len = 0, cap2_off = 0, cap2_len = 0, qtrimmed = 0;
+
+  __device__ __forceinline__ bool adapter_runs(const cs_op &) const { return true; }
+  __device__ __forceinline__ void adapter_matched(const cs_op &op, const Walk &, int, int, int) {
+    atomicAdd(&stats[csdev::ST_OPS + op.stat_slot], 1ull);
+  }
+  __device__ __forceinline__ void cut(const cs_op &op, int off, int c) {
+    // (selects, not branches: stores to one capture or the other become one store through a selected address, and
+    // that keeps all four words in scratch)
+    const bool one = op.capture == 1, two = op.capture == 2;
+    cap_off = one ? (uint32_t)off : cap_off;
+    cap_len = one ? (uint32_t)c : cap_len;
+    cap2_off = two ? (uint32_t)off : cap2_off;
+    cap2_len = two ? (uint32_t)c : cap2_len;
+  }
+  __device__ __forceinline__ void quality_trimmed(int k) { qtrimmed += (uint32_t)k; }
+
+  __device__ __forceinline__ void demux(const DevOp &d, const Env &v, const uint8_t *seq, Walk &w) {
+    const cs_op &op = d.op;
+    const int s = w.s, n = w.e - w.s;
+    const bool at_end = d.filter_mode && op.reversed != 0;  // barcodes at the 3' end: SuffixAdapter ops
+    uint32_t id = CS_DEMUX_NONE;
+    int cut = 0;
+    bool ambiguous = false;
+    if (d.filter_mode) {
+      // the barcodes' own ops (cs_plan_set_demux_ops): candidates from the table over the first bases, each one's
+      // PrefixAdapter located on the read, the outcomes merged as in trim_kernel
+      const uint32_t *first = reinterpret_cast<const uint32_t *>((uintptr_t)d.peq[0]);
+      const uint8_t *pool = reinterpret_cast<const uint8_t *>((uintptr_t)d.peq[1]);
+      const DevOp *bops = reinterpret_cast<const DevOp *>((uintptr_t)d.peq[2]);
+      const uint32_t ent = first[prefix_index(seq + s, n, (int)d.peq[3], at_end, v.fold)];
+      const uint32_t cnt = ent & 0xffu, off = ent >> 8;
+      uint32_t hits = 0;
+      bool exact_taken = false;
+      const int mb = (int)op.m;
+      for (uint32_t ci = 0; ci < cnt; ++ci) {
+        const uint32_t b = pool[off + ci];
+        const DevOp &bd = bops[b];
+        int qs = 0, qe = 0, errors;
+        if (!locate_sized<CS_MAX_ADAPTER>(bd, v, seq + s, n, qs, qe, errors)) continue;
+        bool exact = n >= mb && (at_end ? qs == n - mb : qe == mb);
+        for (int i = 0; exact && i < mb; ++i)
+          exact = query_code(seq[at_end ? s + n - mb + i : s + i], v.coded, v.fold) == (uint32_t)bd.op.seq[i];
+        if (id == CS_DEMUX_NONE || (exact && !exact_taken)) {
+          id = b;
+          cut = at_end ? qs : qe;
+        }
+        exact_taken = exact_taken || exact;
+        ++hits;
+      }
+      ambiguous = hits > 1u;
+    } else {  // the table over every prefix of m + k bases: barcode, bases to remove, "several barcodes claim it"
+      const uint16_t *table = reinterpret_cast<const uint16_t *>((uintptr_t)d.peq[0]);
+      const uint32_t entry = table[prefix_index(seq + s, n, (int)op.m + (int)op.k, false, v.fold)];
+      if ((entry & 0xffu) != CS_DEMUX_NONE) id = entry & 0xffu;
+      cut = (int)((entry >> 8) & 0xfu);
+      ambiguous = (entry & 0x4000u) != 0;
+    }
+    if (id != CS_DEMUX_NONE) {
+      if (at_end)
+        w.e = s + cut;  // SuffixAdapter: RemoveAfterMatch
+      else
+        w.s += cut;
+      ++w.n_matches;
+      w.flags |= op.match_flag;
+      atomicAdd(&stats[csdev::ST_OPS + op.stat_slot], 1ull);
+      if (ambiguous) w.flags |= CS_F_AMBIGUOUS;
+      bc = id;
+    } else if (op.required) {
+      w.flags |= CS_F_UNTRIMMED;
+    }
+  }
+};
+
 __global__ void __launch_bounds__(64) long_kernel(LongArgs a) {
   if (a.gate && *a.gate != ~0ull) return;
   const DevPlan *plan = &csdev::c_plans[a.plan_slot];
-  const int n_ops = plan->n_ops[a.mate];
-  const int rule = plan->params.select_rule;
-  const bool tie_ins = plan->params.indel_tie == CS_TIE_INSERTION;
-  const bool fold = plan->params.case_rule == CS_CASE_FOLD;
-  const bool coded = plan->coded != 0;
+  const Env v(plan);
   const uint32_t total = min(*a.n_long, a.cap);
   for (uint32_t it = blockIdx.x * 64u + threadIdx.x; it < total; it += gridDim.x * 64u) {
     const LongRec lr = a.rec[it];
-    const uint8_t *seq = a.text + lr.seq_off, *qual = a.text + lr.qual_off;
-    int s = 0, e = (int)lr.len, n_matches = 0;
-    uint32_t flags = 0, bc = CS_DEMUX_NONE;
-    uint32_t cap_off = 0, cap_len = 0, cap2_off = 0, cap2_len = 0, qtrimmed = 0;
-    for (int t = 0; t < n_ops; ++t) {
-      const DevOp &d = plan->ops[a.mate][t];
-      const cs_op &op = d.op;
-      const int n = e - s;
-      if (op.kind == CS_OP_ADAPTER) {
-        int qs = 0, qe = 0;
-        bool hit = false;
-        if (op.shortcut == CS_SHORTCUT_FIND) {  // cutadapt <= 2.x: str.find on the query as the aligner sees it
-          for (int p = 0; p + (int)op.m <= n && !hit; ++p) {
-            int i = 0;
-            for (; i < (int)op.m; ++i)
-              if (query_code(seq[s + (op.reversed ? n - 1 - (p + i) : p + i)], coded, fold) != (uint32_t)op.seq[i]) break;
-            if (i == (int)op.m) {
-              hit = true;
-              qs = p;
-              qe = p + op.m;
-            }
-          }
-        }
-        if (!hit) hit = locate(d, coded, fold, rule, tie_ins, seq + s, n, qs, qe);
-        if (hit) {
-          int rstart = qs, rstop = qe;
-          if (op.reversed) {
-            rstart = n - qe;
-            rstop = n - qs;
-          }
-          ++n_matches;
-          flags |= op.match_flag;
-          atomicAdd(&a.stats[csdev::ST_OPS + op.stat_slot], 1ull);
-          if (op.remove == CS_REMOVE_BEFORE)
-            s += rstop;
-          else
-            e = s + rstart;
-        } else if (op.required) {
-          flags |= CS_F_UNTRIMMED;
-        }
-      } else if (op.kind == CS_OP_CUT) {
-        if (op.conditional && n_matches == 0 && n < (int)op.force_min_len) continue;
-        if (op.cut_len == 0) continue;
-        int c, off;
-        if (op.cut_len > 0) {
-          c = min((int)op.cut_len, n);
-          off = s;
-          s += c;
-        } else {
-          c = min(-(int)op.cut_len, n);
-          off = e - c;
-          e -= c;
-        }
-        if (op.capture == 1) {
-          cap_off = (uint32_t)off;
-          cap_len = (uint32_t)c;
-        } else if (op.capture == 2) {
-          cap2_off = (uint32_t)off;
-          cap2_len = (uint32_t)c;
-        }
-      } else if (op.kind == CS_OP_DEMUX && d.filter_mode) {
-        // the barcodes' own ops (cs_plan_set_demux_ops): candidates from the table over the first bases, each one's
-        // PrefixAdapter located on the read, the outcomes merged as in trim_kernel
-        const uint32_t *first = reinterpret_cast<const uint32_t *>((uintptr_t)d.peq[0]);
-        const uint8_t *pool = reinterpret_cast<const uint8_t *>((uintptr_t)d.peq[1]);
-        const DevOp *bops = reinterpret_cast<const DevOp *>((uintptr_t)d.peq[2]);
-        const int depth = (int)d.peq[3];
-        const bool at_end = op.reversed != 0;  // barcodes at the 3' end: SuffixAdapter ops
-        const int take = min(n, depth);
-        uint32_t idx = 0, pw = 1, block = 0;
-        for (int u = 0; u < depth; ++u) {
-          if (u < take) {
-            uint8_t ch = seq[at_end ? s + n - 1 - u : s + u];
-            if (fold && ch >= 'a' && ch <= 'z') ch = (uint8_t)(ch - 32);
-            const uint32_t digit = (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T') ? (((uint32_t)ch >> 1) & 3u) : 4u;
-            idx += digit * pw;
-            block += pw;
-          }
-          pw *= 5u;
-        }
-        const uint32_t ent = first[block + idx];
-        const uint32_t cnt = ent & 0xffu, off = ent >> 8;
-        uint32_t id = CS_DEMUX_NONE, hits = 0;
-        int cut = 0;
-        bool exact_taken = false;
-        const int mb = (int)op.m;
-        for (uint32_t ci = 0; ci < cnt; ++ci) {
-          const uint32_t b = pool[off + ci];
-          const DevOp &bd = bops[b];
-          int qs = 0, qe = 0;
-          if (!locate(bd, coded, fold, rule, tie_ins, seq + s, n, qs, qe)) continue;
-          bool exact = n >= mb && (at_end ? qs == n - mb : qe == mb);
-          for (int i = 0; exact && i < mb; ++i)
-            exact = query_code(seq[at_end ? s + n - mb + i : s + i], coded, fold) == (uint32_t)bd.op.seq[i];
-          if (id == CS_DEMUX_NONE || (exact && !exact_taken)) {
-            id = b;
-            cut = at_end ? qs : qe;
-          }
-          exact_taken = exact_taken || exact;
-          ++hits;
-        }
-        if (id != CS_DEMUX_NONE) {
-          if (at_end)
-            e = s + cut;  // SuffixAdapter: RemoveAfterMatch
-          else
-            s += cut;
-          ++n_matches;
-          flags |= op.match_flag;
-          atomicAdd(&a.stats[csdev::ST_OPS + op.stat_slot], 1ull);
-          if (hits > 1u) flags |= CS_F_AMBIGUOUS;
-          bc = id;
-        } else if (op.required) {
-          flags |= CS_F_UNTRIMMED;
-        }
-      } else if (op.kind == CS_OP_DEMUX) {
-        const int span = (int)op.m + (int)op.k;
-        const uint16_t *table = reinterpret_cast<const uint16_t *>((uintptr_t)d.peq[0]);
-        const int take = min(n, span);
-        uint32_t idx = 0, pw = 1, block = 0;
-        for (int u = 0; u < span; ++u) {
-          if (u < take) {
-            uint8_t ch = seq[s + u];
-            if (fold && ch >= 'a' && ch <= 'z') ch = (uint8_t)(ch - 32);
-            const uint32_t digit = (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T') ? (((uint32_t)ch >> 1) & 3u) : 4u;
-            idx += digit * pw;
-            block += pw;
-          }
-          pw *= 5u;
-        }
-        const uint32_t entry = table[block + idx];
-        if ((entry & 0xffu) != CS_DEMUX_NONE) {
-          s += (int)((entry >> 8) & 0xfu);
-          ++n_matches;
-          flags |= op.match_flag;
-          atomicAdd(&a.stats[csdev::ST_OPS + op.stat_slot], 1ull);
-          if (entry & 0x4000u) flags |= CS_F_AMBIGUOUS;
-          bc = entry & 0xffu;
-        } else if (op.required) {
-          flags |= CS_F_UNTRIMMED;
-        }
-      } else if (op.kind == CS_OP_QTRIM) {
-        // cutadapt quality_trim_index (cutoff_front = 0): BWA running sum from the 3' end, first strict maximum
-        int sum = 0, best = 0, stop = n;
-        for (int i = n - 1; i >= 0; --i) {
-          sum += (int)op.q_cutoff - ((int)qual[s + i] - (int)op.q_base);
-          if (sum < 0) break;
-          if (sum > best) {
-            best = sum;
-            stop = i;
-          }
-        }
-        if (stop < n) flags |= CS_F_QTRIMMED;
-        qtrimmed += (uint32_t)(n - stop);
-        e = s + stop;
-      }
-    }
-    if (e - s < (int)plan->params.min_length) flags |= CS_F_TOO_SHORT;
+    const uint8_t *seq = a.text + lr.seq_off;
+    LongEvents ev{a.stats};
+    const Walk w = walk_chain<CS_MAX_ADAPTER>(plan, a.mate, v, seq, a.text + lr.qual_off, (int)lr.len, ev);
     uint32_t xflags = 0;
     if (plan->max_n_on) {  // TooManyN on the final interval: the read's own bytes, up to CS_MAX_READ of them
       uint32_t nn = 0;
-      for (int i = s; i < e; ++i) nn += (seq[i] | 0x20u) == 'n' ? 1u : 0u;
-      if (csdev::too_many_n(nn, e - s, plan->max_n)) {
+      for (int i = w.s; i < w.e; ++i) nn += (seq[i] | 0x20u) == 'n' ? 1u : 0u;
+      if (csdev::too_many_n(nn, w.e - w.s, plan->max_n)) {
         xflags = CS_X_TOO_MANY_N;
         atomicAdd(&a.stats[csdev::ST_TOO_MANY_N], 1ull);
       }
     }
     LongRes r;
-    r.start = (uint32_t)s;
-    r.stop = (uint32_t)e;
-    r.cap_off = cap_off;
-    r.cap2_off = cap2_off;
-    r.cap_len = (uint8_t)cap_len;
-    r.cap2_len = (uint8_t)cap2_len;
-    r.flags = (uint8_t)flags;
-    r.bc = (uint8_t)bc;
+    r.start = (uint32_t)w.s;
+    r.stop = (uint32_t)w.e;
+    r.cap_off = ev.cap_off;
+    r.cap2_off = ev.cap2_off;
+    r.cap_len = (uint8_t)ev.cap_len;
+    r.cap2_len = (uint8_t)ev.cap2_len;
+    r.flags = (uint8_t)w.flags;
+    r.bc = (uint8_t)ev.bc;
     r.xflags = (uint8_t)xflags;
     r._pad[0] = r._pad[1] = r._pad[2] = 0;
     a.res[it] = r;
     atomicAdd(&a.stats[csdev::ST_READS], 1ull);
     atomicAdd(&a.stats[csdev::ST_IN_BP], (unsigned long long)lr.len);
-    atomicAdd(&a.stats[csdev::ST_OUT_BP], (unsigned long long)(e - s));
-    atomicAdd(&a.stats[csdev::ST_QTRIM_BP], (unsigned long long)qtrimmed);
-    if (flags & CS_F_TOO_SHORT) atomicAdd(&a.stats[csdev::ST_TOO_SHORT], 1ull);
-    if (flags & CS_F_UNTRIMMED) atomicAdd(&a.stats[csdev::ST_UNTRIMMED], 1ull);
+    atomicAdd(&a.stats[csdev::ST_OUT_BP], (unsigned long long)(w.e - w.s));
+    atomicAdd(&a.stats[csdev::ST_QTRIM_BP], (unsigned long long)ev.qtrimmed);
+    if (w.flags & CS_F_TOO_SHORT) atomicAdd(&a.stats[csdev::ST_TOO_SHORT], 1ull);
+    if (w.flags & CS_F_UNTRIMMED) atomicAdd(&a.stats[csdev::ST_UNTRIMMED], 1ull);
   }
 }
 

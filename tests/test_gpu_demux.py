@@ -233,6 +233,107 @@ def test_demux_on_the_3prime_barcode_of_single_end_reads(length, count, text):
             assert got[route][0] == want[route], route
 
 
+def short_barcoded_reads(rng, codes, length, at_end, n=360):
+    """Reads of 0 to 40 nt around the barcodes of ``codes`` (at the 5' end, or ``at_end`` in front of a stretch of the
+    3' adapter): exact, one edit, lower case, an N inside the barcode, a foreign barcode, the midpoint between
+    codes[0] and codes[1] (one mismatch from each: an ambiguous hit), and every read length up to the barcode's own
+    and the table's depth."""
+    p7 = "AGATCGGAAGAGCACACGTC"
+    midpoint = codes[0][:1] + codes[1][1] + codes[0][2:]
+    reads = []
+    for i in range(n):
+        kind = i % 9
+        code = codes[rng.randrange(len(codes))]
+        if kind == 1:
+            code = util.mutate(rng, code, 1)
+        elif kind == 2:
+            at = rng.randrange(length)
+            code = code[:at] + "N" + code[at + 1:]
+        elif kind == 3:
+            code = util.random_dna(rng, length)
+        elif kind == 4:
+            code = midpoint
+        body = util.random_dna(rng, rng.randrange(0, 41 - 12 - len(code)))
+        if at_end:
+            seq = body + code + p7[:rng.choice((0, 0, 5, 12))]
+        else:
+            seq = code + body + p7[:rng.choice((0, 0, 5, 12))]
+        if kind == 5:
+            seq = seq.lower()
+        elif kind == 6:  # shorter than the barcode, shorter than the table's m + k bases
+            cut = (i // 9) % (length + 3)
+            seq = seq[len(seq) - cut:] if at_end else seq[:cut]
+        assert len(seq) <= 40
+        reads.append((seq, "".join(rng.choice("#+5?I") for _ in seq)))
+    return reads
+
+
+@pytest.mark.parametrize("length", [6, 8])
+@pytest.mark.parametrize("form", ["table", "ops5", "ops3"])
+def test_long_read_walk_demultiplexes_like_the_rows(form, length):
+    """Row stride 4 takes every read longer than 4 nt out of the rows: the long-read kernel walks the chain, its two
+    demultiplexing branches included -- the table over the first m + k bases (``table``) and the candidates' own ops
+    (cs_plan_set_demux_ops) with the barcodes at the 5' end (``ops5``) and at the 3' end (``ops3``, SuffixAdapter ops,
+    the table walked backwards).  Same text at the reads' natural stride (the tile kernels, which the tests above hold
+    to independent runs and the oracle): same routes -- one per barcode --, same counts, same bytes (the interval and
+    the flags that route a record), same statistics.  (CS_F_AMBIGUOUS itself routes nothing; which of its claimants
+    an ambiguous read goes to does.)"""
+    from cutseq_amd import textpath
+    from test_gpu_parity import stats_dict
+
+    count, at_end = 12, form == "ops3"
+    rng = random.Random(length * 10 + len(form))
+    codes = barcode_set(rng, count - 1, length, 3)
+    while True:  # codes[1]: two substitutions away from codes[0], so that the read between them is claimed by both
+        near = list(codes[0])
+        near[1] = rng.choice("ACGT".replace(near[1], ""))
+        near[4] = rng.choice("ACGT".replace(near[4], ""))
+        if "".join(near) not in codes:
+            break
+    codes.insert(1, "".join(near))
+    scheme = (f"ACACGACGCTCTTCCGATCTNNNN>({codes[0]})AGATCGGAAGAGCACACGTC" if at_end else
+              f"ACACGACGCTCTTCCGATCT({codes[0]})NNNN>AGATCGGAAGAGCACACGTC")
+    st = planmod.CutadaptConfig()
+    st.ensure_inline_barcode = True
+    st.min_length = 5  # (reads of 40 nt at most: some of every barcode's reads stay long enough for its route)
+    st.demux_barcodes = codes
+    tp = planmod.compile_single(BarcodeConfig(scheme), st)
+    tp.demux.by_ops = form != "table"
+    assert tp.demux.tabulated == (form == "table") and tp.demux.at_end == at_end
+    reads = short_barcoded_reads(rng, codes, length, at_end)
+    n = len(reads)
+    lens = np.array([len(s) for s, _ in reads])
+    text1 = b"".join(b"@LR:%d 1:N:0:X\n%s\n+\n%s\n" % (i, s.encode(), q.encode()) for i, (s, q) in enumerate(reads))
+
+    # what the case holds, from the tile kernels' per-read results
+    batch = util.batch_from_reads(reads)
+    bc = np.empty(n, dtype=np.uint8)
+    with TrimEngine(tp, device=0, slots=1, max_reads=n, max_stride=batch.stride) as eng:
+        g1, _, _ = eng.submit(0, batch.seq1, batch.qual1, batch.len1, bc=bc)
+        eng.wait(0)
+    assert ((g1["flags"] & abi.CS_F_AMBIGUOUS) != 0).any() and len(set(bc.tolist())) == count + 1
+    assert set(range(length + 2)) <= set(lens.tolist()) and lens.max() <= 40
+
+    def run(stride):
+        with TrimEngine(tp, device=0, slots=0) as eng:
+            with textpath.TextEngine(eng, slots=1, max_text_bytes=len(text1) + 1024, max_records=n, stride=stride, bins=count) as te:
+                te.submit(0, text1, len(text1), None, 0, n)
+                res = te.wait(0)
+                got, _, counts = te.routes(0)
+                out = np.empty(max(int(res.out_bytes[0]), 1), dtype=np.uint8)
+                te.fetch(0, out)
+            return textpath.split_routes(got, [out], False), counts.tolist(), int(res.n_long[0]), stats_dict(eng.stats()[0])
+
+    want_streams, want_counts, rows_long, want_stats = run(batch.stride)
+    got_streams, got_counts, n_long, got_stats = run(4)
+    assert rows_long == 0 and n_long == int((lens > 4).sum())
+    assert sum(want_counts) == n and sum(want_counts[3:]) > n // 8 and want_counts[2] > 0
+    assert got_counts == want_counts
+    for route in range(3 + count):
+        assert got_streams[route][0] == want_streams[route][0], route
+    assert got_stats == want_stats
+
+
 def test_demux_table_matches_the_oracle_on_every_prefix():
     """The device-built table against the CPU oracle's PrefixAdapter on all 5^0 + ... + 5^(m+k) prefixes."""
     rng = random.Random(3)
