@@ -189,3 +189,12 @@ RESULT_DTYPE = _np.dtype(
 )
 CAP2_DTYPE = _np.dtype([("off", "<u2"), ("len", "u1"), ("_pad", "u1")])
 assert RESULT_DTYPE.itemsize == 8 and CAP2_DTYPE.itemsize == 4
+
+
+class ReadTooLong(ValueError):
+    """A read beyond what the device takes (CS_MAX_READ on the text path: its positions are 32-bit, its long-read
+    kernel serial per read; CS_MAX_STRIDE on the record path).  A user error: the CLI reports it without a traceback."""
+
+    def __init__(self, message: str, longest: int = 0):
+        super().__init__(message)
+        self.longest = longest

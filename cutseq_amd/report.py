@@ -12,6 +12,9 @@ describe the FIRST AdapterCutter of each mate's chain.
 from __future__ import annotations
 
 import json
+import os
+import sys
+import time
 from typing import Optional
 
 import numpy as np
@@ -276,3 +279,19 @@ class Progress:
             return
         with self._lock:
             print(("\r" if self.live else "") + self._line("Done", self._time.time()), file=self.stream, flush=True)
+
+
+def phase(tag: str) -> None:
+    """Diagnostic (CUTSEQ_PROFILE=1): seconds since the interpreter started, per phase of the run."""
+    if os.environ.get("CUTSEQ_PROFILE") == "1":
+        print(f'{{"cutseq_phase": "{tag}", "process_seconds": {time.perf_counter() - _T_IMPORT + _IMPORT_OFFSET:.3f}}}', file=sys.stderr)
+
+
+_T_IMPORT = time.perf_counter()
+try:  # seconds between process start and this module's import (Linux: from /proc)
+    with open("/proc/self/stat") as _fh:
+        _start_ticks = int(_fh.read().rsplit(")", 1)[1].split()[19])
+    with open("/proc/uptime") as _fh:
+        _IMPORT_OFFSET = float(_fh.read().split()[0]) - _start_ticks / os.sysconf("SC_CLK_TCK")
+except Exception:  # pragma: no cover
+    _IMPORT_OFFSET = 0.0

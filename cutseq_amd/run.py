@@ -14,17 +14,17 @@ from __future__ import annotations
 import argparse
 import logging
 import os
-import queue
 import re
 import sys
-import threading
 import time
 from collections import deque
 from typing import List, Optional
 
-from . import __version__, abi, report, shard
+from . import __version__, abi, fanout, report
+from .abi import ReadTooLong
 from .common import BUILDIN_ADAPTERS, BarcodeConfig, print_builtin_adapters, remove_fq_suffix
 from .plan import CutadaptConfig, TrimPlan, compile_paired, compile_single
+from .report import phase as _phase
 
 logging.basicConfig(level=logging.INFO, format="%(asctime)s -  %(levelname)s - %(message)s")
 
@@ -247,97 +247,68 @@ def dry_run(tp: TrimPlan, barcode: BarcodeConfig):
             print(f"Step {i}: {step}")
 
 
-class _DeviceWorker(threading.Thread):
+class _DeviceWorker(fanout.Worker):
     """One GPU: owns the device's TrimEngine, keeps ``SLOTS`` chunks in flight on it (the H2D copy of one
     overlaps the kernels and the D2H copy of the other) and reports every finished chunk to ``done``.
     Counterpart of one worker process of ``make_runner(inpaths, cores=N)`` (cutseq/run.py:436, 753)."""
 
     SLOTS = 2
 
-    def __init__(self, tp: TrimPlan, device: int, done: "queue.Queue", chunk_reads: int):
-        super().__init__(daemon=True, name=f"cutseq-gpu{device}")
-        self.tp, self.device, self.done, self.chunk_reads = tp, device, done, chunk_reads
-        self.inbox: "queue.Queue" = queue.Queue(maxsize=self.SLOTS)
-        self.engine = None
+    def __init__(self, tp: TrimPlan, device: int, chunk_reads: int):
+        super().__init__(f"cutseq-gpu{device}")
+        self.tp, self.device, self.chunk_reads = tp, device, chunk_reads
         self.stride_cap = 0
-        self.stats = None  # summed cs_stats of every engine this device has had
-        self.error: Optional[BaseException] = None
 
-    def _collect_stats(self):
-        part = [s.as_dict() for s in self.engine.stats()]
-        self.stats = part if self.stats is None else [shard.merge_stats([a, b]) for a, b in zip(self.stats, part)]
-
-    def _engine_for(self, stride: int, inflight: deque):
+    def ensure(self, chunk):
         """The engine, rebuilt with longer rows when a chunk needs them -- after everything the old one still
         has in flight came back and its counters were saved."""
-        if self.engine is not None and stride <= self.stride_cap:
+        if self.engine is not None and chunk.stride <= self.stride_cap:
             return
         from .engine import TrimEngine
-        while inflight:
-            self._finish_oldest(inflight)
+        self.drain()
         if self.engine is not None:
             self._collect_stats()
             self.engine.close()
-        self.stride_cap = max(stride, 152)
+        self.stride_cap = max(chunk.stride, 152)
         self.engine = TrimEngine(self.tp, device=self.device, slots=self.SLOTS, max_reads=self.chunk_reads,
                                  max_stride=self.stride_cap)
 
-    def _finish_oldest(self, inflight: deque):
-        k, slot, chunk, res = inflight.popleft()
-        self.engine.wait(slot)
-        self.done.put((k, chunk, res))
-
-    def run(self):
+    def submit(self, slot: int, chunk):
         from . import fastq
-        inflight: deque = deque()  # (chunk index, slot, chunk, result arrays), oldest first
-        n = 0
-        try:
-            while True:
-                item = self.inbox.get()
-                if item is None:
-                    break
-                k, chunk = item
-                self._engine_for(chunk.stride, inflight)
-                if len(inflight) == self.SLOTS:
-                    self._finish_oldest(inflight)  # frees exactly the slot this chunk takes
-                paired = chunk.paired
-                # result arrays in pinned memory, like the inputs: the D2H copy is a DMA transfer too
-                owned = [fastq.PINNED.take(chunk.n * 8)]
-                out1 = owned[0][: chunk.n * 8].view(abi.RESULT_DTYPE)
-                cap2 = out2 = None
-                if self.tp.needs_cap2:
-                    owned.append(fastq.PINNED.take(chunk.n * 4))
-                    cap2 = owned[-1][: chunk.n * 4].view(abi.CAP2_DTYPE)
-                if paired:
-                    owned.append(fastq.PINNED.take(chunk.n * 8))
-                    out2 = owned[-1][: chunk.n * 8].view(abi.RESULT_DTYPE)
-                if self.tp.demux is not None:
-                    owned.append(fastq.PINNED.take(chunk.n))
-                    chunk.bc = owned[-1][: chunk.n]
-                if self.tp.max_n is not None:  # TooManyN flags of both mates
-                    owned.append(fastq.PINNED.take(chunk.n))
-                    xf1 = owned[-1][: chunk.n]
-                    xf2 = None
-                    if paired:
-                        owned.append(fastq.PINNED.take(chunk.n))
-                        xf2 = owned[-1][: chunk.n]
-                    chunk.xflags = (xf1, xf2)
-                chunk._owned = chunk._owned + tuple((fastq.PINNED, b) for b in owned)
-                slot = n % self.SLOTS
-                res = self.engine.submit(slot, chunk.seq1, chunk.qual1, chunk.len1, chunk.seq2, chunk.qual2,
-                                         chunk.len2, out=(out1, cap2, out2), bc=chunk.bc, xflags=chunk.xflags)
-                inflight.append((k, slot, chunk, res))
-                n += 1
-            while inflight:
-                self._finish_oldest(inflight)
-            if self.engine is not None:
-                self._collect_stats()
-        except BaseException as exc:
-            self.error = exc
-        finally:
-            if self.engine is not None:
-                self.engine.close()
-            self.done.put(self)  # "this device is finished" (or failed)
+        paired = chunk.paired
+        # result arrays in pinned memory, like the inputs: the D2H copy is a DMA transfer too
+        owned = [fastq.PINNED.take(chunk.n * 8)]
+        out1 = owned[0][: chunk.n * 8].view(abi.RESULT_DTYPE)
+        cap2 = out2 = None
+        if self.tp.needs_cap2:
+            owned.append(fastq.PINNED.take(chunk.n * 4))
+            cap2 = owned[-1][: chunk.n * 4].view(abi.CAP2_DTYPE)
+        if paired:
+            owned.append(fastq.PINNED.take(chunk.n * 8))
+            out2 = owned[-1][: chunk.n * 8].view(abi.RESULT_DTYPE)
+        if self.tp.demux is not None:
+            owned.append(fastq.PINNED.take(chunk.n))
+            chunk.bc = owned[-1][: chunk.n]
+        if self.tp.max_n is not None:  # TooManyN flags of both mates
+            owned.append(fastq.PINNED.take(chunk.n))
+            xf1 = owned[-1][: chunk.n]
+            xf2 = None
+            if paired:
+                owned.append(fastq.PINNED.take(chunk.n))
+                xf2 = owned[-1][: chunk.n]
+            chunk.xflags = (xf1, xf2)
+        chunk._owned = chunk._owned + tuple((fastq.PINNED, b) for b in owned)
+        res = self.engine.submit(slot, chunk.seq1, chunk.qual1, chunk.len1, chunk.seq2, chunk.qual2,
+                                 chunk.len2, out=(out1, cap2, out2), bc=chunk.bc, xflags=chunk.xflags)
+        return chunk, res
+
+    def finish(self, slot: int, handle):
+        self.engine.wait(slot)
+        return handle  # (chunk, result arrays)
+
+    def close(self):
+        if self.engine is not None:
+            self.engine.close()
 
 
 def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
@@ -345,7 +316,7 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
 
     Counterpart of ``runner.run(pipeline, Progress(), outfiles)`` (cutseq/run.py:473, 794): chunks of
     ``fastq.CHUNK_READS`` records go round-robin to one worker thread per GPU, come back in any order and are
-    formatted / compressed / written strictly in input order."""
+    formatted / compressed / written strictly in input order (``fanout.run_ordered``)."""
     from . import capi, fastq
 
     n_dev = capi.device_count()
@@ -364,10 +335,11 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
     if any(d < 0 or d >= n_dev for d in devices):
         _fail(f"GPU {max(devices)} does not exist: this process sees {n_dev} (--ranks N puts rank r on GPU r; "
               "CUTSEQ_DEVICES=0,0,... lists the GPUs to use, one entry per rank or worker, repeats allowed).")
-    # Text path (default): the device parses the records and formats the output (textio.py / cs_text_*); the host
-    # path below (native parser / formatter in a thread pool) stays for demultiplexing runs and as CUTSEQ_TEXT_PATH=0.
+    # Text path (default): the device parses the records and formats the output (textio.py / cs_text_*), demultiplexing
+    # runs included.  The record path below is the second host implementation (native parser / formatter of
+    # cutseq_host.c in a thread pool), selected by CUTSEQ_TEXT_PATH=0 and held to the same outputs by the tests.
+    from . import textio
     if os.environ.get("CUTSEQ_TEXT_PATH", "1") != "0":
-        from . import textio
         return textio.run_text_pipeline(args, tp, devices, _block_records(args, len(devices)),
                                         shares=shares)
     if shares is not None:
@@ -379,22 +351,10 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
             _fail(f"{name}: FASTA input, standard input and bzip2 / xz / zstandard files need the text path (CUTSEQ_TEXT_PATH unset).")
     chunk_reads = int(os.environ.get("CUTSEQ_CHUNK_READS", fastq.CHUNK_READS))
     paired = tp.paired
-    in1 = args.input_file[0]
-    in2 = args.input_file[1] if paired else None
-
-    # output files: trimmed / short / untrimmed, per mate; paired --auto-rc on a '-' library swaps
-    # the trimmed pair (run.py:787-791)
-    def mk(names):
-        return [fastq.OutputFile(n) if n else None for n in names]
-
     n_bins = len(tp.demux.barcodes) if tp.demux is not None else 0
-    trimmed = mk(args.output_file) if not n_bins else [None] * len(args.output_file)
-    if paired and tp.swap_outputs:
-        trimmed = trimmed[::-1]
-    outs = [trimmed, mk(args.short_file), mk(args.untrimmed_file)]
-    for names in (args.demux_files if n_bins else ()):  # streams 3 .. : the trimmed reads of one barcode each
-        files = mk(names)
-        outs.append(files[::-1] if paired and tp.swap_outputs else files)
+    # the open file (or None) per [stream][mate]
+    outs = [[fastq.OutputFile(n) if n else None for n in names]
+            for names in textio.output_name_groups(args, paired, tp.swap_outputs, n_bins)]
     # which (route, mate) streams go to disk, and whether they are gzip
     gz = [[(fh.gz if fh is not None else None) for fh in (group + [None])[:2]] for group in outs]
 
@@ -403,12 +363,21 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
     t0 = time.perf_counter()
     pool = fastq._pool()
     max_finishing = fastq.pool_size() + 2  # chunks being formatted / compressed (about 90 MB each)
-    done: "queue.Queue" = queue.Queue()
+    finishing: deque = deque()
     if tp.demux is not None:
         from . import demux  # look-up tables once, here: every device worker would otherwise build its own
         demux.ensure_tables(tp, devices[0])
-    workers = [_DeviceWorker(tp, dev, done, chunk_reads) for dev in devices]
-    failure: List[BaseException] = []
+    workers = [_DeviceWorker(tp, dev, chunk_reads) for dev in devices]
+
+    def chunks():
+        for k, chunk in enumerate(fastq.read_chunks(args.input_file[0], args.input_file[1] if paired else None,
+                                                    chunk_reads, pinned=True)):
+            if chunk.stride > abi.CS_MAX_STRIDE:
+                record = k * chunk_reads + int(chunk.len1.argmax()) + 1
+                chunk.release()
+                raise ReadTooLong(f"reads longer than {abi.CS_MAX_STRIDE} nt are not supported by the GPU tile "
+                                  f"(record {record} or its mate)")
+            yield chunk
 
     def finish(chunk, r1, cap2, r2):
         """Pool job: records -> bytes on their way to disk; also this chunk's share of the report."""
@@ -422,85 +391,31 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
         finally:
             chunk.release()
 
-    def collect():
-        """Re-establishes the input order behind the GPUs and feeds the writers."""
-        waiting, next_k, alive = {}, 0, len(workers)
-        finishing: deque = deque()
-        try:
-            while alive or waiting:
-                item = done.get()
-                if isinstance(item, _DeviceWorker):
-                    alive -= 1
-                    if item.error is not None:
-                        raise item.error
-                    continue
-                waiting[item[0]] = item
-                while next_k in waiting:
-                    _, chunk, (r1, cap2, r2) = waiting.pop(next_k)
-                    next_k += 1
-                    progress.update(chunk.n)
-                    fut = pool.submit(finish, chunk, r1, cap2, r2)
-                    for route in range(len(outs)):
-                        for m in range(2 if paired else 1):
-                            if outs[route][m] is not None:
-                                outs[route][m].write_job(fut, route, m)
-                    finishing.append(fut)
-                    while finishing and (len(finishing) >= max_finishing or finishing[0].done()):
-                        report.merge_totals(totals, finishing.popleft().result()[1])
-                if not alive and waiting and next_k not in waiting:
-                    raise RuntimeError("a chunk went missing between the GPU workers and the writer")
-            while finishing:
-                report.merge_totals(totals, finishing.popleft().result()[1])
-        except BaseException as exc:
-            failure.append(exc)
+    def emit(item):
+        chunk, (r1, cap2, r2) = item
+        progress.update(chunk.n)
+        fut = pool.submit(finish, chunk, r1, cap2, r2)
+        for route in range(len(outs)):
+            for m in range(2 if paired else 1):
+                if outs[route][m] is not None:
+                    outs[route][m].write_job(fut, route, m)
+        finishing.append(fut)
+        while finishing and (len(finishing) >= max_finishing or finishing[0].done()):
+            report.merge_totals(totals, finishing.popleft().result()[1])
 
-    collector = threading.Thread(target=collect, daemon=True, name="cutseq-collect")
-    for w in workers:
-        w.start()
-    collector.start()
-    first_error: Optional[BaseException] = None
-    try:
-        for k, chunk in enumerate(fastq.read_chunks(in1, in2, chunk_reads, pinned=True)):
-            if failure:
-                break
-            if chunk.stride > abi.CS_MAX_STRIDE:
-                raise ReadTooLong(f"reads longer than {abi.CS_MAX_STRIDE} nt are not supported by the GPU tile "
-                                  f"(record {k * chunk_reads + int(chunk.len1.argmax()) + 1} or its mate)")
-            w = workers[k % len(workers)]
-            while not failure:
-                try:
-                    w.inbox.put((k, chunk), timeout=0.2)
-                    break
-                except queue.Full:
-                    continue
-    except BaseException as exc:
-        first_error = exc
-    finally:
-        for w in workers:
-            while True:  # the sentinel must get in even when the worker died with a full inbox
-                try:
-                    w.inbox.put(None, timeout=0.2)
-                    break
-                except queue.Full:
-                    if not w.is_alive():
-                        break
-        for w in workers:
-            w.join()
-        collector.join()
-        for group in outs:
-            for fh in group:
-                if fh is None:
-                    continue
-                try:
-                    fh.close()
-                except BaseException as exc:  # keep closing the others; report the first failure
-                    first_error = first_error or exc
-    if first_error is None and failure:
-        first_error = failure[0]
-    if first_error is None:
-        first_error = next((w.error for w in workers if w.error is not None), None)
-    if first_error is not None:
-        raise first_error  # (the pinned arena is left alone: parse / format jobs of the pool may still hold its buffers)
+    def merge_rest():
+        first = None
+        while finishing:  # every job is awaited: none may outlive the files it writes to
+            try:
+                report.merge_totals(totals, finishing.popleft().result()[1])
+            except BaseException as exc:
+                first = first or exc
+        if first is not None:
+            raise first
+
+    fanout.run_ordered(workers, chunks(), emit, orphan=lambda item: item[0].release(), discard=lambda chunk: chunk.release(),
+                       closers=[merge_rest] + [fh.close for group in outs for fh in group if fh is not None])
+    # (after an error the pinned arena is left alone: parse / format jobs of the pool may still hold its buffers)
     fastq.PINNED.free_pinned()  # every chunk has been written and released
     stats = [w.stats for w in workers if w.stats is not None]
     totals["seconds"] = time.perf_counter() - t0
@@ -509,10 +424,6 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
     totals["stats"] = stats
     totals["devices"] = devices
     return totals
-
-
-class ReadTooLong(ValueError):
-    pass
 
 
 def run_cutseq(args, argv=None):
@@ -592,22 +503,6 @@ def _block_records(args, n_devices: int) -> int:
     while block > 16384 and block > want:
         block //= 2
     return block
-
-
-def _phase(tag: str) -> None:
-    """Diagnostic (CUTSEQ_PROFILE=1): seconds since the interpreter started, per phase of the run."""
-    if os.environ.get("CUTSEQ_PROFILE") == "1":
-        print(f'{{"cutseq_phase": "{tag}", "process_seconds": {time.perf_counter() - _T_IMPORT + _IMPORT_OFFSET:.3f}}}', file=sys.stderr)
-
-
-_T_IMPORT = time.perf_counter()
-try:  # seconds between process start and this module's import (Linux: from /proc)
-    with open("/proc/self/stat") as _fh:
-        _start_ticks = int(_fh.read().rsplit(")", 1)[1].split()[19])
-    with open("/proc/uptime") as _fh:
-        _IMPORT_OFFSET = float(_fh.read().split()[0]) - _start_ticks / os.sysconf("SC_CLK_TCK")
-except Exception:  # pragma: no cover
-    _IMPORT_OFFSET = 0.0
 
 
 def main(argv: Optional[List[str]] = None):

@@ -8,10 +8,15 @@ order.  Counterpart of ``runner.run(pipeline, Progress(), outfiles)`` with ``mak
 
   TextReader    one thread per input file: page cache (several ``pread`` calls at once) or inflate pool -> pinned
                 block buffer -> ``TextBlock(buf, nbytes, n_records)``
-  TextWorker    one thread per GPU: a ``TrimEngine`` + ``TextEngine``, three batches in flight; grows the row stride
-                or the text capacity when a batch needs it
-  run_text_pipeline   pairs the mates' blocks, deals them round-robin, re-orders the results and feeds one
-                ``StreamWriter`` per output file (plain: parallel ``pwrite``; ``.gz``: 4 MB gzip members from the pool)
+  TextWorker    one thread per GPU (a ``fanout.Worker``): a ``TrimEngine`` + ``TextEngine``, three batches in flight;
+                grows the row stride or the text capacity when a batch needs it
+  run_text_pipeline   pairs the mates' blocks and hands them to ``fanout.run_ordered`` (round-robin deal, results back
+                in input order), which feeds one ``StreamWriter`` per output file (plain: parallel ``pwrite``;
+                ``.gz``: 4 MB gzip members from the pool)
+
+Every run takes this path by default, demultiplexing runs included (``--demux-barcodes``: routes 3 + b).  The record
+path (``run.run_pipeline`` with the native parser / formatter of ``cutseq_host.c``) is a second host implementation
+behind ``CUTSEQ_TEXT_PATH=0``, held to the same outputs by the tests' switch matrix.
 """
 from __future__ import annotations
 
@@ -21,12 +26,12 @@ import os
 import queue
 import threading
 import time
-from collections import deque
 from typing import List, Optional
 
 import numpy as np
 
-from . import abi, codec, fastq, report, shard, textpath
+from . import abi, codec, fanout, fastq, report, textpath
+from .abi import ReadTooLong
 
 CHUNK_READS = 1 << 18
 _BLOCK = 8 << 20          # bytes per pread / per inflate hand-over
@@ -578,77 +583,72 @@ class StreamWriter:
 
 
 class _Done:
-    __slots__ = ("k", "n", "res", "out", "sizes", "counts", "info", "info_bytes")
+    __slots__ = ("n", "res", "out", "sizes", "counts", "info", "info_bytes")
 
-    def __init__(self, k, n, res, out, sizes=None, counts=None, info=None, info_bytes=0):
-        self.k, self.n, self.res, self.out, self.sizes, self.counts = k, n, res, out, sizes, counts
+    def __init__(self, n, res, out, sizes=None, counts=None, info=None, info_bytes=0):
+        self.n, self.res, self.out, self.sizes, self.counts = n, res, out, sizes, counts
         self.info, self.info_bytes = info, info_bytes  # --info-file: the batch's table (a pinned buffer) and its size
 
 
-class TextWorker(threading.Thread):
-    """One GPU.  Counterpart of one worker process of ``make_runner(inpaths, cores=N)`` (cutseq/run.py:436, 753)."""
+class TextWorker(fanout.Worker):
+    """One GPU.  Counterpart of one worker process of ``make_runner(inpaths, cores=N)`` (cutseq/run.py:436, 753).
+    An item is the pair of the mates' blocks ``(b1, b2 | None)``, a finished one a :class:`_Done`."""
 
     SLOTS = 3
+    _tick = staticmethod(_tick)
 
-    def __init__(self, tp, device: int, done: "queue.Queue", chunk_reads: int, compress: bool = False, bins: int = 0,
+    def __init__(self, tp, device: int, chunk_reads: int, compress: bool = False, bins: int = 0,
                  fasta_routes: int = 0, info: int = 0):
-        super().__init__(daemon=True, name=f"cutseq-gpu{device}")
+        super().__init__(f"cutseq-gpu{device}")
         self.info = info  # abi.CS_INFO_* bits: the batches also yield the --info-file table
-        self.tp, self.device, self.done, self.chunk_reads, self.compress = tp, device, done, chunk_reads, compress
+        self.tp, self.device, self.chunk_reads, self.compress = tp, device, chunk_reads, compress
         self.fasta_routes = fasta_routes  # bit 2 * class + mate: that stream's records leave as FASTA
         self.bins = bins  # demultiplexing: one route per barcode behind the three ordinary ones
-        self.inbox: "queue.Queue" = queue.Queue(maxsize=self.SLOTS)
-        self.engine = self.text = None
+        self.text = None
         self.stride, self.capacity, self.want_stride = 152, 0, 152
-        self.stats = None
-        self.error: Optional[BaseException] = None
-        self.submitted = 0
 
-    def _collect_stats(self):
-        part = [s.as_dict() for s in self.engine.stats()]
-        self.stats = part if self.stats is None else [shard.merge_stats([a, b]) for a, b in zip(self.stats, part)]
+    def begin(self):
+        # the trimming engine right away (plan upload, code object load: 0.1-0.2 s), while the readers are still
+        # getting their first blocks; the text engine follows when the first block says how big it has to be
+        from .engine import TrimEngine
+        self.engine = TrimEngine(self.tp, device=self.device, slots=0)
 
-    def _ensure(self, inflight: deque, text_bytes: int, stride: Optional[int] = None):
+    def ensure(self, item):
         """The text engine, rebuilt for longer rows or bigger blocks -- after everything in flight came back."""
-        stride = max(stride or self.stride, self.want_stride)
+        b1, b2 = item
+        text_bytes = max(b1.nbytes, b2.nbytes if b2 is not None else 0)
+        stride = max(self.stride, self.want_stride)
         if self.text is not None and stride <= self.stride and text_bytes <= self.capacity:
             return
-        from .engine import TrimEngine
-        while inflight:
-            self._finish(inflight)
+        self.drain()
         if self.text is not None:
             self.text.close()
-        if self.engine is None:
-            self.engine = TrimEngine(self.tp, device=self.device, slots=0)
-        self.stride = max(self.stride, stride)
+        self.stride = stride
         self.capacity = max(self.capacity, int(text_bytes * 1.25) + (1 << 20))
         self.text = textpath.TextEngine(self.engine, slots=self.SLOTS, max_text_bytes=self.capacity,
                                         max_records=self.chunk_reads, stride=self.stride, compress=self.compress,
                                         bins=self.bins, fasta_routes=self.fasta_routes, info=self.info)
-        self.submitted = 0
 
-    def _submit(self, inflight: deque, k: int, b1: TextBlock, b2: Optional[TextBlock]):
-        slot = self.submitted % self.SLOTS
-        self.submitted += 1
+    def submit(self, slot: int, item):
+        b1, b2 = item
         if os.environ.get("CUTSEQ_DEBUG_BLOCKS") == "1":  # diagnostic: what goes to the device
             import sys
             L = _host()
-            print(f"block {k}: slot {slot} records {b1.n}/{b2.n if b2 is not None else '-'} bytes {b1.nbytes}/"
+            print(f"block at record {b1.first_record}: slot {slot} records {b1.n}/{b2.n if b2 is not None else '-'} bytes {b1.nbytes}/"
                   f"{b2.nbytes if b2 is not None else '-'} newlines {L.csh_count_newlines(b1.buf.ctypes.data, b1.nbytes)}/"
                   f"{L.csh_count_newlines(b2.buf.ctypes.data, b2.nbytes) if b2 is not None else '-'} capacity {self.capacity}",
                   file=sys.stderr, flush=True)
         self.text.submit(slot, b1.buf, b1.nbytes, b2.buf if b2 is not None else None, b2.nbytes if b2 is not None else 0, b1.n)
-        inflight.append((k, slot, b1, b2))
+        return item
 
-    def _finish(self, inflight: deque):
-        k, slot, b1, b2 = inflight.popleft()
+    def finish(self, slot: int, item) -> _Done:
+        b1, b2 = item
         t0 = time.perf_counter()
         try:
             res = self.text.wait(slot, first_record=b1.first_record)
             t0 = _tick("wait", t0)
-        except textpath.ReadTooLong as exc:
-            from .run import ReadTooLong
-            raise ReadTooLong(f"{exc} in records {b1.first_record + 1}..{b1.first_record + b1.n}")
+        except ReadTooLong as exc:
+            raise ReadTooLong(f"{exc} in records {b1.first_record + 1}..{b1.first_record + b1.n}", exc.longest)
         except textpath.TextFormatError as exc:
             if exc.code == abi.CS_TEXT_ERR_IDS_DIFFER:
                 raise ValueError(str(exc))
@@ -672,45 +672,15 @@ class TextWorker(threading.Thread):
         b1.release()
         if b2 is not None:
             b2.release()
-        self.done.put(_Done(k, b1.n, res, out, sizes, counts, info_buf, info_bytes))
+        return _Done(b1.n, res, out, sizes, counts, info_buf, info_bytes)
 
-    def run(self):
-        inflight: deque = deque()
+    def close(self):
         try:
-            # the trimming engine right away (plan upload, code object load: 0.1-0.2 s), while the readers are still
-            # getting their first blocks; the text engine follows when the first block says how big it has to be
-            t0 = time.perf_counter()
-            from .engine import TrimEngine
-            self.engine = TrimEngine(self.tp, device=self.device, slots=0)
-            _tick("ensure", t0)
-            while True:
-                t0 = time.perf_counter()
-                item = self.inbox.get()
-                t0 = _tick("idle", t0)
-                if item is None:
-                    break
-                k, b1, b2 = item
-                self._ensure(inflight, max(b1.nbytes, b2.nbytes if b2 is not None else 0))
-                t0 = _tick("ensure", t0)
-                if len(inflight) == self.SLOTS:
-                    self._finish(inflight)
-                t0 = time.perf_counter()
-                self._submit(inflight, k, b1, b2)
-                _tick("submit", t0)
-            while inflight:
-                self._finish(inflight)
-            if self.engine is not None:
-                self._collect_stats()
-        except BaseException as exc:
-            self.error = exc
+            if self.text is not None:
+                self.text.close()
         finally:
-            try:
-                if self.text is not None:
-                    self.text.close()
-                if self.engine is not None:
-                    self.engine.close()
-            finally:
-                self.done.put(self)
+            if self.engine is not None:
+                self.engine.close()
 
 
 _FASTA_EXT = (".fasta", ".fa", ".fna", ".csfasta", ".csfa")
@@ -784,53 +754,51 @@ def output_formats(groups, has_qualities: bool) -> int:
     return mask
 
 
+def output_name_groups(args, paired: bool, swap_outputs: bool, n_bins: int) -> List[list]:
+    """The output files' names by the stream they receive -- [trimmed, too short, untrimmed, barcode 0, barcode 1, ...],
+    one entry per mate each (None: no such file).  Paired --auto-rc on a '-' library swaps the mates' trimmed files
+    (cutseq/run.py:787-791), the barcodes' too; a demultiplexing run has no common trimmed file, and one handed over
+    without files for its barcodes gets one nameless group for their streams (dropped, and of class 3 all the same)."""
+    mates = 2 if paired else 1
+    groups = [list(args.output_file) if not n_bins else [], list(args.short_file or []), list(args.untrimmed_file or [])]
+    if n_bins:
+        groups += [list(names) for names in (getattr(args, "demux_files", None) or [[]])]
+    groups = [(g + [None, None])[:mates] for g in groups]
+    if paired and swap_outputs:
+        groups = [g if q in (1, 2) else g[::-1] for q, g in enumerate(groups)]
+    return groups
+
+
 def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
     """The CLI's run on the text path -> the run statistics ``report`` expects.  ``shares``: per input file the part
     of it this process takes (``ranks.py``)."""
     global _DISCARD
     _DISCARD = os.environ.get("CUTSEQ_DISCARD_OUTPUT") == "1"  # diagnostic: the writers drop their bytes
     paired = tp.paired
-    in1 = args.input_file[0]
-    in2 = args.input_file[1] if paired else None
     share = shares or [{}, {}]
-    r1 = TextReader(in1, chunk_reads, **share[0])  # (a missing input file raises here, before anything else exists)
+    r1 = TextReader(args.input_file[0], chunk_reads, **share[0])  # (a missing input file raises here, before anything else exists)
     r2 = None
     opened: List[StreamWriter] = []
     try:
-        r2 = TextReader(in2, chunk_reads, **share[1]) if paired else None
-        if PROFILE:
-            from .run import _phase
-            _phase("readers started")
+        r2 = TextReader(args.input_file[1], chunk_reads, **share[1]) if paired else None
+        report.phase("readers started")
 
-        # every output a ".gz" file: the device compresses (deflate_kernels.hip.inc) and the writers pass the members
-        # through; otherwise text comes back and ".gz" outputs are deflated in the host pool (CUTSEQ_GPU_DEFLATE=0 too)
         # demultiplexing (table form): the trimmed pairs of barcode b are route 3 + b, one pair of files each
         n_bins = len(tp.demux.barcodes) if tp.demux is not None else 0
-        bin_files = list(getattr(args, "demux_files", None) or []) if n_bins else []
-        names_all = [n for group in [args.output_file if not n_bins else [], args.short_file, args.untrimmed_file] + bin_files
-                     for n in group if n]
+        name_groups = output_name_groups(args, paired, tp.swap_outputs, n_bins)
+        # every output a ".gz" file: the device compresses (deflate_kernels.hip.inc) and the writers pass the members
+        # through; otherwise text comes back and ".gz" outputs are deflated in the host pool (CUTSEQ_GPU_DEFLATE=0 too)
+        names_all = [n for group in name_groups for n in group if n]
         compress = bool(names_all) and all(n != "-" and codec.container_of_name(n) == "gzip" for n in names_all) and os.environ.get("CUTSEQ_GPU_DEFLATE", "1") != "0"
         if r2 is not None and r1.fasta != r2.fasta:
             raise fastq.FastqFormatError("the two input files are in different formats (one FASTA, one FASTQ)")
-        # the files by the stream they receive: paired --auto-rc on a '-' library swaps the mates' trimmed files
-        swap = paired and tp.swap_outputs
-        trimmed_names = list(args.output_file) if not n_bins else [None] * len(args.output_file)
-        name_groups = [trimmed_names[::-1] if swap else trimmed_names, list(args.short_file or []),
-                       list(args.untrimmed_file or [])] + [list(names)[::-1] if swap else list(names) for names in bin_files]
-        name_groups = [(g + [None, None])[:2 if paired else 1] for g in name_groups]  # one entry per stream there is
-        # (a demultiplexing plan without files for its barcodes: their streams are dropped, and are of class 3 all the same)
-        no_bin_files = [[None] * (2 if paired else 1)] if n_bins and not bin_files else []
-        fasta_routes = output_formats(name_groups + no_bin_files, has_qualities=not r1.fasta)
+        fasta_routes = output_formats(name_groups, has_qualities=not r1.fasta)
 
-        def mk(names):
-            group = []
-            for n in names:
-                group.append(StreamWriter(n, precompressed=compress) if n else None)
-                if group[-1] is not None:
-                    opened.append(group[-1])
-            return group
+        def writer(name, precompressed):
+            opened.append(StreamWriter(name, precompressed=precompressed))
+            return opened[-1]
 
-        outs = [mk(names) for names in name_groups]
+        outs = [[writer(n, compress) if n else None for n in names] for names in name_groups]
         # --info-file: one more stream per batch.  The container goes by the file's name like a record output's; a
         # ".gz" table leaves the device as gzip members (CUTSEQ_GPU_DEFLATE=0: deflated in the host pool instead).
         info_name = getattr(args, "info_file", None)
@@ -838,8 +806,7 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         if info_name:
             info_gz = info_name != "-" and codec.container_of_name(info_name) == "gzip" and os.environ.get("CUTSEQ_GPU_DEFLATE", "1") != "0"
             info_flags = abi.CS_INFO_ON | (abi.CS_INFO_GZIP if info_gz else 0) | (abi.CS_INFO_NO_QUAL if r1.fasta else 0)
-            info_out = StreamWriter(info_name, precompressed=info_gz)
-            opened.append(info_out)
+            info_out = writer(info_name, info_gz)
     except BaseException:
         r1.close()
         if r2 is not None:
@@ -852,17 +819,35 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         raise
     totals = report.new_totals()
     t_start = time.perf_counter()
-    if PROFILE:
-        from .run import _phase
-        _phase("readers and writers open")
-    done: "queue.Queue" = queue.Queue()
-    workers = [TextWorker(tp, dev, done, chunk_reads, compress, n_bins, fasta_routes, info_flags) for dev in devices]
+    report.phase("readers and writers open")
+    workers = [TextWorker(tp, dev, chunk_reads, compress, n_bins, fasta_routes, info_flags) for dev in devices]
     if n_bins:
         totals["routes"] += [0] * n_bins
     budget = threading.Semaphore(2 * len(workers) * TextWorker.SLOTS + 2)  # batches between reader and disk
-    failure: List[BaseException] = []
-
     progress = report.Progress()
+
+    def pairs():
+        """The mates' blocks, side by side."""
+        while True:
+            t0 = time.perf_counter()
+            b1 = r1.get()
+            b2 = r2.get() if r2 is not None else None
+            _tick("main_wait_readers", t0)
+            if b1 is None and b2 is None:
+                return
+            if r2 is not None and (b1 is None or b2 is None or b1.n != b2.n):
+                for b in (b1, b2):
+                    if b is not None:
+                        b.release()
+                raise fastq.FastqFormatError(
+                    "Reads are improperly paired! There are more reads in one file than in the other, "
+                    "or a record is truncated.")
+            yield b1, b2
+
+    def admit(failed):
+        while not budget.acquire(timeout=0.2):
+            if failed():
+                return
 
     def emit(item: _Done):
         res = item.res
@@ -893,96 +878,18 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         for fh, view in jobs:
             fh.put(view, shared)
 
-    def collect():
-        waiting, next_k, alive = {}, 0, len(workers)
-        try:
-            while alive or waiting:
-                item = done.get()
-                if isinstance(item, TextWorker):
-                    alive -= 1
-                    if item.error is not None:
-                        raise item.error
-                    if not alive and waiting and next_k not in waiting:
-                        raise RuntimeError("a batch went missing between the GPU workers and the writers")
-                    continue
-                waiting[item.k] = item
-                while next_k in waiting:
-                    emit(waiting.pop(next_k))
-                    next_k += 1
-        except BaseException as exc:
-            failure.append(exc)
-            while alive:  # keep the workers from blocking on a dead consumer
-                item = done.get()
-                if isinstance(item, TextWorker):
-                    alive -= 1
-                else:
-                    for b in item.out + ([item.info] if item.info is not None else []):
-                        fastq.PINNED.give(b)
-                    budget.release()
+    def orphan(item: _Done):
+        for b in item.out + ([item.info] if item.info is not None else []):
+            fastq.PINNED.give(b)
+        budget.release()
 
-    collector = threading.Thread(target=collect, daemon=True, name="cutseq-collect")
-    for w in workers:
-        w.start()
-    collector.start()
-    first_error: Optional[BaseException] = None
-    try:
-        k = 0
-        while not failure:
-            t0 = time.perf_counter()
-            b1 = r1.get()
-            b2 = r2.get() if r2 is not None else None
-            _tick("main_wait_readers", t0)
-            if b1 is None and b2 is None:
-                break
-            if r2 is not None and (b1 is None or b2 is None or b1.n != b2.n):
-                for b in (b1, b2):
-                    if b is not None:
-                        b.release()
-                raise fastq.FastqFormatError(
-                    "Reads are improperly paired! There are more reads in one file than in the other, "
-                    "or a record is truncated.")
-            while not budget.acquire(timeout=0.2):
-                if failure:
-                    break
-            w = workers[k % len(workers)]
-            while not failure:
-                try:
-                    w.inbox.put((k, b1, b2), timeout=0.2)
-                    break
-                except queue.Full:
-                    continue
-            k += 1
-    except BaseException as exc:
-        first_error = exc
-    finally:
-        r1.close()
-        if r2 is not None:
-            r2.close()
-        for w in workers:
-            while True:
-                try:
-                    w.inbox.put(None, timeout=0.2)
-                    break
-                except queue.Full:
-                    if not w.is_alive():
-                        break
-        for w in workers:
-            w.join()
-        collector.join()
-        for group in outs + [[info_out]]:
-            for fh in group:
-                if fh is None:
-                    continue
-                try:
-                    fh.close()
-                except BaseException as exc:
-                    first_error = first_error or exc
-    if first_error is None and failure:
-        first_error = failure[0]
-    if first_error is None:
-        first_error = next((w.error for w in workers if w.error is not None), None)
-    if first_error is not None:
-        raise first_error
+    def discard(item):
+        for b in item:
+            if b is not None:
+                b.release()
+
+    fanout.run_ordered(workers, pairs(), emit, orphan, admit=admit, discard=discard,
+                       closers=[r.close for r in (r1, r2) if r is not None] + [fh.close for fh in opened])
     # (the pinned arena stays: page-locking gigabytes costs more than a short run; it is freed when the process ends)
     stats = [w.stats for w in workers if w.stats is not None]
     for m in range(2 if paired else 1):

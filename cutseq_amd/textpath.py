@@ -14,6 +14,7 @@ from typing import Optional
 import numpy as np
 
 from . import abi, capi
+from .abi import ReadTooLong  # noqa: F401  (the name callers know it by)
 from .engine import TrimEngine
 from .plan import CutOp, TrimPlan
 
@@ -30,14 +31,6 @@ class TextFormatError(ValueError):
 
 class InfoMismatch(RuntimeError):
     """``CS_TEXT_ERR_INFO_MISMATCH`` / ``CS_TEXT_ERR_INFO_OVERFLOW``: an engine fault, never the input's."""
-
-
-class ReadTooLong(ValueError):
-    """A read beyond CS_MAX_READ (the text path's positions are 32-bit, its long-read kernel serial per read)."""
-
-    def __init__(self, longest: int):
-        super().__init__(f"reads longer than {abi.CS_MAX_READ} nt are not supported (a read of {longest} nt)")
-        self.longest = longest
 
 
 def max_tag(plan: TrimPlan) -> int:
@@ -127,7 +120,8 @@ class TextEngine:
         res = abi.cs_text_result()
         capi.check(self.L.cs_text_wait(self._h, slot, C.byref(res)))
         if res.error == abi.CS_TEXT_ERR_TOO_LONG:
-            raise ReadTooLong(int(res.max_len))
+            raise ReadTooLong(f"reads longer than {abi.CS_MAX_READ} nt are not supported (a read of {int(res.max_len)} nt)",
+                              int(res.max_len))
         if res.error == abi.CS_TEXT_ERR_MALFORMED:
             raise TextFormatError(res.error, first_record + res.error_record,
                                   f"malformed FASTQ record {first_record + res.error_record + 1} "

@@ -231,6 +231,41 @@ def test_cli_many_chunks_two_engines_on_one_gpu(tmp_path, monkeypatch):
     assert len(rep["engine"]["per_device"]) == 2  # both engines saw chunks
 
 
+@pytest.fixture(params=["", "CUTSEQ_TEXT_PATH=0"])
+def path_switch(request):
+    return dict([request.param.split("=")]) if request.param else {}
+
+
+def test_cli_unwritable_output_ends_the_run_with_its_error(tmp_path, path_switch):
+    """An output path whose parent is a regular file: the child process ends with that OSError (an ordinary host I/O
+    error) instead of hanging, on the text path and on the record path.  The file fails to OPEN, before any worker
+    starts, so this is the CLI's exit only; the failure in the middle of a run is the next test's."""
+    import os
+    import subprocess
+    import sys
+    (tmp_path / "file").write_bytes(b"not a directory")
+    env = dict(os.environ, CUTSEQ_DEVICES="0,0", CUTSEQ_CHUNK_READS="64", CUTSEQ_PROGRESS="0", **path_switch)
+    r = subprocess.run([sys.executable, "-m", "cutseq_amd.run", "-A", "TAKARAV3", R1, R2, "-O", str(tmp_path / "out"),
+                        "-s", str(tmp_path / "file" / "s1.fq.gz"), str(tmp_path / "s2.fq.gz")],
+                       capture_output=True, text=True, cwd=str(util.GOLDEN.parents[1]), env=env, timeout=60)
+    assert r.returncode == 1, r.stderr[-1500:]
+    assert "NotADirectoryError" in r.stderr and "s1.fq.gz" in r.stderr
+
+
+def test_cli_write_error_in_the_middle_of_a_run_leaves_no_thread(tmp_path, monkeypatch, path_switch):
+    """... and in this process, with a file that opens and cannot be written (/dev/full), so that the error comes up
+    while chunks are in flight (two workers on GPU 0, 16 chunks): the OSError is raised through the fan-out's drain
+    and every thread of the run is gone."""
+    import errno
+    import threading
+    for k, v in dict(path_switch, CUTSEQ_DEVICES="0,0", CUTSEQ_CHUNK_READS="64").items():
+        monkeypatch.setenv(k, v)
+    with pytest.raises(OSError) as e:
+        cli.main(["-A", "TAKARAV3", R1, R2, "-O", str(tmp_path / "out"), "-o", "/dev/full", str(tmp_path / "t2.fq")])
+    assert e.value.errno == errno.ENOSPC
+    assert [t.name for t in threading.enumerate() if t.name.startswith("cutseq-")] == []
+
+
 def test_cli_full_reference_input_in_small_chunks(tmp_path, monkeypatch):
     """BASELINE.json config 1 at full size: the reference's own 10 000-pair input (tests/golden/fixture10k_*,
     a copy of test/input_R{1,2}.fq.gz), defaults, in chunks of 1 500 records so that seven chunks cycle

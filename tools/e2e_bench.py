@@ -1,12 +1,19 @@
 #!/usr/bin/env python3
 """Tier E through the product CLI, in-process, with start-up amortised.
 
-  python tools/e2e_bench.py [pairs] [workdir]
+  python tools/e2e_bench.py [pairs] [workdir] [--forms plain_warm,plain_to_gz] [--tree DIR] [--keep]
 
 Writes a synthetic paired data set once (plain text and multi-member gzip), then runs
 ``cutseq_amd.run.main`` on it: plain -> plain twice (the second run has warm buffers and page cache),
 gz -> gz once.  Prints one JSON object.  Not the headline metric: bench.py reports the HBM-resident rate.
+
+For an A/B of two commits on one machine: ``--forms`` runs only the named forms (``plain_warm`` brings its cold run
+along), ``--tree DIR`` takes ``cutseq_amd`` from another built checkout (the data set is always written by this
+tree's ``make_fastq.py``: both legs read the same files), ``--keep`` leaves the data set in the work directory (and
+reuses the one that is there), so that the legs can alternate, one process each, over the same files.
+profiles/fanout_ab.log was measured this way.
 """
+import argparse
 import json
 import os
 import shutil
@@ -20,24 +27,36 @@ sys.path.insert(0, str(ROOT))
 
 
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 8_000_000
+    ap = argparse.ArgumentParser()
+    ap.add_argument("pairs", type=int, nargs="?", default=8_000_000)
+    ap.add_argument("workdir", nargs="?", default="/dev/shm/cutseq_e2e")
+    ap.add_argument("--forms", type=lambda v: v.split(","), default=None)
+    ap.add_argument("--tree", default=None)
+    ap.add_argument("--keep", action="store_true")
+    opts = ap.parse_args()
+    if opts.tree:
+        sys.path.insert(0, str(Path(opts.tree).resolve()))
+    n = opts.pairs
     # the steady-state regime: blocks of 262 144 records, what inputs of 25 M pairs and more get (smaller inputs get
     # smaller blocks -- a fresh process spends more time page-locking big buffers than it saves: tools/cold_runs.py)
     os.environ.setdefault("CUTSEQ_CHUNK_READS", "262144")
-    work = Path(sys.argv[2] if len(sys.argv) > 2 else "/dev/shm/cutseq_e2e")
+    work = Path(opts.workdir)
     work.mkdir(parents=True, exist_ok=True)
     free = shutil.disk_usage(work).free
     need = n * 2 * 340 * 3
     if free < need:
         raise SystemExit(f"{work}: {free >> 20} MiB free, {need >> 20} MiB needed for {n} pairs")
     out = {"pairs": n, "workdir": str(work), "cpus": len(os.sched_getaffinity(0))}
-    t0 = time.perf_counter()
-    subprocess.run([sys.executable, str(ROOT / "tools" / "make_fastq.py"), str(n), str(work / "syn")], check=True)
-    out["make_gz_s"] = round(time.perf_counter() - t0, 2)
     from cutseq_amd import codec, fastq, run as cli
+    out["tree"] = str(Path(cli.__file__).resolve().parents[1])
+    have = opts.keep and all((work / f"{stem}_R{m}.{end}").exists() for m in (1, 2) for stem, end in (("syn", "fastq.gz"), ("plain", "fastq")))
+    t0 = time.perf_counter()
+    if not have:
+        subprocess.run([sys.executable, str(ROOT / "tools" / "make_fastq.py"), str(n), str(work / "syn")], check=True)
+    out["make_gz_s"] = round(time.perf_counter() - t0, 2)
 
     t0 = time.perf_counter()
-    for m in (1, 2):  # plain copies of the same records
+    for m in () if have else (1, 2):  # plain copies of the same records
         src = codec.GzipSource(str(work / f"syn_R{m}.fastq.gz"), None, fastq.ARENA.take, fastq.ARENA.give)
         with open(work / f"plain_R{m}.fastq", "wb") as dst:
             for arr, nbytes in src.blocks():
@@ -47,6 +66,8 @@ def main():
     out["gunzip_s"] = round(time.perf_counter() - t0, 2)
 
     def run(tag, inputs, outputs):
+        if opts.forms and tag not in opts.forms and not (tag == "plain_cold" and "plain_warm" in opts.forms):
+            return
         for old in work.glob("o[12].fastq"), work.glob("s[12].fastq"), work.glob("gzout_*"):
             for f in old:  # a run writes NEW files: freeing the previous run's gigabytes of tmpfs pages is not its job
                 f.unlink()
@@ -71,6 +92,8 @@ def main():
     # the usual sequencer output: ONE gzip member per file (gzip -1 of the first half of the records), which no
     # reader can enter in the middle
     n_single = n // 2
+    if opts.forms and "single_member_gz_to_gz" not in opts.forms:
+        return finish(work, out, opts.keep)
     t0 = time.perf_counter()
     procs = []
     for m in (1, 2):
@@ -85,7 +108,12 @@ def main():
     run("single_member_gz_to_gz", single_in, ["-O", str(work / "gzout")])
     out["single_member_gz_to_gz"]["pairs"] = n_single
     n = n_all
-    shutil.rmtree(work, ignore_errors=True)
+    finish(work, out, opts.keep)
+
+
+def finish(work, out, keep):
+    if not keep:
+        shutil.rmtree(work, ignore_errors=True)
     print(json.dumps(out))
 
 
