@@ -45,6 +45,9 @@ CS_F_UNTRIMMED = 0x40
 CS_F_AMBIGUOUS = 0x80
 
 CS_X_TOO_MANY_N = 0x01  # cs_reads.xflags
+CS_X_TOO_LONG = 0x02
+CS_X_TOO_MANY_EE = 0x04
+CS_X_COUNTS = 3  # cs_xflag_counts_fetch: one count per CS_X_* bit, bit 0 first
 
 CS_OK = 0
 CS_ERR_ARG, CS_ERR_HIP, CS_ERR_NO_GPU, CS_ERR_NOMEM, CS_ERR_STATE = -1, -2, -3, -4, -5

@@ -3,6 +3,7 @@
 // gfx950 (MI355X) only; there is no CPU path in this library.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -132,7 +133,7 @@ struct cs_engine {
   bool paired = false;
   bool coded = false;
   bool wide = false;  // some adapter needs 64-bit bit-vectors
-  bool max_n = false;  // the plan has a TooManyN filter (cs_plan_set_max_n)
+  uint32_t filters = 0;  // CS_X_* bits of the plan's filters (cs_plan_set_max_length / _max_n / _max_ee)
   int n_cus = 256;
   uint32_t n_table_ops = 1;
   uint32_t col_dwords = 0;   // per-wave DP scratch the plan needs (resolve kernel)
@@ -259,17 +260,19 @@ struct Geometry {
   uint32_t tile_rows, lds_stride_dw, col_dwords, lds_bytes, item_slots;
 };
 
-template <int MODE, bool MAXN>
+template <int MODE, int FILT>
 const void *kernel_variant(const cs_engine *eng) {
   if (eng->coded)
-    return eng->wide ? reinterpret_cast<const void *>(csdev::trim_kernel<true, true, MODE, MAXN>)
-                     : reinterpret_cast<const void *>(csdev::trim_kernel<true, false, MODE, MAXN>);
-  return eng->wide ? reinterpret_cast<const void *>(csdev::trim_kernel<false, true, MODE, MAXN>)
-                   : reinterpret_cast<const void *>(csdev::trim_kernel<false, false, MODE, MAXN>);
+    return eng->wide ? reinterpret_cast<const void *>(csdev::trim_kernel<true, true, MODE, FILT>)
+                     : reinterpret_cast<const void *>(csdev::trim_kernel<true, false, MODE, FILT>);
+  return eng->wide ? reinterpret_cast<const void *>(csdev::trim_kernel<false, true, MODE, FILT>)
+                   : reinterpret_cast<const void *>(csdev::trim_kernel<false, false, MODE, FILT>);
 }
 template <int MODE>
-const void *kernel_of(const cs_engine *eng) {  // plans with TooManyN take the kernels that decide it
-  return eng->max_n ? kernel_variant<MODE, true>(eng) : kernel_variant<MODE, false>(eng);
+const void *kernel_of(const cs_engine *eng) {  // plans with filters take the kernels that decide them
+  if (!eng->filters) return kernel_variant<MODE, csdev::FILT_NONE>(eng);
+  if (eng->filters == CS_X_TOO_MANY_N) return kernel_variant<MODE, csdev::FILT_MAXN>(eng);
+  return kernel_variant<MODE, csdev::FILT_ALL>(eng);
 }
 const void *kernel_for(const cs_engine *eng, int mode) {
   if (mode == csdev::MODE_RESOLVE) return kernel_of<csdev::MODE_RESOLVE>(eng);
@@ -660,6 +663,28 @@ int cs_plan_set_max_n(cs_plan *plan, double count) {
   return CS_OK;
 }
 
+int cs_plan_set_max_length(cs_plan *plan, uint32_t length) {
+  if (!plan) return fail(CS_ERR_ARG, "null plan");
+  plan->host.max_length_on = 1;
+  plan->host.max_length = length;
+  return CS_OK;
+}
+
+int cs_plan_set_max_ee(cs_plan *plan, double errors) {
+  if (!plan) return fail(CS_ERR_ARG, "null plan");
+  if (!(errors >= 0.0)) return fail(CS_ERR_ARG, "max_ee %g: the bound must not be negative or NaN", errors);
+  plan->host.max_ee_on = 1;
+  plan->host.max_ee = errors;
+  for (int b = 0; b < 256; ++b) plan->host.ee_table[b] = pow(10.0, (double)(33 - b) / 10.0);
+  return CS_OK;
+}
+
+int cs_plan_set_ee_reversed(cs_plan *plan, int reversed) {
+  if (!plan) return fail(CS_ERR_ARG, "null plan");
+  plan->host.ee_reversed = reversed ? 1u : 0u;
+  return CS_OK;
+}
+
 int cs_plan_set_demux(cs_plan *plan, int mate, int op_index, const uint16_t *table, size_t entries) {
   if (!plan || !table) return fail(CS_ERR_ARG, "null plan or table");
   if (mate < 1 || mate > 2 || op_index < 0 || op_index >= plan->host.n_ops[mate - 1])
@@ -932,7 +957,8 @@ int cs_engine_create(const cs_plan *plan, int device, uint32_t n_slots, uint32_t
   eng->device = device;
   eng->paired = plan->host.n_ops[1] > 0;
   eng->coded = plan->host.coded != 0;
-  eng->max_n = plan->host.max_n_on != 0;
+  eng->filters = (plan->host.max_length_on ? CS_X_TOO_LONG : 0u) | (plan->host.max_n_on ? CS_X_TOO_MANY_N : 0u) |
+                 (plan->host.max_ee_on ? CS_X_TOO_MANY_EE : 0u);
   eng->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   eng->n_table_ops = (uint32_t)(plan->host.n_ops[0] > plan->host.n_ops[1] ? plan->host.n_ops[0] : plan->host.n_ops[1]);
   if (eng->n_table_ops < 1) eng->n_table_ops = 1;
@@ -1049,8 +1075,8 @@ int cs_engine_create(const cs_plan *plan, int device, uint32_t n_slots, uint32_t
     ENG_TRY(hipMemcpyToSymbol(HIP_SYMBOL(csdev::c_plans), &dp, sizeof(csdev::DevPlan),
                               (size_t)eng->plan_slot * sizeof(csdev::DevPlan), hipMemcpyHostToDevice));
   }
-  ENG_TRY(hipMalloc(&eng->d_stats, 2 * sizeof(cs_stats)));
-  ENG_TRY(hipMemset(eng->d_stats, 0, 2 * sizeof(cs_stats)));
+  ENG_TRY(hipMalloc(&eng->d_stats, csdev::kStatsBlockWords * 8));  // (the two cs_stats, then the XST_* words)
+  ENG_TRY(hipMemset(eng->d_stats, 0, csdev::kStatsBlockWords * 8));
   eng->slots.resize(n_slots);
   const size_t bytes = (size_t)max_reads * max_stride;
   for (Slot &s : eng->slots) {
@@ -1060,7 +1086,7 @@ int cs_engine_create(const cs_plan *plan, int device, uint32_t n_slots, uint32_t
       ENG_TRY(hipMalloc(&s.d_len[m], (size_t)max_reads * sizeof(uint16_t)));
       ENG_TRY(hipMalloc(&s.d_out[m], (size_t)max_reads * sizeof(cs_result)));
       ENG_TRY(hipMalloc(&s.d_bc[m], (size_t)max_reads));
-      if (eng->max_n) ENG_TRY(hipMalloc(&s.d_xf[m], (size_t)max_reads));  // (only a plan with TooManyN writes them)
+      if (eng->filters) ENG_TRY(hipMalloc(&s.d_xf[m], (size_t)max_reads));  // (only a plan with a filter writes them)
     }
     ENG_TRY(hipMalloc(&s.d_cap2, (size_t)max_reads * sizeof(cs_cap2)));
     ENG_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
@@ -1158,7 +1184,7 @@ int cs_trim_batch(cs_engine *eng, uint32_t slot, const cs_reads *r1, const cs_re
     dev[m].out = s.d_out[m];
     dev[m].cap2 = (m == 0 && rr[m]->cap2) ? s.d_cap2 : nullptr;
     dev[m].bc = rr[m]->bc ? s.d_bc[m] : nullptr;
-    dev[m].xflags = (rr[m]->xflags && eng->max_n) ? s.d_xf[m] : nullptr;  // (only a plan with the filter writes them)
+    dev[m].xflags = (rr[m]->xflags && eng->filters) ? s.d_xf[m] : nullptr;  // (only a plan with a filter writes them)
   }
   // H2D and scan kernel on the engine stream, resolve kernel and D2H on the resolve stream: the next slot's
   // copies and scan kernel overlap this slot's resolve kernel and write-back
@@ -1170,7 +1196,7 @@ int cs_trim_batch(cs_engine *eng, uint32_t slot, const cs_reads *r1, const cs_re
     if (m == 0 && rr[m]->cap2)
       HIP_TRY(hipMemcpyAsync(rr[m]->cap2, s.d_cap2, (size_t)n_reads * sizeof(cs_cap2), hipMemcpyDeviceToHost, rs));
     if (rr[m]->bc) HIP_TRY(hipMemcpyAsync(rr[m]->bc, s.d_bc[m], (size_t)n_reads, hipMemcpyDeviceToHost, rs));
-    if (rr[m]->xflags && eng->max_n)
+    if (rr[m]->xflags && eng->filters)
       HIP_TRY(hipMemcpyAsync(rr[m]->xflags, s.d_xf[m], (size_t)n_reads, hipMemcpyDeviceToHost, rs));
   }
   HIP_TRY(hipEventRecord(s.done, rs));
@@ -1198,6 +1224,29 @@ int cs_stats_fetch(cs_engine *eng, cs_stats stats[2], int reset) {
   HIP_TRY(hipMemcpyAsync(stats, eng->d_stats, 2 * sizeof(cs_stats), hipMemcpyDeviceToHost, eng->stream));
   if (reset) HIP_TRY(hipMemsetAsync(eng->d_stats, 0, 2 * sizeof(cs_stats), eng->stream));
   HIP_TRY(hipStreamSynchronize(eng->stream));
+  return CS_OK;
+}
+
+int cs_xflag_counts_fetch(cs_engine *eng, uint64_t counts[2][CS_X_COUNTS], int reset) {
+  if (!eng || !counts) return fail(CS_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(eng->device));
+  for (Lane &ln : eng->lanes)
+    if (ln.used) HIP_TRY(hipStreamWaitEvent(eng->stream, ln.done, 0));
+  unsigned long long many_n[2], rest[2][csdev::kXStatWords];
+  unsigned long long *xst = eng->d_stats + csdev::kXStatBase;
+  for (int m = 0; m < 2; ++m) {
+    unsigned long long *word = eng->d_stats + (size_t)m * csdev::kStatWords + csdev::ST_TOO_MANY_N;
+    HIP_TRY(hipMemcpyAsync(&many_n[m], word, 8, hipMemcpyDeviceToHost, eng->stream));
+    if (reset) HIP_TRY(hipMemsetAsync(word, 0, 8, eng->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(rest, xst, sizeof rest, hipMemcpyDeviceToHost, eng->stream));
+  if (reset) HIP_TRY(hipMemsetAsync(xst, 0, sizeof rest, eng->stream));
+  HIP_TRY(hipStreamSynchronize(eng->stream));
+  for (int m = 0; m < 2; ++m) {  // in the order of the bits: CS_X_TOO_MANY_N, CS_X_TOO_LONG, CS_X_TOO_MANY_EE
+    counts[m][0] = many_n[m];
+    counts[m][1] = rest[m][csdev::XST_TOO_LONG];
+    counts[m][2] = rest[m][csdev::XST_TOO_MANY_EE];
+  }
   return CS_OK;
 }
 
@@ -1533,7 +1582,7 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
     t->mixed_formats = mask != 0 && mask != exist;
     t->tp.fasta_routes = mask == exist ? 0xffu : mask;
   }
-  t->tp.max_n = eng->max_n ? 1 : 0;
+  t->tp.filters = (uint8_t)eng->filters;
   t->tp.flag_too_short = CS_F_TOO_SHORT;
   t->tp.flag_untrimmed = CS_F_UNTRIMMED;
   const char *const *suf[2] = {params->suffix1, params->suffix2};
@@ -1664,7 +1713,7 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
         c.take(s.d_bc, max_records);
         c.take(s.d_routes, 1);
       }
-      if (t->tp.max_n)
+      if (t->tp.filters)
         for (int m = 0; m < mates; ++m) c.take(s.d_xf[m], max_records);
       if (t->info) {
         c.take(s.d_imatch, (size_t)max_records * (eng->info_adapters ? eng->info_adapters : 1u));
@@ -1759,10 +1808,14 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
       la.n_long = &s.d_meta->n_long[m];
       la.cap = n_records;
       la.stats = eng->d_stats + (size_t)m * csdev::kStatWords;
+      la.xstats = eng->d_stats + csdev::kXStatBase + (size_t)m * csdev::kXStatWords;
       la.plan_slot = (uint32_t)eng->plan_slot;
       la.mate = m;
       la.gate = &s.d_meta->err;
-      hipLaunchKernelGGL(cslong::long_kernel, dim3(256), dim3(64), 0, st, la);
+      if (eng->filters & (CS_X_TOO_LONG | CS_X_TOO_MANY_EE))
+        hipLaunchKernelGGL(cslong::long_kernel<true>, dim3(256), dim3(64), 0, st, la);
+      else
+        hipLaunchKernelGGL(cslong::long_kernel<false>, dim3(256), dim3(64), 0, st, la);
     }
     HIP_TRY(hipGetLastError());
     cs_reads rd[2];
@@ -1952,6 +2005,18 @@ int cs_text_routes(cs_text *t, uint32_t slot, uint64_t *bytes, uint64_t *text_by
     }
   if (count)
     for (uint32_t q = 0; q < t->n_routes; ++q) count[q] = t->tp.n_bins ? s.h_routes->count[q] : m.route_count[q];
+  return CS_OK;
+}
+
+int cs_text_discards(cs_text *t, uint32_t slot, uint32_t pairs[3]) {
+  if (!t || !pairs) return fail(CS_ERR_ARG, "null argument");
+  if (slot >= t->slots.size()) return fail(CS_ERR_ARG, "slot %u out of range", slot);
+  TextSlot &s = t->slots[slot];
+  if (!s.waited) return fail(CS_ERR_STATE, "slot %u: cs_text_wait first", slot);
+  const cstext::TextMeta &m = *s.h_meta;
+  pairs[0] = m.n_too_long;
+  pairs[1] = m.n_too_many_n;
+  pairs[2] = m.n_too_many_ee;
   return CS_OK;
 }
 

@@ -397,19 +397,20 @@ static uint8_t *emit(uint8_t *o, const uint8_t *id, int32_t idl, const uint8_t *
   return o;
 }
 
-/* TooManyN (cs_reads.xflags bit 0, CS_X_TOO_MANY_N), pair filter "any": behind TooShort, in front of IsUntrimmedAny.
- * xf1 / xf2 NULL: no such filter. */
+/* The discarding filters (cs_reads.xflags: CS_X_TOO_MANY_N 1, CS_X_TOO_LONG 2, CS_X_TOO_MANY_EE 4), pair filter "any":
+ * behind TooShort, in front of IsUntrimmedAny.  Whichever of them catches the pair, it goes nowhere (which one it
+ * counts under is report.account_chunk's business).  xf1 / xf2 NULL: no such filter. */
 #define CSH_ROUTE_DISCARD (-1)
 static int route_of(const csh_format_params *fp, unsigned flags, unsigned xflags) {
   if (flags & fp->flag_too_short) return 1;
-  if (xflags & 1u) return CSH_ROUTE_DISCARD;
+  if (xflags & 7u) return CSH_ROUTE_DISCARD;
   return (fp->untrimmed_filter && (flags & fp->flag_untrimmed)) ? 2 : 0;
 }
 
 /* Format one chunk.  out[route][mate] are caller-allocated buffers (capacity: raw chunk bytes +
  * 260 per record is always enough); out_len[route][mate] receives the bytes written and
  * counts[route] the records (pairs).  Routes: 0 trimmed, 1 short, 2 untrimmed.  xf1 / xf2 (may be NULL): per-read
- * CS_X_* flags; the pairs TooManyN takes are written nowhere and counted in no route (n - the sum of counts[]).
+ * CS_X_* flags; the pairs TooLong / TooManyN / TooManyExpectedErrors take are written nowhere and counted in no route (n - the sum of counts[]).
  * Returns 0, or -(record index + 1) when the mates' ids differ. */
 int64_t csh_format_chunk(const csh_format_params *fp, int64_t n, uint32_t stride, const uint8_t *raw1,
                          const int64_t *name_off1, const int32_t *name_len1, const uint8_t *seq1,
@@ -469,7 +470,7 @@ int64_t csh_format_chunk(const csh_format_params *fp, int64_t n, uint32_t stride
  * [bin_off[mate * (n_bins + 1) + b], bin_off[.. + b + 1]).  Two passes: sizes, then bytes.  Records whose
  * bin is out of range (no barcode) are written to route 2 whatever their flags say.
  * bin_counts[b] receives the records (pairs) of bin b, counts[1], counts[2] those of the other routes.  xf1 / xf2 as
- * for csh_format_chunk: TooManyN takes a pair before the untrimmed and barcode routes see it. */
+ * for csh_format_chunk: a discarding filter takes a pair before the untrimmed and barcode routes see it. */
 typedef struct {
   int route;
   int32_t id1o, id1l, id2o, id2l, nl1, nl2;

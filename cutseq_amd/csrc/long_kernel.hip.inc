@@ -30,7 +30,7 @@ struct LongRec {  // one long read of one mate
 struct LongRes {  // its result: cs_result + cs_cap2 with 32-bit positions
   uint32_t start, stop, cap_off, cap2_off;
   uint8_t cap_len, cap2_len, flags, bc;
-  uint8_t xflags, _pad[3];  // CS_X_* (TooManyN)
+  uint8_t xflags, _pad[3];  // CS_X_* (TooLong, TooManyN, TooManyExpectedErrors)
 };
 
 struct Env {  // the plan's aligner settings
@@ -287,6 +287,7 @@ struct LongArgs {
   const uint32_t *n_long;      // how many of them (device side: the record kernel counts)
   uint32_t cap;                // capacity of rec / res
   unsigned long long *stats;   // this mate's cs_stats block (u64 words)
+  unsigned long long *xstats;  // this mate's csdev::XST_* words behind the two cs_stats
   uint32_t plan_slot;
   int mate;
   const unsigned long long *gate;
@@ -369,6 +370,9 @@ struct LongEvents {  // what long_kernel keeps of a walk besides the interval an
   }
 };
 
+// MORE: the instantiation that also decides TooLong and TooManyExpectedErrors (plans with cs_plan_set_max_length or
+// cs_plan_set_max_ee); every other plan runs the kernel it ran before those filters came.
+template <bool MORE>
 __global__ void __launch_bounds__(64) long_kernel(LongArgs a) {
   if (a.gate && *a.gate != ~0ull) return;
   const DevPlan *plan = &csdev::c_plans[a.plan_slot];
@@ -386,6 +390,24 @@ __global__ void __launch_bounds__(64) long_kernel(LongArgs a) {
       if (csdev::too_many_n(nn, w.e - w.s, plan->max_n)) {
         xflags = CS_X_TOO_MANY_N;
         atomicAdd(&a.stats[csdev::ST_TOO_MANY_N], 1ull);
+      }
+    }
+    if constexpr (MORE) {
+      if (plan->max_length_on && w.e > w.s && (uint32_t)(w.e - w.s) > plan->max_length) {  // TooLong
+        xflags |= CS_X_TOO_LONG;
+        atomicAdd(&a.xstats[csdev::XST_TOO_LONG], 1ull);
+      }
+      if (plan->max_ee_on) {  // TooManyExpectedErrors: the same left-to-right double sum as csdev::expected_errors
+        const uint8_t *qual = a.text + lr.qual_off;
+        double ee = 0.0;
+        if (!plan->ee_reversed)
+          for (int i = w.s; i < w.e; ++i) ee += plan->ee_table[qual[i]];
+        else  // (cs_plan_set_ee_reversed)
+          for (int i = w.e - 1; i >= w.s; --i) ee += plan->ee_table[qual[i]];
+        if (ee > plan->max_ee) {
+          xflags |= CS_X_TOO_MANY_EE;
+          atomicAdd(&a.xstats[csdev::XST_TOO_MANY_EE], 1ull);
+        }
       }
     }
     LongRes r;

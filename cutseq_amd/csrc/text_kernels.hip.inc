@@ -14,8 +14,9 @@
 //   text_restride         sequence and quality lines -> the [n][stride] rows the trimming kernels take (one lane per
 //                         destination dword: two aligned source dwords, one funnel shift)
 //   (scan + resolve kernels: trim_kernel.hip.inc, unchanged)
-//   format_sizes / format_scan / format_offsets   route of every record (TooShort -> TooManyN -> IsUntrimmedAny ->
-//                         sink, pair filter "any"; TooManyN discards the pair: no route, no bytes) and the byte offset of its output record inside the route's stream: block
+//   format_sizes / format_scan / format_offsets   route of every record (TooShort -> TooLong -> TooManyN ->
+//                         TooManyExpectedErrors -> IsUntrimmedAny -> sink, pair filter "any"; the three in the middle
+//                         discard the pair: no route, no bytes) and the byte offset of its output record inside the route's stream: block
 //                         sums, exclusive scan, block-local scans -- output order = input order
 //   format_copy           32 lanes per output record: '@' id ['_' UMI] '\n' seq[start:stop] "\n+\n" qual[start:stop] '\n'
 //
@@ -46,16 +47,18 @@ struct TextMeta {                    // what the host reads back per batch (one 
   uint32_t n_lines[2];
   uint32_t max_len;                  // longest read seen (the host grows the row stride when it exceeds it)
   uint32_t no_index;                 // bit m: mate m's text has the wrong line count, its newline index was not written
-  uint32_t n_too_many_n;             // pairs TooManyN discarded (plans with cs_plan_set_max_n)
-  uint32_t _pad;
-  unsigned long long written_bp[2];  // bases of the records that reach the final sink (route 0), per mate
+  // pairs the discarding filters took, each under the FIRST of TooLong -> TooManyN -> TooManyExpectedErrors that
+  // caught it (cs_plan_set_max_length / _max_n / _max_ee); n_too_many_ee fills what was padding
+  uint32_t n_too_many_n, n_too_long, n_too_many_ee;
+  alignas(8) unsigned long long written_bp[2];  // bases of the records that reach the final sink (route 0), per mate
   uint32_t n_long[2];                // per mate: reads longer than the rows (long_kernel.hip.inc walks their chains)
   unsigned long long gz_route_bytes[3][2];  // compressed output (deflate_kernels.hip.inc): bytes of each gzip member
   unsigned long long gz_bytes[2];           // ... per mate
 };
+static_assert(offsetof(TextMeta, written_bp) == 112 && sizeof(TextMeta) == 200, "TextMeta layout");
 
 constexpr uint32_t kMaxRoutes = 3 + 255;  // trimmed / short / untrimmed + one route per barcode of a demultiplexing plan
-constexpr uint32_t kRouteDiscard = 0x1feu;  // TooManyN: the pair goes nowhere (below the 0x1ff of the lanes past the end)
+constexpr uint32_t kRouteDiscard = 0x1feu;  // a discarding filter: the pair goes nowhere (below the 0x1ff of the lanes past the end)
 constexpr uint32_t kDiscarded = ~0u;        // FormatArgs.dst of a discarded record (no output offset is ever that)
 
 struct TextParams {  // constant per engine
@@ -67,7 +70,8 @@ struct TextParams {  // constant per engine
   uint8_t demux_mate;                // n_bins > 0: the mate (0 / 1) whose chain holds the demultiplexing op
   uint8_t fasta_routes;              // bit 2 * class + mate: that stream's records are ">id\nseq\n" (class = route, 3 for
                                      // every barcode's route).  cs_text_create folds cs_text_params.fasta_out into it
-  uint8_t max_n;                     // the plan has TooManyN: FormatArgs.xf holds its per-read flags
+  uint8_t filters;                   // the plan has some of TooLong / TooManyN / TooManyExpectedErrors (CS_X_* bits):
+                                     // FormatArgs.xf holds the per-read flags
   uint8_t _pad;
 };
 
@@ -358,7 +362,7 @@ struct FormatArgs {
   const uint32_t *long_of[2];        // per record: index into lrec / lres, or kNotLong
   const cslong::LongRec *lrec[2];
   const cslong::LongRes *lres[2];
-  const uint8_t *xf[2];    // TextParams.max_n: cs_reads.xflags of the tile kernels (long reads: LongRes.xflags)
+  const uint8_t *xf[2];    // TextParams.filters: cs_reads.xflags of the tile kernels (long reads: LongRes.xflags)
   uint32_t n, stride;
   uint32_t *blk;           // [n_blocks][6] block sums, then their exclusive scan (column = route * 2 + mate)
   unsigned long long *totals;  // [6] column sums
@@ -373,6 +377,8 @@ struct FormatArgs {
 
 struct RecordShape {
   uint32_t route, len[2];
+  uint32_t why;  // route == kRouteDiscard: 1 << 10 * k for the k-th of TooLong, TooManyN, TooManyExpectedErrors (the
+                 // first that caught the pair); 0 otherwise.  Three ten-bit counters sum in one word over a block.
 };
 
 // One mate's read as the formatter sees it, wherever its result came from: the rows and 8-byte results of the tile
@@ -438,9 +444,16 @@ __device__ __forceinline__ RecordShape record_shape(const FormatArgs &a, const T
   }
   if (tp.has_umi) tag = 1u + r1.cap_len + (tp.paired ? r2.cap_len : r1.cap2_len);
   s.route = (flags & tp.flag_too_short) ? 1u : ((tp.untrimmed_filter && (flags & tp.flag_untrimmed)) ? 2u : 0u);
-  // TooManyN (pair filter "any"), behind TooShort and in front of IsUntrimmedAny: cutadapt has no file for it
-  if (tp.max_n && s.route != 1u && ((xflags_of(a, 0, r) | (tp.paired ? xflags_of(a, 1, r) : 0u)) & CS_X_TOO_MANY_N))
-    s.route = kRouteDiscard;
+  // TooLong -> TooManyN -> TooManyExpectedErrors (pair filter "any": the OR of the mates' bits), behind TooShort and
+  // in front of IsUntrimmedAny: no file for any of them, the pair counts under the first that catches it
+  s.why = 0;
+  if (tp.filters && s.route != 1u) {
+    const uint32_t xf = (xflags_of(a, 0, r) | (tp.paired ? xflags_of(a, 1, r) : 0u)) & tp.filters;
+    if (xf) {
+      s.route = kRouteDiscard;
+      s.why = (xf & CS_X_TOO_LONG) ? 1u : ((xf & CS_X_TOO_MANY_N) ? 1u << 10 : 1u << 20);
+    }
+  }
   if (tp.n_bins && s.route == 0u) {
     const uint32_t slot = a.long_of[tp.demux_mate][r];  // (a read longer than the rows: its barcode is in the long kernel's result)
     const uint32_t bc = slot != kNotLong ? a.lres[tp.demux_mate][slot].bc : a.bc[r];
@@ -455,12 +468,19 @@ __device__ __forceinline__ RecordShape record_shape(const FormatArgs &a, const T
   return s;
 }
 
+// a block's discards (RecordShape.why summed over its 256 records) -> the batch's three counts
+__device__ __forceinline__ void add_discards(TextMeta *meta, uint32_t packed) {
+  if (packed & 0x3ffu) atomicAdd(&meta->n_too_long, packed & 0x3ffu);
+  if ((packed >> 10) & 0x3ffu) atomicAdd(&meta->n_too_many_n, (packed >> 10) & 0x3ffu);
+  if (packed >> 20) atomicAdd(&meta->n_too_many_ee, packed >> 20);
+}
+
 // (a rejected batch is not formatted: sizes derived from half-parsed records could exceed the output buffers)
 __global__ void __launch_bounds__(256) format_sizes(FormatArgs a, TextParams tp) {
   __shared__ uint32_t sh[8];
   if (a.meta->err != ~0ull) return;
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  RecordShape s = {3u, {0u, 0u}};
+  RecordShape s = {3u, {0u, 0u}, 0u};
   if (r < a.n) s = record_shape(a, tp, r);
 #pragma unroll
   for (uint32_t c = 0; c < 6; ++c) {
@@ -474,7 +494,7 @@ __global__ void __launch_bounds__(256) format_offsets(FormatArgs a, TextParams t
   __shared__ uint32_t sh[8];
   if (a.meta->err != ~0ull) return;
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  RecordShape s = {3u, {0u, 0u}};
+  RecordShape s = {3u, {0u, 0u}, 0u};
   if (r < a.n) s = record_shape(a, tp, r);
   // where a route's stream starts inside the mate's buffer: behind the routes in front of it
   unsigned long long base[3][2];
@@ -498,7 +518,7 @@ __global__ void __launch_bounds__(256) format_offsets(FormatArgs a, TextParams t
     counts[q] = total;
   }
   uint32_t discarded = 0;
-  if (tp.max_n) (void)block_scan_256(r < a.n && s.route == kRouteDiscard ? 1u : 0u, discarded, sh);
+  if (tp.filters) (void)block_scan_256(r < a.n ? s.why : 0u, discarded, sh);
   // cutadapt's written_bp: what reaches the final sink (report.account_chunk)
   uint32_t kept_bp[2] = {0, 0};
 #pragma unroll
@@ -518,7 +538,7 @@ __global__ void __launch_bounds__(256) format_offsets(FormatArgs a, TextParams t
   if (threadIdx.x == 0) {
     for (uint32_t q = 0; q < 3; ++q)
       if (counts[q]) atomicAdd(&a.meta->route_count[q], counts[q]);
-    if (discarded) atomicAdd(&a.meta->n_too_many_n, discarded);
+    add_discards(a.meta, discarded);
     for (uint32_t m = 0; m < 2; ++m)
       if (kept_bp[m]) atomicAdd(&a.meta->written_bp[m], (unsigned long long)kept_bp[m]);
     if (blockIdx.x == 0) {
@@ -573,12 +593,12 @@ __global__ void __launch_bounds__(256) format_offsets_bins(FormatArgs a, TextPar
   }
   __syncthreads();
   const uint32_t r = blockIdx.x * 256u + tid;
-  RecordShape s = {0x1ffu, {0u, 0u}};  // (lanes behind the last record: a route of their own)
+  RecordShape s = {0x1ffu, {0u, 0u}, 0u};  // (lanes behind the last record: a route of their own)
   if (r < a.n) {
     s = record_shape(a, tp, r);
     if (s.route == kRouteDiscard) {
       s.len[0] = s.len[1] = 0;
-      atomicAdd(&n_gone, 1u);
+      atomicAdd(&n_gone, s.why);
     } else {
       atomicAdd(&wsum[wave][s.route * 2u], s.len[0]);
       if (tp.paired) atomicAdd(&wsum[wave][s.route * 2u + 1u], s.len[1]);
@@ -633,7 +653,7 @@ __global__ void __launch_bounds__(256) format_offsets_bins(FormatArgs a, TextPar
   if (tid == 0) {
     for (uint32_t m = 0; m < 2; ++m)
       if (kept_bp[m]) atomicAdd(&a.meta->written_bp[m], (unsigned long long)kept_bp[m]);
-    if (n_gone) atomicAdd(&a.meta->n_too_many_n, n_gone);
+    add_discards(a.meta, n_gone);
   }
   if (blockIdx.x == 0) {
     for (uint32_t i = tid; i < cols; i += 256u) a.route_bytes[i] = a.totals[i];
@@ -678,7 +698,7 @@ __global__ void __launch_bounds__(256) format_copy(FormatArgs a, TextParams tp) 
   for (unsigned long long it = ((unsigned long long)blockIdx.x * 256ull + threadIdx.x) >> 5; it < items;
        it += ((unsigned long long)gridDim.x * 256ull) >> 5) {
     const uint32_t m = tp.paired ? (uint32_t)(it & 1ull) : 0u, r = (uint32_t)(tp.paired ? it >> 1 : it);
-    if (tp.max_n && a.dst[m][r] == kDiscarded) continue;  // (TooManyN; uniform over the record's 32 lanes)
+    if (tp.filters && a.dst[m][r] == kDiscarded) continue;  // (a discarded pair; uniform over the record's 32 lanes)
     const ReadView me = read_view(a, m, r);
     const ReadView r1 = m == 0 ? me : read_view(a, 0, r);
     const uint32_t idr = a.idr[m][r];

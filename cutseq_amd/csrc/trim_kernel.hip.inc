@@ -126,6 +126,12 @@ struct DevPlan {
   int32_t max_n_on;  // cs_plan_set_max_n was called: TooManyN(max_n) on the final interval of every read
   DevOp ops[2][CS_MAX_OPS];
   double max_n;
+  // the other two filters of the final interval (kernels with FILT == 2; new fields behind the old ones, so that the
+  // other kernels' loads keep their offsets)
+  uint32_t max_length_on, max_length;  // cs_plan_set_max_length: TooLong(max_length)
+  uint32_t max_ee_on, ee_reversed;     // cs_plan_set_max_ee: TooManyExpectedErrors(max_ee); cs_plan_set_ee_reversed
+  double max_ee;
+  double ee_table[256];                // 10 ** (-(byte - 33) / 10), the host's pow(), indexed by the raw quality byte
 };
 
 // Plans live in constant memory (scalar loads for everything wave-uniform); one slot per
@@ -2384,6 +2390,11 @@ enum { ST_READS = 0, ST_IN_BP, ST_OUT_BP, ST_QTRIM_BP, ST_TOO_SHORT, ST_UNTRIMME
 constexpr int ST_TOO_MANY_N = ST_OPS + CS_MAX_OPS;  // cs_stats.n_too_many_n, behind op_matched[]
 constexpr int kStatWords = ST_TOO_MANY_N + 1;
 static_assert(sizeof(cs_stats) == kStatWords * 8, "cs_stats layout");
+// The per-mate counts of the other CS_X_* bits lie behind the two cs_stats (cs_stats itself and the LDS accumulators
+// keep their size): word kXStatBase + mate * kXStatWords + XST_*; cs_xflag_counts_fetch reads them.
+enum { XST_TOO_LONG = 0, XST_TOO_MANY_EE, kXStatWords };
+constexpr int kXStatBase = 2 * kStatWords;
+constexpr int kStatsBlockWords = kXStatBase + 2 * kXStatWords;
 
 // ---- TooManyN (cs_plan_set_max_n, cutadapt --max-n): 'N' / 'n' bases in [s, e) of a row, and the filter's rule.
 // Raw bytes (ASCII rows in HBM, or a raw tile: its case folding only turns 'n' into 'N'): exact zero-byte test on
@@ -2423,6 +2434,38 @@ __device__ __forceinline__ bool too_many_n(uint32_t n, int len, double count) {
   if (count < 1.0) return len > 0 && (double)n / (double)len > count;
   return (double)n > count;
 }
+// cutadapt TooManyExpectedErrors: e = 0.0; for every quality byte of [s, e), left to right: e += table[byte].  One lane
+// per read and one IEEE double add per base, in index order: the filter compares this sum with strict >, so a tree or
+// a wave reduction (another rounding order) would decide reads at the threshold differently.  There is nothing to fuse
+// (no multiply) and the build has no fast-math, so the adds stay as written; a byte outside [s, e) of the first or
+// last dword adds nothing (not +0.0 either).  qrow: the read's quality row in HBM, dword-aligned.  reversed
+// (wave-uniform, cs_plan_set_ee_reversed): the caller writes the read reverse-complemented, so "left to right" in the
+// read cutadapt's filter sees is e - 1 down to s here.
+__device__ __forceinline__ double expected_errors(const uint32_t *qrow, int s, int e, const double *table, bool reversed) {
+  double ee = 0.0;
+  if (e <= s) return ee;
+  const int d0 = s >> 2, d1 = (e - 1) >> 2;
+  if (!reversed) {
+    for (int d = d0; d <= d1; ++d) {
+      const uint32_t w = qrow[d];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int p = 4 * d + b;
+        if (p >= s && p < e) ee += table[(w >> (8 * b)) & 0xffu];
+      }
+    }
+  } else {
+    for (int d = d1; d >= d0; --d) {
+      const uint32_t w = qrow[d];
+#pragma unroll
+      for (int b = 3; b >= 0; --b) {
+        const int p = 4 * d + b;
+        if (p >= s && p < e) ee += table[(w >> (8 * b)) & 0xffu];
+      }
+    }
+  }
+  return ee;
+}
 
 // ---------------------------------------------------------------------------------
 // Two kernels, one body.
@@ -2450,7 +2493,11 @@ enum { MODE_SCAN = 0, MODE_RESOLVE = 1 };
 #ifndef CS_SCAN_WAVES
 #define CS_SCAN_WAVES 5  // diagnostic builds: -DCS_SCAN_WAVES=6 / 7 (tools/lean_probe.sh)
 #endif
-template <bool CODED, bool WIDE, int MODE, bool MAXN>
+// FILT: the filters of the final interval this instantiation decides.  0: none (the code every plan without a filter
+// runs); 1: TooManyN alone (what a plan with cs_plan_set_max_n and nothing else runs); 2: any set of TooLong, TooManyN
+// and TooManyExpectedErrors, chosen at run time from the plan.
+enum { FILT_NONE = 0, FILT_MAXN = 1, FILT_ALL = 2 };
+template <bool CODED, bool WIDE, int MODE, int FILT>
 __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) trim_kernel(KArgs a) {
   if (a.gate && *a.gate != ~0ull) return;  // (wave-uniform: one wave per block)
   const DevPlan *plan = &c_plans[a.plan_slot];
@@ -3401,11 +3448,13 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
     if (ma.bc) ma.bc[gr] = (uint8_t)(meta >> 16);
   }
 
-  // ---- TooManyN on the final interval (cs_plan_set_max_n): kernels of their own (MAXN), so that a plan without the
-  // filter runs exactly the code it ran before (in the scan kernel's register budget any code here costs a spill)
-  if constexpr (MAXN) {
+  // ---- the filters of the final interval (cs_plan_set_max_n / _max_length / _max_ee): kernels of their own (FILT), so
+  // that a plan without a filter runs exactly the code it ran before (in the scan kernel's register budget any code
+  // here costs a spill), and a plan with TooManyN alone the code it ran before the other two came
+  if constexpr (FILT != FILT_NONE) {
+    const bool with_n = FILT == FILT_MAXN || plan->max_n_on;  // (wave-uniform, like the two below)
     bool many = false;
-    if (fin) {
+    if (fin && with_n) {
       uint32_t nn;
       // the fast form vouched for every byte of the tile exactly when the wave's staging has not failed (mode 1 only:
       // mode 2 never stages again, whatever the bytes are)
@@ -3419,9 +3468,25 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
     }
     const uint32_t w_many = wave_count(many);
     if (lane == 0 && w_many) atomicAdd(&sacc[ST_TOO_MANY_N], w_many);
-    if (fin && ma.xflags) ma.xflags[gr] = many ? (uint8_t)CS_X_TOO_MANY_N : (uint8_t)0;
+    uint32_t xf = many ? (uint32_t)CS_X_TOO_MANY_N : 0u;
+    if constexpr (FILT == FILT_ALL) {
+      const bool is_long = fin && plan->max_length_on && e > s && (uint32_t)(e - s) > plan->max_length;
+      bool errs = false;
+      if (plan->max_ee_on && ma.qual) {  // the read's own quality row, as the quality trimmer reads it
+        double ee = 0.0;
+        if (fin)
+          ee = expected_errors(reinterpret_cast<const uint32_t *>(ma.qual + (size_t)gr * a.stride_dw * 4u), s, e,
+                               plan->ee_table, plan->ee_reversed != 0);
+        errs = ee > plan->max_ee;
+      }
+      xf |= (is_long ? (uint32_t)CS_X_TOO_LONG : 0u) | (errs ? (uint32_t)CS_X_TOO_MANY_EE : 0u);
+      const uint32_t w_long = wave_count(is_long), w_errs = wave_count(errs);
+      unsigned long long *xst = a.stats + kXStatBase + mate * kXStatWords;
+      if (lane == 0 && w_long) atomicAdd(&xst[XST_TOO_LONG], (unsigned long long)w_long);
+      if (lane == 0 && w_errs) atomicAdd(&xst[XST_TOO_MANY_EE], (unsigned long long)w_errs);
+    }
+    if (fin && ma.xflags) ma.xflags[gr] = (uint8_t)xf;
   }
-
 
   // ---- statistics of this tile (reads that finished here): wave sums -> LDS accumulators
   {

@@ -41,6 +41,12 @@ class TrimEngine:
                 capi.check(self.L.cs_plan_set_demux_ops(self._plan_h, mate, index, C.cast(ops, C.c_void_p), len(op.barcodes)))
         if plan.max_n is not None:
             capi.check(self.L.cs_plan_set_max_n(self._plan_h, float(plan.max_n)))
+        if plan.max_length is not None:
+            capi.check(self.L.cs_plan_set_max_length(self._plan_h, min(int(plan.max_length), 0xFFFFFFFF)))
+        if plan.max_ee is not None:
+            capi.check(self.L.cs_plan_set_max_ee(self._plan_h, float(plan.max_ee)))
+            # (--auto-rc turns the read round before cutadapt's filters see it: the sum runs the other way)
+            capi.check(self.L.cs_plan_set_ee_reversed(self._plan_h, 1 if plan.reverse_complement else 0))
         self.n_slots, self.max_reads, self.max_stride = slots, max_reads, max_stride
         try:
             capi.check(self.L.cs_engine_create(self._plan_h, device, slots, max_reads, max_stride,
@@ -95,8 +101,8 @@ class TrimEngine:
         ``out``: optional (res1, cap2 | None, res2 | None) arrays to fill (e.g. pinned memory).
         ``bc``: optional uint8 array [n] for the barcode index (plans with a demultiplexing op; filled from the mate
         whose chain holds it).
-        ``xflags``: optional (mate 1, mate 2 | None) uint8 arrays [n] for ``cs_reads.xflags`` (CS_X_TOO_MANY_N of a plan
-        with ``max_n``)."""
+        ``xflags``: optional (mate 1, mate 2 | None) uint8 arrays [n] for ``cs_reads.xflags`` (the CS_X_* bits of a plan
+        with ``max_n``, ``max_length`` or ``max_ee``; a plan with none of them leaves the arrays untouched)."""
         if seq1.ndim != 2:
             raise ValueError("seq1: expected a 2-D array [n_reads, stride]")
         n, stride = seq1.shape
@@ -178,3 +184,10 @@ class TrimEngine:
         st = (abi.cs_stats * 2)()
         capi.check(self.L.cs_stats_fetch(self._eng_h, C.byref(st), 1 if reset else 0))
         return st[0], st[1]
+
+    def xflag_counts(self, reset: bool = False) -> Tuple[dict, dict]:
+        """Per mate: how many reads got each ``CS_X_*`` bit (per-mate counts: no pairs, no precedence)."""
+        counts = ((C.c_uint64 * abi.CS_X_COUNTS) * 2)()
+        capi.check(self.L.cs_xflag_counts_fetch(self._eng_h, C.byref(counts), 1 if reset else 0))
+        keys = ("too_many_n", "too_long", "too_many_ee")
+        return tuple({k: int(counts[m][i]) for i, k in enumerate(keys)} for m in range(2))

@@ -168,7 +168,7 @@ class Chunk:
 
     _owned: tuple = ()  # (arena, buffer) pairs behind the arrays above
     bc: Optional[np.ndarray] = None  # demultiplexing runs: barcode index per record (filled by the device)
-    xflags: Optional[tuple] = None  # runs with --max-n: cs_reads.xflags of (mate 1, mate 2 | None), filled by the device
+    xflags: Optional[tuple] = None  # runs with -M / --max-n / --max-ee: cs_reads.xflags of (mate 1, mate 2 | None), filled by the device
 
     @property
     def paired(self) -> bool:
@@ -454,7 +454,7 @@ class Lease:
 
 
 def _xflags_pointers(chunk: Chunk, xflags):
-    """``xflags``: None, or the (mate 1, mate 2 | None) uint8 arrays of ``cs_reads.xflags`` (TooManyN)."""
+    """``xflags``: None, or the (mate 1, mate 2 | None) uint8 arrays of ``cs_reads.xflags`` (CS_X_* bits)."""
     if xflags is None:
         return None, None
     xf1, xf2 = xflags
@@ -467,7 +467,7 @@ def _xflags_pointers(chunk: Chunk, xflags):
 def format_chunk(chunk: Chunk, plan, res1: np.ndarray, cap2: Optional[np.ndarray], res2: Optional[np.ndarray],
                  copy: bool = True, lease=None, xflags=None):
     """-> (data[route][mate], counts[route]) with routes 0 trimmed, 1 short, 2 untrimmed.  ``xflags`` (the per-read
-    ``cs_reads.xflags`` of both mates, or None): pairs TooManyN takes are written nowhere and counted in no route
+    ``cs_reads.xflags`` of both mates, or None): pairs TooLong / TooManyN / TooManyExpectedErrors take are written nowhere and counted in no route
     (``chunk.n - sum(counts)`` of them).  ``data`` holds
     ``bytes``; with ``copy=False`` it holds memoryviews into this thread's reusable buffers, valid
     until the thread formats its next chunk -- except the streams flagged in ``lease[route][mate]``,

@@ -49,6 +49,9 @@ class CutadaptConfig:
         self.demux_barcodes = None
         # cutadapt --max-n (the reference's TODO, run.py:452, 770): TooManyN(max_n) on both mates, None = off
         self.max_n = None
+        # cutadapt -M / --max-length and --max-ee: TooLong(max_length), TooManyExpectedErrors(max_ee), both mates
+        self.max_length = None
+        self.max_ee = None
 
 
 @dataclass
@@ -225,6 +228,13 @@ class TrimPlan:
     case_rule: int = abi.CS_CASE_FOLD
     indel_tie: int = abi.CS_TIE_INSERTION
     max_n: Optional[float] = None  # TooManyN(max_n) filter (cs_plan_set_max_n); None = no such filter
+    max_length: Optional[int] = None  # TooLong(max_length) filter (cs_plan_set_max_length); None = no such filter
+    max_ee: Optional[float] = None  # TooManyExpectedErrors(max_ee) filter (cs_plan_set_max_ee); None = no such filter
+
+    @property
+    def has_filters(self) -> bool:
+        """Some filter writes ``cs_reads.xflags`` (and discards pairs on the output paths)."""
+        return self.max_n is not None or self.max_length is not None or self.max_ee is not None
 
     @property
     def paired(self) -> bool:
@@ -445,6 +455,8 @@ def compile_single(barcode: BarcodeConfig, settings: CutadaptConfig, untrimmed_r
         case_rule=getattr(settings, "case_rule", abi.CS_CASE_FOLD),
         indel_tie=getattr(settings, "indel_tie", abi.CS_TIE_INSERTION),
         max_n=getattr(settings, "max_n", None),
+        max_length=getattr(settings, "max_length", None),
+        max_ee=getattr(settings, "max_ee", None),
     )
 
 
@@ -527,6 +539,8 @@ def compile_paired(barcode: BarcodeConfig, settings: CutadaptConfig, untrimmed_r
         case_rule=getattr(settings, "case_rule", abi.CS_CASE_FOLD),
         indel_tie=getattr(settings, "indel_tie", abi.CS_TIE_INSERTION),
         max_n=getattr(settings, "max_n", None),
+        max_length=getattr(settings, "max_length", None),
+        max_ee=getattr(settings, "max_ee", None),
     )
 
 

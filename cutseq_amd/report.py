@@ -38,27 +38,34 @@ ADAPTER_TYPES = {
 
 
 def new_totals() -> dict:
-    # too_many_n: pairs the TooManyN filter (--max-n) discarded -- written nowhere, in no route
-    return {"in_pairs": 0, "routes": [0, 0, 0], "in_bp": [0, 0], "out_bp": [0, 0], "written_bp": [0, 0], "too_many_n": 0}
+    # too_long / too_many_n / too_many_ee: pairs the discarding filters (-M, --max-n, --max-ee) took -- written nowhere,
+    # in no route, each pair under the first of the three that caught it
+    return {"in_pairs": 0, "routes": [0, 0, 0], "in_bp": [0, 0], "out_bp": [0, 0], "written_bp": [0, 0], "too_many_n": 0,
+            "too_long": 0, "too_many_ee": 0}
+
+
+# the discarding filters in cutadapt's order (behind TooShort, in front of IsUntrimmedAny): the total a pair counts in
+DISCARD_ORDER = (("too_long", abi.CS_X_TOO_LONG), ("too_many_n", abi.CS_X_TOO_MANY_N), ("too_many_ee", abi.CS_X_TOO_MANY_EE))
 
 
 def account_chunk(totals: dict, tp: TrimPlan, len1: np.ndarray, res1: np.ndarray,
                   len2: Optional[np.ndarray] = None, res2: Optional[np.ndarray] = None, xflags=None) -> None:
     """Fold one chunk's results into the run totals.  ``written_bp`` counts what reaches the final
     sink only (cutadapt's ``written_bp``): pairs routed to the short / untrimmed files are excluded, and so are
-    the pairs TooManyN discards (``xflags``: the per-read ``cs_reads.xflags`` of both mates, or None)."""
+    the pairs the discarding filters take (``xflags``: the per-read ``cs_reads.xflags`` of both mates, or None)."""
     flags = res1["flags"].astype(np.uint8)
     if res2 is not None:
         flags = flags | res2["flags"].astype(np.uint8)
     short = (flags & abi.CS_F_TOO_SHORT) != 0
     dropped = short.copy()
-    if xflags is not None:  # TooShort first, then TooManyN (pair filter "any")
+    if xflags is not None:  # TooShort first, then TooLong, TooManyN, TooManyExpectedErrors (pair filter "any")
         xf = xflags[0].astype(np.uint8)
         if res2 is not None and xflags[1] is not None:
             xf = xf | xflags[1].astype(np.uint8)
-        many = ((xf & abi.CS_X_TOO_MANY_N) != 0) & ~short
-        totals["too_many_n"] = totals.get("too_many_n", 0) + int(many.sum())
-        dropped |= many
+        for key, bit in DISCARD_ORDER:  # a pair counts once, under the first filter that catches it
+            taken = ((xf & bit) != 0) & ~dropped
+            totals[key] = totals.get(key, 0) + int(taken.sum())
+            dropped |= taken
     if tp.untrimmed_filter:
         dropped |= (flags & abi.CS_F_UNTRIMMED) != 0
     keep = ~dropped
@@ -74,7 +81,8 @@ def account_chunk(totals: dict, tp: TrimPlan, len1: np.ndarray, res1: np.ndarray
 
 def merge_totals(into: dict, part: dict) -> None:
     into["in_pairs"] += part["in_pairs"]
-    into["too_many_n"] = into.get("too_many_n", 0) + part.get("too_many_n", 0)
+    for key, _bit in DISCARD_ORDER:
+        into[key] = into.get(key, 0) + part.get(key, 0)
     for key in ("routes", "in_bp", "out_bp", "written_bp"):
         if len(into[key]) < len(part[key]):  # demultiplexing runs: one more stream per barcode
             into[key].extend([0] * (len(part[key]) - len(into[key])))
@@ -113,7 +121,8 @@ def minimal_report(tp: TrimPlan, totals: dict) -> str:
     fields = ["status", "in_reads", "in_bp", "too_short", "too_long", "too_many_n", "out_reads",
               "w/adapters", "qualtrim_bp", "out_bp"]
     s1, _ = first_adapter(tp.r1)
-    vals = ["OK", totals["in_pairs"], sum(totals["in_bp"]), totals["routes"][1], 0, totals.get("too_many_n", 0),
+    vals = ["OK", totals["in_pairs"], sum(totals["in_bp"]), totals["routes"][1], totals.get("too_long", 0),
+            totals.get("too_many_n", 0),
             written_pairs(totals),
             _matched(totals, 0, s1), _mate_sum(totals, 0, "qualtrim_bp"), totals["written_bp"][0]]
     if tp.paired:
@@ -170,6 +179,10 @@ def json_report(tp: TrimPlan, totals: dict, barcode, input1, input2, output1, ou
     filtered["too_short"] = totals["routes"][1]
     if tp.max_n is not None:  # (None: no such filter in the run, as cutadapt reports it)
         filtered["too_many_n"] = totals.get("too_many_n", 0)
+    if tp.max_length is not None:
+        filtered["too_long"] = totals.get("too_long", 0)
+    if tp.max_ee is not None:
+        filtered["too_many_expected_errors"] = totals.get("too_many_ee", 0)
     q1, q2 = _mate_sum(totals, 0, "qualtrim_bp"), (_mate_sum(totals, 1, "qualtrim_bp") if paired else None)
     engine = {"name": "cutseq_amd", "version": __version__, "devices": totals.get("devices"),
               "seconds": totals.get("seconds"), "is_untrimmed_any": totals["routes"][2] if tp.untrimmed_filter else None,

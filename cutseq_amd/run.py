@@ -91,6 +91,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Extension (cutadapt's option; a TODO of the reference): discard reads with more than COUNT 'N' "
                         "bases. If COUNT is a number between 0 and 1, it is interpreted as a fraction of the read "
                         "length. A pair is discarded if either read has too many N.")
+    p.add_argument("-M", "--max-length", type=int, default=None, metavar="LEN",
+                   help="Extension (cutadapt's option): discard reads longer than LEN after trimming. A pair is discarded "
+                        "if either read is too long. The counterpart of -m.")
+    p.add_argument("--max-ee", "--max-expected-errors", dest="max_ee", type=float, default=None, metavar="ERRORS",
+                   help="Extension (cutadapt's option): discard reads whose expected number of errors, the sum of "
+                        "10^(-Q/10) over the trimmed read's qualities, exceeds ERRORS. A pair is discarded if either "
+                        "read has too many. Needs an input with qualities.")
     p.add_argument("--info-file", type=str, default=None, metavar="FILE",
                    help="Extension (cutadapt's option; a TODO of the reference): write a tab-separated table of the "
                         "adapter matches of read 1 to FILE, one row per match, in input order; reads without a match "
@@ -158,6 +165,11 @@ def resolve_args(args):
     max_n = getattr(args, "max_n", None)
     if max_n is not None and not max_n >= 0:  # (NaN fails the comparison too)
         _fail(f"--max-n: the count must not be negative (got {max_n}).")
+    max_length, max_ee = getattr(args, "max_length", None), getattr(args, "max_ee", None)
+    if max_length is not None and max_length < 0:
+        _fail(f"-M/--max-length: the length must not be negative (got {max_length}).")
+    if max_ee is not None and not max_ee >= 0:  # (NaN fails the comparison too)
+        _fail(f"--max-ee: the number of expected errors must not be negative (got {max_ee}).")
     if getattr(args, "info_file", None):
         if args.demux_barcodes:
             _fail("--info-file cannot be combined with --demux-barcodes: the table form of the demultiplexing op has "
@@ -205,6 +217,8 @@ def settings_from_args(args) -> CutadaptConfig:
     st.force_anywhere = args.force_anywhere
     st.select_rule = abi.CS_SELECT_LEFTMOST if args.cutadapt_selection == "4" else abi.CS_SELECT_SCORE
     st.max_n = getattr(args, "max_n", None)
+    st.max_length = getattr(args, "max_length", None)
+    st.max_ee = getattr(args, "max_ee", None)
     if getattr(args, "demux", None) is not None:
         st.demux_barcodes = list(args.demux[1])
     return st
@@ -289,7 +303,7 @@ class _DeviceWorker(fanout.Worker):
         if self.tp.demux is not None:
             owned.append(fastq.PINNED.take(chunk.n))
             chunk.bc = owned[-1][: chunk.n]
-        if self.tp.max_n is not None:  # TooManyN flags of both mates
+        if self.tp.has_filters:  # the CS_X_* flags of both mates
             owned.append(fastq.PINNED.take(chunk.n))
             xf1 = owned[-1][: chunk.n]
             xf2 = None
@@ -436,6 +450,11 @@ def run_cutseq(args, argv=None):
     if settings.dry_run:
         dry_run(tp, barcode)
         return None
+    if tp.max_ee is not None:  # (standard input: the text path checks once it has seen the first byte)
+        from . import codec
+        for name in args.input_file:
+            if name != "-" and codec.sniff_input(name)[1] in (b">", b"#"):
+                _fail(f"--max-ee needs qualities: {name} is a FASTA file.")
     totals = None
     if getattr(args, "rank_spec", None):  # a child of --ranks: its share, its part files, its totals; the parent reports
         from . import ranks

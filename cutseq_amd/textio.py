@@ -583,10 +583,11 @@ class StreamWriter:
 
 
 class _Done:
-    __slots__ = ("n", "res", "out", "sizes", "counts", "info", "info_bytes")
+    __slots__ = ("n", "res", "out", "sizes", "counts", "info", "info_bytes", "discards")
 
-    def __init__(self, n, res, out, sizes=None, counts=None, info=None, info_bytes=0):
+    def __init__(self, n, res, out, sizes=None, counts=None, info=None, info_bytes=0, discards=None):
         self.n, self.res, self.out, self.sizes, self.counts = n, res, out, sizes, counts
+        self.discards = discards  # plans with -M / --max-n / --max-ee: pairs (too_long, too_many_n, too_many_ee) took
         self.info, self.info_bytes = info, info_bytes  # --info-file: the batch's table (a pinned buffer) and its size
 
 
@@ -660,6 +661,7 @@ class TextWorker(fanout.Worker):
         sizes = counts = None
         if self.bins:
             sizes, _, counts = self.text.routes(slot)
+        discards = self.text.discards(slot) if self.tp.has_filters else None
         out = [fastq.PINNED.take(max(int(res.out_bytes[m]), 1)) for m in range(2 if b2 is not None else 1)]
         info_buf, info_bytes = None, 0
         if self.info:
@@ -672,7 +674,7 @@ class TextWorker(fanout.Worker):
         b1.release()
         if b2 is not None:
             b2.release()
-        return _Done(b1.n, res, out, sizes, counts, info_buf, info_bytes)
+        return _Done(b1.n, res, out, sizes, counts, info_buf, info_bytes, discards)
 
     def close(self):
         try:
@@ -792,6 +794,8 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         compress = bool(names_all) and all(n != "-" and codec.container_of_name(n) == "gzip" for n in names_all) and os.environ.get("CUTSEQ_GPU_DEFLATE", "1") != "0"
         if r2 is not None and r1.fasta != r2.fasta:
             raise fastq.FastqFormatError("the two input files are in different formats (one FASTA, one FASTQ)")
+        if r1.fasta and tp.max_ee is not None:
+            raise fastq.FastqFormatError("--max-ee needs qualities: the input is FASTA")
         fasta_routes = output_formats(name_groups, has_qualities=not r1.fasta)
 
         def writer(name, precompressed):
@@ -861,7 +865,9 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
                 totals["routes"][q] += int(res.route_count[q])
         for m in range(2 if paired else 1):
             totals["written_bp"][m] += int(res.written_bp[m])
-        totals["too_many_n"] += int(res.n_too_many_n)
+        if item.discards is not None:
+            for key, pairs in zip(("too_long", "too_many_n", "too_many_ee"), item.discards):
+                totals[key] += pairs
         sizes = item.sizes if item.sizes is not None else res.route_bytes
         jobs = []
         for m in range(2 if paired else 1):

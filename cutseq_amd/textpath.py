@@ -161,6 +161,13 @@ class TextEngine:
         capi.check(self.L.cs_text_routes(self._h, slot, got.ctypes.data, raw.ctypes.data, count.ctypes.data))
         return got, raw, count
 
+    def discards(self, slot: int):
+        """Behind :meth:`wait`: the batch's pairs that (too_long, too_many_n, too_many_ee) discarded, each pair under
+        the first of the three filters that caught it."""
+        pairs = (C.c_uint32 * 3)()
+        capi.check(self.L.cs_text_discards(self._h, slot, C.byref(pairs)))
+        return int(pairs[0]), int(pairs[1]), int(pairs[2])
+
     def fetch(self, slot: int, dst1, dst2=None) -> None:
         """Output text of the batch into the caller's buffers (``res.out_bytes[m]`` bytes each); frees the slot."""
         capi.check(self.L.cs_text_fetch(self._h, slot, _address(dst1) or None, _address(dst2) or None))

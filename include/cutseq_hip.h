@@ -117,8 +117,11 @@ enum {
 
 /* per-read extra flag bits (cs_reads.xflags; cs_result.flags has no free bit) */
 enum {
-  CS_X_TOO_MANY_N = 0x01 /* TooManyN(count) of cs_plan_set_max_n is true for this mate (cutadapt --max-n) */
+  CS_X_TOO_MANY_N = 0x01, /* TooManyN(count) of cs_plan_set_max_n is true for this mate (cutadapt --max-n) */
+  CS_X_TOO_LONG = 0x02,   /* TooLong(length) of cs_plan_set_max_length is true for this mate (cutadapt -M)  */
+  CS_X_TOO_MANY_EE = 0x04 /* TooManyExpectedErrors(errors) of cs_plan_set_max_ee is true for this mate (cutadapt --max-ee) */
 };
+#define CS_X_COUNTS 3 /* CS_X_* bits: cs_xflag_counts_fetch returns one count per bit, bit 0 first */
 
 typedef struct cs_op {
   uint8_t kind;          /* CS_OP_*                                                   */
@@ -196,8 +199,8 @@ typedef struct cs_reads {
   cs_result *out;
   cs_cap2 *cap2; /* may be NULL */
   uint8_t *bc;   /* may be NULL; CS_OP_DEMUX: index of the barcode that matched, CS_DEMUX_NONE otherwise */
-  uint8_t *xflags; /* may be NULL; CS_X_* bits per read (0 where none applies); not written by a plan without
-                      cs_plan_set_max_n (its kernels are the ones without the filter) */
+  uint8_t *xflags; /* may be NULL; CS_X_* bits per read (0 where none applies); not written by a plan without any of
+                      cs_plan_set_max_n / _max_length / _max_ee (its kernels are the ones without the filters) */
 } cs_reads;
 
 typedef struct cs_plan cs_plan;
@@ -236,6 +239,29 @@ int cs_plan_set_demux_ops(cs_plan *plan, int mate, int op_index, const cs_op *op
  * The text path discards such a pair (pair filter "any") after TooShort and before IsUntrimmedAny.  Called before
  * cs_engine_create, like cs_plan_set_demux; never called: no filter.  CS_ERR_ARG for a negative or NaN count. */
 int cs_plan_set_max_n(cs_plan *plan, double count);
+
+/* cutadapt's -M / --max-length filter, TooLong(length), on both mates: a read whose final interval is longer than
+ * `length` bases (stop - start > length, 32 bits) gets CS_X_TOO_LONG.  Called like cs_plan_set_max_n. */
+int cs_plan_set_max_length(cs_plan *plan, uint32_t length);
+
+/* cutadapt's --max-ee / --max-expected-errors filter, TooManyExpectedErrors(errors), on both mates: a read gets
+ * CS_X_TOO_MANY_EE when expected_errors(qual[start:stop]) > errors, where
+ *     e = 0.0; for every quality byte b, left to right: e += T[b];   T[b] = pow(10, -(b - 33) / 10.0)
+ * in IEEE double.  The device adds in exactly that order, one lane per read, so the sum equals the loop's to the bit
+ * (T is computed once on the host and uploaded with the plan; indexed by the raw byte, 0..255).  The comparison is
+ * strict, an empty interval has 0 expected errors, INFINITY never fires.  A mate without qualities (cs_reads.qual ==
+ * NULL) never gets the bit.  Called like cs_plan_set_max_n; CS_ERR_ARG for a negative or NaN bound.
+ *
+ * Order of the filter steps on the text path and in the host formatter (pair filter "any" throughout): TooShort ->
+ * TooLong -> TooManyN -> TooManyExpectedErrors -> IsUntrimmedAny -> sink.  The three in the middle discard the pair:
+ * it is written nowhere, counted in no route, and counted under the first of them that catches it. */
+int cs_plan_set_max_ee(cs_plan *plan, double errors);
+
+/* For a caller that writes the reads reverse-complemented (cs_text_params.reverse_complement, csh_format_chunk; the
+ * reference's ReverseComplementConverter is a modifier, so cutadapt's filters see the read turned round): reversed != 0
+ * makes the expected-error sum run over qual[stop - 1] down to qual[start], the left-to-right order of the read as it
+ * is written.  The other two filters do not depend on the orientation.  Default 0. */
+int cs_plan_set_ee_reversed(cs_plan *plan, int reversed);
 
 /* One engine per GPU (one per process in the multi-GPU layout; replaces
  * make_runner(inpaths, cores=threads), run.py:436,753). Uploads the op tables, owns a
@@ -278,6 +304,12 @@ int cs_sync(cs_engine *eng, uint32_t slot);
  * stats[0] = mate 1, stats[1] = mate 2.  Ordered behind every launch the engine has issued so far (on
  * any stream) and synchronous. */
 int cs_stats_fetch(cs_engine *eng, cs_stats stats[2], int reset);
+
+/* How many reads of each mate got each CS_X_* bit: counts[mate][k] for bit 1 << k (TooManyN, TooLong,
+ * TooManyExpectedErrors).  Per mate and per bit: not pair counts, and no precedence between the filters.  Ordered and
+ * synchronous like cs_stats_fetch.  counts[m][0] is cs_stats.n_too_many_n; `reset` zeroes all six counters (that word
+ * of cs_stats included), and cs_stats_fetch's reset leaves the other four alone. */
+int cs_xflag_counts_fetch(cs_engine *eng, uint64_t counts[2][CS_X_COUNTS], int reset);
 
 /* Timing of the last cs_trim_device / cs_trim_device_pipelined call, measured with HIP events recorded
  * around each kernel on the stream it ran on (ms, the two kernels added).  Synchronises on the stop event. */
@@ -360,7 +392,8 @@ typedef struct cs_text_result {
   uint32_t max_len;           /* longest read of the batch                                                      */
   uint32_t n_records;
   uint32_t route_count[3];    /* records (pairs) per route (n_bins > 0: [0] = all barcodes together; likewise below) */
-  uint32_t n_too_many_n;      /* pairs discarded by TooManyN (cs_plan_set_max_n), in no route                    */
+  uint32_t n_too_many_n;      /* pairs discarded by TooManyN (cs_plan_set_max_n), in no route; cs_text_discards has
+                                 this and the other two discarding filters' counts                                */
   uint64_t route_bytes[3][2]; /* [route][mate]                                                                  */
   uint64_t out_bytes[2];      /* per mate: sum over the routes = what cs_text_fetch copies                      */
   uint64_t written_bp[2];     /* per mate: bases of the records of route 0 (cutadapt's written_bp)              */
@@ -386,6 +419,10 @@ int cs_text_wait(cs_text *t, uint32_t slot, cs_text_result *res);
  * delivers them (gzip members if compress), text_bytes[route][mate] uncompressed, count[route] records.  The streams of
  * a mate lie in route order in the fetched buffer.  Any of the three pointers may be NULL. */
 int cs_text_routes(cs_text *t, uint32_t slot, uint64_t *bytes, uint64_t *text_bytes, uint32_t *count);
+/* Behind cs_text_wait: the pairs (single-end: reads) of the slot's batch that the discarding filters took, by
+ * precedence: pairs[0] TooLong, pairs[1] TooManyN (= cs_text_result.n_too_many_n), pairs[2] TooManyExpectedErrors.
+ * A pair that several of them catch counts once, under the first in that order; one that TooShort catches in none. */
+int cs_text_discards(cs_text *t, uint32_t slot, uint32_t pairs[3]);
 /* Copies the output text (res->out_bytes[m] bytes per mate) into the caller's buffers and blocks until it is
  * there; the slot is free for the next cs_text_submit afterwards.  dst2 == NULL for single-end. */
 int cs_text_fetch(cs_text *t, uint32_t slot, void *dst1, void *dst2);

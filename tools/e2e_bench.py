@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Tier E through the product CLI, in-process, with start-up amortised.
 
-  python tools/e2e_bench.py [pairs] [workdir] [--forms plain_warm,plain_to_gz] [--tree DIR] [--keep]
+  python tools/e2e_bench.py [pairs] [workdir] [--forms plain_warm,plain_to_gz] [--tree DIR] [--keep] [--extra='-M 100']
 
 Writes a synthetic paired data set once (plain text and multi-member gzip), then runs
 ``cutseq_amd.run.main`` on it: plain -> plain twice (the second run has warm buffers and page cache),
@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--forms", type=lambda v: v.split(","), default=None)
     ap.add_argument("--tree", default=None)
     ap.add_argument("--keep", action="store_true")
+    ap.add_argument("--extra", type=lambda v: v.split(), default=[],
+                    help="more command-line options for every run, e.g. --extra='-M 100 --max-ee 1'")
     opts = ap.parse_args()
     if opts.tree:
         sys.path.insert(0, str(Path(opts.tree).resolve()))
@@ -46,7 +48,7 @@ def main():
     need = n * 2 * 340 * 3
     if free < need:
         raise SystemExit(f"{work}: {free >> 20} MiB free, {need >> 20} MiB needed for {n} pairs")
-    out = {"pairs": n, "workdir": str(work), "cpus": len(os.sched_getaffinity(0))}
+    out = {"pairs": n, "workdir": str(work), "cpus": len(os.sched_getaffinity(0)), "extra": opts.extra}
     from cutseq_amd import codec, fastq, run as cli
     out["tree"] = str(Path(cli.__file__).resolve().parents[1])
     have = opts.keep and all((work / f"{stem}_R{m}.{end}").exists() for m in (1, 2) for stem, end in (("syn", "fastq.gz"), ("plain", "fastq")))
@@ -73,7 +75,7 @@ def main():
                 f.unlink()
         t0 = time.perf_counter()
         try:
-            cli.main(["-A", "TAKARAV3", "--trim-polyA"] + inputs + outputs)
+            cli.main(["-A", "TAKARAV3", "--trim-polyA"] + opts.extra + inputs + outputs)
         except SystemExit as exc:  # pragma: no cover
             if exc.code:
                 raise

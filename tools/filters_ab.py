@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Cost of the filters of the final interval (-M, --max-n, --max-ee) on the bench configuration: device-generated
+config-3 pairs (TAKARAV3, 150 nt), pipelined cs_trim_device calls as bench.py issues them; the plan without a filter,
+with each filter alone and with all three, alternating.  Prints one JSON line per leg and a summary line: M pairs/s,
+scan and resolve kernel ms per call, reads flagged per call and mate.
+
+  python tools/filters_ab.py [--pairs 20000000] [--steps 20] [--warmup 5] [--rounds 3] [--max-length 100] [--max-ee 1]
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+import torch  # noqa: E402
+
+from cutseq_amd import abi, synth, workloads  # noqa: E402
+from cutseq_amd.engine import TrimEngine  # noqa: E402
+
+
+def leg(d, n, stride, filters, steps, warmup, with_xflags):
+    tp = workloads.make_plan("config3")
+    tp.max_length, tp.max_n, tp.max_ee = filters.get("max_length"), filters.get("max_n"), filters.get("max_ee")
+    dev = torch.device("cuda:0")
+    sets = []
+    for _ in range(3):
+        o1 = torch.empty((n, 8), dtype=torch.uint8, device=dev)
+        o2 = torch.empty((n, 8), dtype=torch.uint8, device=dev)
+        x1 = torch.empty(n, dtype=torch.uint8, device=dev) if with_xflags else None
+        x2 = torch.empty(n, dtype=torch.uint8, device=dev) if with_xflags else None
+        r1 = abi.cs_reads(d["seq1"].data_ptr(), d["qual1"].data_ptr(), d["len1"].data_ptr(), o1.data_ptr(), None, None,
+                          x1.data_ptr() if x1 is not None else None)
+        r2 = abi.cs_reads(d["seq2"].data_ptr(), d["qual2"].data_ptr(), d["len2"].data_ptr(), o2.data_ptr(), None, None,
+                          x2.data_ptr() if x2 is not None else None)
+        sets.append((r1, r2, o1, o2, x1, x2))
+    with TrimEngine(tp, device=0, slots=0) as eng:
+        stream = torch.cuda.Stream(device=dev)
+        sh = C.c_void_p(stream.cuda_stream)
+        for i in range(warmup):
+            eng.trim_device(sets[i % 3][0], sets[i % 3][1], n, stride, stream=sh, pipelined=True)
+        eng.join(sh)
+        torch.cuda.synchronize(dev)
+        eng.stats(reset=True)
+        eng.xflag_counts(reset=True)
+        eng.kernel_time_totals(reset=True)
+        t0 = time.perf_counter()
+        for i in range(steps):
+            eng.trim_device(sets[i % 3][0], sets[i % 3][1], n, stride, stream=sh, pipelined=True)
+        eng.join(sh)
+        torch.cuda.synchronize(dev)
+        elapsed = time.perf_counter() - t0
+        calls, scan_ms, resolve_ms = eng.kernel_time_totals()
+        c1, c2 = eng.xflag_counts()
+    return {"filters": filters, "mpairs_s": n * steps / elapsed / 1e6, "scan_ms": scan_ms / calls,
+            "resolve_ms": resolve_ms / calls, "flagged": {k: [c1[k] // steps, c2[k] // steps] for k in c1}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=20_000_000)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--max-n", type=float, default=0.0)
+    ap.add_argument("--max-length", type=int, default=100)
+    ap.add_argument("--max-ee", type=float, default=1.0)
+    ap.add_argument("--xflags", action="store_true", help="also write cs_reads.xflags (the text path does)")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    n = args.pairs
+    stride = synth._stride_for(150)
+    names = ("seq1", "qual1", "len1", "seq2", "qual2", "len2")
+    d = {k: torch.empty((n,) if k.startswith("len") else (n, stride),
+                        dtype=torch.int16 if k.startswith("len") else torch.uint8, device=dev) for k in names}
+    assert workloads.fill_device("config3", n, [d[k].data_ptr() for k in names]) == stride
+    torch.cuda.synchronize(dev)
+    legs = (("off", {}), ("max_n", {"max_n": args.max_n}), ("max_length", {"max_length": args.max_length}),
+            ("max_ee", {"max_ee": args.max_ee}),
+            ("all", {"max_length": args.max_length, "max_n": args.max_n, "max_ee": args.max_ee}))
+    res = {key: [] for key, _ in legs}
+    for _ in range(args.rounds):
+        for key, filters in legs:
+            r = leg(d, n, stride, filters, args.steps, args.warmup, args.xflags)
+            res[key].append(r)
+            print(json.dumps({"leg": key, **r}), flush=True)
+    med = {k: {f: statistics.median(x[f] for x in v) for f in ("mpairs_s", "scan_ms", "resolve_ms")} for k, v in res.items()}
+    slow = {k: round(100.0 * (1.0 - med[k]["mpairs_s"] / med["off"]["mpairs_s"]), 2) for k in med if k != "off"}
+    print(json.dumps({"summary": med, "slowdown_pct": slow, "pairs": n, "steps": args.steps, "rounds": args.rounds}),
+          flush=True)
+
+
+if __name__ == "__main__":
+    main()

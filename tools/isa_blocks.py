@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Basic blocks of one kernel in a gfx950 assembly dump, biggest first: VALU / SALU / LDS / VMEM counts.
     hipcc -O3 --offload-arch=gfx950 -std=c++17 -Iinclude -S --cuda-device-only -o x.s cutseq_amd/csrc/cutseq_hip.hip
-    python3 tools/isa_blocks.py x.s _ZN5csdev11trim_kernelILb1ELb0ELi0ELb0EEEvNS_5KArgsE [min_instructions]
+    python3 tools/isa_blocks.py x.s _ZN5csdev11trim_kernelILb1ELb0ELi0ELi0EEEvNS_5KArgsE [min_instructions]
 """
 import re
 import sys

@@ -10,4 +10,4 @@ mkdir -p /tmp/isa
   ${KRES_FLAGS} -o /tmp/isa/x.s cutseq_amd/csrc/cutseq_hip.hip 2>&1 | grep -E -A9 "Function Name: .*(${KRES_KERNELS:-trim_kernelILb1ELb0ELi[01]})" |
   grep -E "Function Name|VGPRs|Scratch|Occupancy|Spill" | sed 's/.*remark: //; s/ \[-Rpass.*//'
 [ -n "${KRES_KERNELS}" ] && exit 0
-python3 tools/isa_blocks.py /tmp/isa/x.s _ZN5csdev11trim_kernelILb1ELb0ELi0ELb0EEEvNS_5KArgsE ${1:-150}
+python3 tools/isa_blocks.py /tmp/isa/x.s _ZN5csdev11trim_kernelILb1ELb0ELi0ELi0EEEvNS_5KArgsE ${1:-150}
