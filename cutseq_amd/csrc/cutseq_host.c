@@ -364,17 +364,105 @@ static void rc_init(void) {
   rc_ready = 1;
 }
 
-static uint8_t *emit(uint8_t *o, const uint8_t *id, int32_t idl, const uint8_t *tag1, int32_t t1, const uint8_t *tag2,
-                     int32_t t2, int has_umi, const uint8_t *seq, const uint8_t *qual, int32_t s, int32_t e, int rc) {
+/* One mate's share of a parsed chunk (csh_fastq_parse) with the device's results; xflags (may be NULL): per-read
+ * CS_X_* flags */
+typedef struct csh_mate {
+  const uint8_t *raw;
+  const int64_t *name_off;
+  const int32_t *name_len;
+  const uint8_t *seq, *qual;
+  const csh_result *res;
+  const uint8_t *xflags;
+} csh_mate;
+
+/* mate[1] is read only when csh_format_params.paired; cap2 (single-end, may be NULL): the second capture; bin
+ * (n_bins > 0): barcode index per record */
+typedef struct csh_chunk {
+  int64_t n;
+  uint32_t stride;
+  csh_mate mate[2];
+  const csh_cap2 *cap2;
+  const uint8_t *bin;
+  int32_t n_bins;
+} csh_chunk;
+
+/* binned, bin_off ([2][n_bins + 1]) and bin_counts ([n_bins]) are read only when n_bins > 0 */
+typedef struct csh_format_out {
+  uint8_t *out[3][2];
+  int64_t out_len[3][2];
+  int64_t counts[3];
+  uint8_t *binned[2];
+  int64_t *bin_off;
+  int64_t *bin_counts;
+} csh_format_out;
+
+/* for a caller that mirrors the three argument structs (ctypes): a library built from other definitions is told apart */
+void csh_format_struct_sizes(int64_t sizes[3]) {
+  sizes[0] = sizeof(csh_format_params);
+  sizes[1] = sizeof(csh_chunk);
+  sizes[2] = sizeof(csh_format_out);
+}
+
+/* The discarding filters (cs_reads.xflags: CS_X_TOO_MANY_N 1, CS_X_TOO_LONG 2, CS_X_TOO_MANY_EE 4), pair filter "any":
+ * behind TooShort, in front of IsUntrimmedAny.  Whichever of them catches the pair, it goes nowhere (which one it
+ * counts under is report.account_chunk's business). */
+#define CSH_ROUTE_DISCARD (-1)
+static int route_of(const csh_format_params *fp, unsigned flags, unsigned xflags) {
+  if (flags & fp->flag_too_short) return 1;
+  if (xflags & 7u) return CSH_ROUTE_DISCARD;
+  return (fp->untrimmed_filter && (flags & fp->flag_untrimmed)) ? 2 : 0;
+}
+
+/* What the header work makes of record i: the stream it goes to, each mate's id, and the two captures that both
+ * mates' names carry (paired: one of either mate; single-end: the read's own two). */
+typedef struct {
+  int stream;
+  const uint8_t *id[2], *tag[2];
+  int32_t idl[2], tagl[2];
+} csh_rec;
+
+/* -> 0, or -1 when the mates' ids differ.  Streams: 0 trimmed, 1 short, 2 untrimmed; with bins a trimmed record goes
+ * to 3 + its bin, or to 2 when its bin is out of range (no barcode), whatever its flags say. */
+static int prep_record(const csh_format_params *fp, const csh_chunk *ck, int64_t i, csh_rec *r) {
+  const csh_mate *m1 = &ck->mate[0], *m2 = &ck->mate[1];
+  const uint8_t *nm1 = m1->raw + m1->name_off[i], *s1 = m1->seq + (size_t)i * ck->stride;
+  int32_t nl1 = strip_suffixes(nm1, m1->name_len[i], fp->suffix1), off;
+  read_id(nm1, nl1, &off, &r->idl[0]);
+  r->id[0] = nm1 + off;
+  r->tag[0] = s1 + m1->res[i].cap_off;
+  r->tagl[0] = m1->res[i].cap_len;
+  unsigned flags = m1->res[i].flags, xflags = m1->xflags ? m1->xflags[i] : 0u;
+  if (fp->paired) {
+    const uint8_t *nm2 = m2->raw + m2->name_off[i];
+    int32_t nl2 = strip_suffixes(nm2, m2->name_len[i], fp->suffix2);
+    if (!ids_match(nm1, nl1, nm2, nl2)) return -1;
+    read_id(nm2, nl2, &off, &r->idl[1]);
+    r->id[1] = nm2 + off;
+    r->tag[1] = m2->seq + (size_t)i * ck->stride + m2->res[i].cap_off;
+    r->tagl[1] = m2->res[i].cap_len;
+    flags |= m2->res[i].flags;
+    if (m2->xflags) xflags |= m2->xflags[i];
+  } else {
+    r->tag[1] = s1 + (ck->cap2 ? ck->cap2[i].off : 0);
+    r->tagl[1] = ck->cap2 ? ck->cap2[i].len : 0;
+  }
+  r->stream = route_of(fp, flags, xflags);
+  if (r->stream == 0 && ck->n_bins) r->stream = ck->bin[i] < ck->n_bins ? 3 + ck->bin[i] : 2;
+  return 0;
+}
+
+/* Mate m of a record as FASTQ text: bases [s, e) of its row, reverse-complemented with rc. */
+static uint8_t *emit(uint8_t *o, const csh_rec *r, int m, int has_umi, const uint8_t *seq, const uint8_t *qual,
+                     int32_t s, int32_t e, int rc) {
   *o++ = '@';
-  memcpy(o, id, (size_t)idl);
-  o += idl;
+  memcpy(o, r->id[m], (size_t)r->idl[m]);
+  o += r->idl[m];
   if (has_umi) {
     *o++ = '_';
-    memcpy(o, tag1, (size_t)t1);
-    o += t1;
-    memcpy(o, tag2, (size_t)t2);
-    o += t2;
+    memcpy(o, r->tag[0], (size_t)r->tagl[0]);
+    o += r->tagl[0];
+    memcpy(o, r->tag[1], (size_t)r->tagl[1]);
+    o += r->tagl[1];
   }
   *o++ = '\n';
   int32_t L = e - s;
@@ -397,186 +485,75 @@ static uint8_t *emit(uint8_t *o, const uint8_t *id, int32_t idl, const uint8_t *
   return o;
 }
 
-/* The discarding filters (cs_reads.xflags: CS_X_TOO_MANY_N 1, CS_X_TOO_LONG 2, CS_X_TOO_MANY_EE 4), pair filter "any":
- * behind TooShort, in front of IsUntrimmedAny.  Whichever of them catches the pair, it goes nowhere (which one it
- * counts under is report.account_chunk's business).  xf1 / xf2 NULL: no such filter. */
-#define CSH_ROUTE_DISCARD (-1)
-static int route_of(const csh_format_params *fp, unsigned flags, unsigned xflags) {
-  if (flags & fp->flag_too_short) return 1;
-  if (xflags & 7u) return CSH_ROUTE_DISCARD;
-  return (fp->untrimmed_filter && (flags & fp->flag_untrimmed)) ? 2 : 0;
+/* The bytes emit writes for the same arguments: "@id[_tags]\n" + bases + "\n+\n" + qualities + "\n".  Nothing else
+ * knows a record's size. */
+static int64_t record_bytes(const csh_rec *r, int m, int has_umi, int32_t s, int32_t e) {
+  return 2 + r->idl[m] + (has_umi ? 1 + r->tagl[0] + r->tagl[1] : 0) + 2 * (int64_t)(e - s) + 4;
 }
 
-/* Format one chunk.  out[route][mate] are caller-allocated buffers (capacity: raw chunk bytes +
- * 260 per record is always enough); out_len[route][mate] receives the bytes written and
- * counts[route] the records (pairs).  Routes: 0 trimmed, 1 short, 2 untrimmed.  xf1 / xf2 (may be NULL): per-read
- * CS_X_* flags; the pairs TooLong / TooManyN / TooManyExpectedErrors take are written nowhere and counted in no route (n - the sum of counts[]).
- * Returns 0, or -(record index + 1) when the mates' ids differ. */
-int64_t csh_format_chunk(const csh_format_params *fp, int64_t n, uint32_t stride, const uint8_t *raw1,
-                         const int64_t *name_off1, const int32_t *name_len1, const uint8_t *seq1,
-                         const uint8_t *qual1, const csh_result *res1, const csh_cap2 *cap2, const uint8_t *raw2,
-                         const int64_t *name_off2, const int32_t *name_len2, const uint8_t *seq2,
-                         const uint8_t *qual2, const csh_result *res2, uint8_t *out[3][2], int64_t out_len[3][2],
-                         int64_t counts[3], const uint8_t *xf1, const uint8_t *xf2) {
+#define CSH_MAX_BINS 255
+
+/* Format one chunk: header rewriting, pair check, routing, FASTQ text.  out->out[route][mate] are the caller's buffers
+ * for the routes 0 trimmed, 1 short, 2 untrimmed; out_len[route][mate] receives the bytes written and counts[route]
+ * the records (pairs).  The pairs a discarding filter takes (xflags) are written nowhere and counted nowhere: n - the
+ * sum of all counts.
+ *
+ * With ck->n_bins > 0 (demultiplexed output, BASELINE.json config 5) route 0 stays empty: its records are split by
+ * ck->bin[i].  The bins of one mate lie back to back in out->binned[mate], bin b at
+ * [bin_off[mate * (n_bins + 1) + b], bin_off[.. + b + 1]), bin_counts[b] its records.  That takes two passes, sizes
+ * (record_bytes) then bytes (emit); a chunk without bins is one pass.
+ *
+ * Capacity: every buffer of mate m, out[.][m] and binned[m], holds at least the bytes of mate m's raw text
+ * + 528 per record + 16.  A record's output is its id and twice its interval, all of which the raw text holds with
+ * as many separators, + "_" and two captures (<= 511 bytes) where the input had none.
+ *
+ * Returns 0, -(i + 1) for the first pair i whose ids differ, -(n + 1) for arguments that cannot be served. */
+int64_t csh_format_chunk(const csh_format_params *fp, const csh_chunk *ck, csh_format_out *out) {
   if (!rc_ready) rc_init();
-  uint8_t *w[3][2];
-  for (int r = 0; r < 3; r++) {
-    counts[r] = 0;
-    for (int m = 0; m < 2; m++) w[r][m] = out[r][m];
-  }
-  for (int64_t i = 0; i < n; i++) {
-    unsigned xflags = xf1 ? xf1[i] : 0u;
-    const uint8_t *nm1 = raw1 + name_off1[i];
-    int32_t nl1 = strip_suffixes(nm1, name_len1[i], fp->suffix1);
-    int32_t id1o, id1l;
-    read_id(nm1, nl1, &id1o, &id1l);
-    const uint8_t *s1 = seq1 + (size_t)i * stride, *q1 = qual1 + (size_t)i * stride;
-    unsigned flags = res1[i].flags;
-    if (!fp->paired) {
-      int route = route_of(fp, flags, xflags);
-      if (route == CSH_ROUTE_DISCARD) continue;
-      const uint8_t *t2 = cap2 ? s1 + cap2[i].off : NULL;
-      w[route][0] = emit(w[route][0], nm1 + id1o, id1l, s1 + res1[i].cap_off, res1[i].cap_len, t2,
-                         cap2 ? cap2[i].len : 0, fp->has_umi, s1, q1, res1[i].start, res1[i].stop,
-                         fp->reverse_complement);
-      counts[route]++;
-      continue;
+  const int64_t n = ck->n;
+  const int n_bins = ck->n_bins, mates = fp->paired ? 2 : 1, has_umi = fp->has_umi;
+  const int rc = !fp->paired && fp->reverse_complement;
+  if (n_bins < 0 || n_bins > CSH_MAX_BINS) return -(n + 1);
+  if (n_bins && !(ck->bin && out->bin_off && out->bin_counts && out->binned[0] && out->binned[mates - 1])) return -(n + 1);
+  const int64_t per_mate = n_bins + 1;
+  csh_rec r;
+  if (n_bins) { /* pass 1: bytes per bin and mate, accumulated at bin_off[.. + b + 1], then turned into offsets */
+    memset(out->bin_off, 0, (size_t)(2 * per_mate) * sizeof(int64_t));
+    memset(out->bin_counts, 0, (size_t)n_bins * sizeof(int64_t));
+    for (int64_t i = 0; i < n; i++) {
+      if (prep_record(fp, ck, i, &r)) return -(i + 1);
+      if (r.stream < 3) continue;
+      for (int m = 0; m < mates; m++) {
+        const csh_result *res = &ck->mate[m].res[i];
+        out->bin_off[m * per_mate + r.stream - 2] += record_bytes(&r, m, has_umi, res->start, res->stop);
+      }
+      out->bin_counts[r.stream - 3]++;
     }
-    const uint8_t *nm2 = raw2 + name_off2[i];
-    int32_t nl2 = strip_suffixes(nm2, name_len2[i], fp->suffix2);
-    if (!ids_match(nm1, nl1, nm2, nl2)) return -(i + 1);
-    int32_t id2o, id2l;
-    read_id(nm2, nl2, &id2o, &id2l);
-    const uint8_t *s2 = seq2 + (size_t)i * stride, *q2 = qual2 + (size_t)i * stride;
-    flags |= res2[i].flags;
-    if (xf2) xflags |= xf2[i];
-    int route = route_of(fp, flags, xflags);
-    if (route == CSH_ROUTE_DISCARD) continue;
-    w[route][0] = emit(w[route][0], nm1 + id1o, id1l, s1 + res1[i].cap_off, res1[i].cap_len, s2 + res2[i].cap_off,
-                       res2[i].cap_len, fp->has_umi, s1, q1, res1[i].start, res1[i].stop, 0);
-    w[route][1] = emit(w[route][1], nm2 + id2o, id2l, s1 + res1[i].cap_off, res1[i].cap_len, s2 + res2[i].cap_off,
-                       res2[i].cap_len, fp->has_umi, s2, q2, res2[i].start, res2[i].stop, 0);
-    counts[route]++;
+    for (int m = 0; m < mates; m++)
+      for (int b = 0; b < n_bins; b++) out->bin_off[m * per_mate + b + 1] += out->bin_off[m * per_mate + b];
   }
-  for (int r = 0; r < 3; r++)
-    for (int m = 0; m < 2; m++) out_len[r][m] = w[r][m] - out[r][m];
-  return 0;
-}
-
-
-/* ---- demultiplexed output (extension, BASELINE.json config 5): the trimmed route split by barcode -------------
- * Like csh_format_chunk, but every record of route 0 goes to the bin bin[i] (< n_bins) names: the bins of one
- * mate lie back to back in out_binned[mate] (capacity as for a route buffer), bin b at
- * [bin_off[mate * (n_bins + 1) + b], bin_off[.. + b + 1]).  Two passes: sizes, then bytes.  Records whose
- * bin is out of range (no barcode) are written to route 2 whatever their flags say.
- * bin_counts[b] receives the records (pairs) of bin b, counts[1], counts[2] those of the other routes.  xf1 / xf2 as
- * for csh_format_chunk: a discarding filter takes a pair before the untrimmed and barcode routes see it. */
-typedef struct {
-  int route;
-  int32_t id1o, id1l, id2o, id2l, nl1, nl2;
-} csh_prep;
-
-static int prep_record(const csh_format_params *fp, int64_t i, const uint8_t *raw1, const int64_t *name_off1,
-                       const int32_t *name_len1, const csh_result *res1, const uint8_t *raw2, const int64_t *name_off2,
-                       const int32_t *name_len2, const csh_result *res2, const uint8_t *xf1, const uint8_t *xf2,
-                       csh_prep *p) {
-  const uint8_t *nm1 = raw1 + name_off1[i];
-  p->nl1 = strip_suffixes(nm1, name_len1[i], fp->suffix1);
-  read_id(nm1, p->nl1, &p->id1o, &p->id1l);
-  unsigned flags = res1[i].flags, xflags = xf1 ? xf1[i] : 0u;
-  if (fp->paired) {
-    const uint8_t *nm2 = raw2 + name_off2[i];
-    p->nl2 = strip_suffixes(nm2, name_len2[i], fp->suffix2);
-    if (!ids_match(nm1, p->nl1, nm2, p->nl2)) return -1;
-    read_id(nm2, p->nl2, &p->id2o, &p->id2l);
-    flags |= res2[i].flags;
-    if (xf2) xflags |= xf2[i];
-  }
-  p->route = route_of(fp, flags, xflags);
-  return 0;
-}
-
-int64_t csh_format_chunk_bins(const csh_format_params *fp, int64_t n, uint32_t stride, const uint8_t *raw1,
-                              const int64_t *name_off1, const int32_t *name_len1, const uint8_t *seq1,
-                              const uint8_t *qual1, const csh_result *res1, const csh_cap2 *cap2, const uint8_t *raw2,
-                              const int64_t *name_off2, const int32_t *name_len2, const uint8_t *seq2,
-                              const uint8_t *qual2, const csh_result *res2, const uint8_t *bin, int32_t n_bins,
-                              uint8_t *out_binned[2], int64_t *bin_off, int64_t *bin_counts, uint8_t *out[3][2],
-                              int64_t out_len[3][2], int64_t counts[3], const uint8_t *xf1, const uint8_t *xf2) {
-  if (!rc_ready) rc_init();
-  if (!bin || n_bins < 1 || n_bins > 255) return -(n + 1);
-  const int mates = fp->paired ? 2 : 1;
-  const int64_t stride_off = n_bins + 1;
+  uint8_t *w[2][3 + CSH_MAX_BINS]; /* write position per mate and stream */
   for (int m = 0; m < 2; m++)
-    for (int b = 0; b <= n_bins; b++) bin_off[m * stride_off + b] = 0;
-  for (int b = 0; b < n_bins; b++) bin_counts[b] = 0;
-  /* pass 1: bytes per bin and mate (accumulated at bin_off[.. + b + 1]) */
-  for (int64_t i = 0; i < n; i++) {
-    csh_prep p;
-    if (prep_record(fp, i, raw1, name_off1, name_len1, res1, raw2, name_off2, name_len2, res2, xf1, xf2, &p))
-      return -(i + 1);
-    if (p.route != 0 || bin[i] >= n_bins) continue;
-    int32_t tag = 0;
-    if (fp->has_umi) tag = 1 + res1[i].cap_len + (fp->paired ? res2[i].cap_len : (cap2 ? cap2[i].len : 0));
-    bin_off[bin[i] + 1] += p.id1l + 2 * (int64_t)(res1[i].stop - res1[i].start) + 6 + tag;
-    if (fp->paired) bin_off[stride_off + bin[i] + 1] += p.id2l + 2 * (int64_t)(res2[i].stop - res2[i].start) + 6 + tag;
-    bin_counts[bin[i]]++;
-  }
+    for (int s = 0; s < 3; s++) w[m][s] = out->out[s][m];
   for (int m = 0; m < mates; m++)
-    for (int b = 0; b < n_bins; b++) bin_off[m * stride_off + b + 1] += bin_off[m * stride_off + b];
-  /* pass 2: bytes */
-  uint8_t *w[3][2];
-  for (int r = 0; r < 3; r++) {
-    counts[r] = 0;
-    for (int m = 0; m < 2; m++) w[r][m] = out[r][m];
-  }
-  int64_t *cur = (int64_t *)malloc((size_t)(2 * stride_off) * sizeof(int64_t));
-  if (!cur) return -(n + 1);
-  for (int64_t j = 0; j < 2 * stride_off; j++) cur[j] = bin_off[j];
+    for (int b = 0; b < n_bins; b++) w[m][3 + b] = out->binned[m] + out->bin_off[m * per_mate + b];
+  for (int s = 0; s < 3; s++) out->counts[s] = 0;
   for (int64_t i = 0; i < n; i++) {
-    csh_prep p;
-    (void)prep_record(fp, i, raw1, name_off1, name_len1, res1, raw2, name_off2, name_len2, res2, xf1, xf2, &p);
-    int route = p.route;
-    if (route == CSH_ROUTE_DISCARD) continue;
-    if (route == 0 && bin[i] >= n_bins) route = 2;
-    const uint8_t *nm1 = raw1 + name_off1[i];
-    const uint8_t *s1 = seq1 + (size_t)i * stride, *q1 = qual1 + (size_t)i * stride;
-    const uint8_t *t2;
-    int32_t t2l;
-    const uint8_t *s2 = NULL, *q2 = NULL;
-    if (fp->paired) {
-      s2 = seq2 + (size_t)i * stride;
-      q2 = qual2 + (size_t)i * stride;
-      t2 = s2 + res2[i].cap_off;
-      t2l = res2[i].cap_len;
-    } else {
-      t2 = cap2 ? s1 + cap2[i].off : NULL;
-      t2l = cap2 ? cap2[i].len : 0;
+    if (prep_record(fp, ck, i, &r)) return -(i + 1);
+    if (r.stream == CSH_ROUTE_DISCARD) continue;
+    for (int m = 0; m < mates; m++) {
+      const csh_mate *mt = &ck->mate[m];
+      w[m][r.stream] = emit(w[m][r.stream], &r, m, has_umi, mt->seq + (size_t)i * ck->stride,
+                            mt->qual + (size_t)i * ck->stride, mt->res[i].start, mt->res[i].stop, rc);
     }
-    uint8_t *o1 = route == 0 ? out_binned[0] + cur[bin[i]] : w[route][0];
-    uint8_t *e1 = emit(o1, nm1 + p.id1o, p.id1l, s1 + res1[i].cap_off, res1[i].cap_len, t2, t2l, fp->has_umi, s1, q1,
-                       res1[i].start, res1[i].stop, fp->paired ? 0 : fp->reverse_complement);
-    if (route == 0)
-      cur[bin[i]] += e1 - o1;
-    else
-      w[route][0] = e1;
-    if (fp->paired) {
-      const uint8_t *nm2 = raw2 + name_off2[i];
-      uint8_t *o2 = route == 0 ? out_binned[1] + cur[stride_off + bin[i]] : w[route][1];
-      uint8_t *e2 = emit(o2, nm2 + p.id2o, p.id2l, s1 + res1[i].cap_off, res1[i].cap_len, t2, t2l, fp->has_umi, s2, q2,
-                         res2[i].start, res2[i].stop, 0);
-      if (route == 0)
-        cur[stride_off + bin[i]] += e2 - o2;
-      else
-        w[route][1] = e2;
-    }
-    if (route != 0) counts[route]++;
+    if (r.stream < 3) out->counts[r.stream]++;
   }
-  free(cur);
-  counts[0] = 0;
-  for (int b = 0; b < n_bins; b++) counts[0] += bin_counts[b];
-  for (int r = 0; r < 3; r++)
-    for (int m = 0; m < 2; m++) out_len[r][m] = w[r][m] - out[r][m];
+  for (int s = 0; s < 3; s++)
+    for (int m = 0; m < 2; m++) out->out_len[s][m] = w[m][s] - out->out[s][m];
+  /* every bin ends where pass 1 said the next one starts */
+  for (int m = 0; m < mates; m++)
+    for (int b = 0; b < n_bins; b++)
+      if (w[m][3 + b] != out->binned[m] + out->bin_off[m * per_mate + b + 1]) return -(n + 1);
   return 0;
 }
 

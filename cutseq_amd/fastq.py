@@ -41,6 +41,20 @@ class _FormatParams(C.Structure):
     ]
 
 
+class _Mate(C.Structure):  # csh_mate
+    _fields_ = [(name, C.c_void_p) for name in ("raw", "name_off", "name_len", "seq", "qual", "res", "xflags")]
+
+
+class _ChunkArgs(C.Structure):  # csh_chunk
+    _fields_ = [("n", C.c_int64), ("stride", C.c_uint32), ("mate", _Mate * 2), ("cap2", C.c_void_p),
+                ("bin", C.c_void_p), ("n_bins", C.c_int32)]
+
+
+class _FormatOut(C.Structure):  # csh_format_out
+    _fields_ = [("out", (C.c_void_p * 2) * 3), ("out_len", (C.c_int64 * 2) * 3), ("counts", C.c_int64 * 3),
+                ("binned", C.c_void_p * 2), ("bin_off", C.c_void_p), ("bin_counts", C.c_void_p)]
+
+
 _bound = None  # the host library once this module's prototypes are bound (see _lib)
 
 
@@ -64,11 +78,16 @@ def _lib():
         L.csh_fastq_count.argtypes = [vp, i64, i64, C.c_int, C.POINTER(i64), C.POINTER(C.c_int32)]
         L.csh_fastq_parse.restype = i64
         L.csh_fastq_parse.argtypes = [vp, i64, i64, C.c_uint32, vp, vp, vp, vp, vp]
+        # a library built from other struct definitions (a stale one) would misread what this module fills in
+        mirrors = (_FormatParams, _ChunkArgs, _FormatOut)
+        sizes = (i64 * 3)()
+        if hasattr(L, "csh_format_struct_sizes"):
+            L.csh_format_struct_sizes(sizes)
+        if list(sizes) != [C.sizeof(t) for t in mirrors]:
+            raise ImportError(f"{L._name}: its csh_format_chunk takes structs of {list(sizes)} bytes, this module "
+                              f"fills {[C.sizeof(t) for t in mirrors]}: rebuild it (python -m cutseq_amd.build)")
         L.csh_format_chunk.restype = i64
-        L.csh_format_chunk.argtypes = [C.POINTER(_FormatParams), i64, C.c_uint32] + [vp] * 13 + [vp, vp, vp] + [vp, vp]
-        L.csh_format_chunk_bins.restype = i64
-        L.csh_format_chunk_bins.argtypes = ([C.POINTER(_FormatParams), i64, C.c_uint32] + [vp] * 13 +
-                                            [vp, C.c_int32, vp, vp, vp] + [vp, vp, vp] + [vp, vp])
+        L.csh_format_chunk.argtypes = [C.POINTER(t) for t in mirrors]
         _bound = L
     return L
 
@@ -220,8 +239,8 @@ class _StrideHint:
 
 
 def _raw_pointer(raw):
-    """Address of a bytes / memoryview / ndarray buffer for the native calls."""
-    return raw if isinstance(raw, bytes) else np.frombuffer(raw, dtype=np.uint8).ctypes.data
+    """Address of a bytes / memoryview / ndarray buffer for the native calls (the caller keeps the object alive)."""
+    return C.cast(raw, C.c_void_p).value if isinstance(raw, bytes) else np.frombuffer(raw, dtype=np.uint8).ctypes.data
 
 
 def _parse(path: str, raw, n_records: int, stride: int, first_record: int, raw_owner=(), pinned: bool = False) -> _Half:
@@ -453,70 +472,6 @@ class Lease:
         ARENA.give(self.arr)
 
 
-def _xflags_pointers(chunk: Chunk, xflags):
-    """``xflags``: None, or the (mate 1, mate 2 | None) uint8 arrays of ``cs_reads.xflags`` (CS_X_* bits)."""
-    if xflags is None:
-        return None, None
-    xf1, xf2 = xflags
-    for x in (xf1, xf2):
-        if x is not None and (x.dtype != np.uint8 or x.shape != (chunk.n,) or not x.flags.c_contiguous):
-            raise ValueError(f"xflags: expected C-contiguous uint8 arrays of shape ({chunk.n},)")
-    return xf1.ctypes.data, (xf2.ctypes.data if xf2 is not None and chunk.paired else None)
-
-
-def format_chunk(chunk: Chunk, plan, res1: np.ndarray, cap2: Optional[np.ndarray], res2: Optional[np.ndarray],
-                 copy: bool = True, lease=None, xflags=None):
-    """-> (data[route][mate], counts[route]) with routes 0 trimmed, 1 short, 2 untrimmed.  ``xflags`` (the per-read
-    ``cs_reads.xflags`` of both mates, or None): pairs TooLong / TooManyN / TooManyExpectedErrors take are written nowhere and counted in no route
-    (``chunk.n - sum(counts)`` of them).  ``data`` holds
-    ``bytes``; with ``copy=False`` it holds memoryviews into this thread's reusable buffers, valid
-    until the thread formats its next chunk -- except the streams flagged in ``lease[route][mate]``,
-    which are formatted straight into arena buffers and come back as :class:`Lease` objects."""
-    L = _lib()
-    fp = _format_params(chunk, plan)
-    # worst case per record: what the input record held (header, sequence, quality: all inside raw)
-    # + '_' + two captures (<= 510) + "@\n\n+\n\n"
-    cap_bytes = [len(chunk.raw1) + 528 * chunk.n + 16, (len(chunk.raw2) + 528 * chunk.n + 16) if chunk.paired else 16]
-    bufs = _out_buffers(cap_bytes)
-    leased = [[None, None] for _ in range(3)]
-    out_ptrs = ((C.c_void_p * 2) * 3)()
-    for r in range(3):
-        for m in range(2):
-            if lease is not None and lease[r][m] and not copy:
-                leased[r][m] = ARENA.take(cap_bytes[m])
-                out_ptrs[r][m] = leased[r][m].ctypes.data
-            else:
-                out_ptrs[r][m] = bufs[r][m].ctypes.data
-    out_len = ((C.c_int64 * 2) * 3)()
-    counts = (C.c_int64 * 3)()
-    xp1, xp2 = _xflags_pointers(chunk, xflags)
-    rc = L.csh_format_chunk(
-        C.byref(fp), chunk.n, chunk.stride, _raw_pointer(chunk.raw1), chunk.name_off1.ctypes.data,
-        chunk.name_len1.ctypes.data, chunk.seq1.ctypes.data, chunk.qual1.ctypes.data, res1.ctypes.data,
-        cap2.ctypes.data if cap2 is not None else None,
-        _raw_pointer(chunk.raw2) if chunk.paired else None,
-        chunk.name_off2.ctypes.data if chunk.paired else None, chunk.name_len2.ctypes.data if chunk.paired else None,
-        chunk.seq2.ctypes.data if chunk.paired else None, chunk.qual2.ctypes.data if chunk.paired else None,
-        res2.ctypes.data if res2 is not None else None, out_ptrs, out_len, counts, xp1, xp2)
-    if rc < 0:
-        for row in leased:
-            for arr in row:
-                if arr is not None:
-                    ARENA.give(arr)
-        i = int(-rc - 1)
-        n1 = bytes(chunk.raw1[chunk.name_off1[i]: chunk.name_off1[i] + chunk.name_len1[i]]).decode(errors="replace")
-        n2 = bytes(chunk.raw2[chunk.name_off2[i]: chunk.name_off2[i] + chunk.name_len2[i]]).decode(errors="replace")
-        err = ValueError(f"Input read IDs not identical: '{n1.split()[0] if n1.split() else n1}' != "
-                         f"'{n2.split()[0] if n2.split() else n2}'")
-        err.record = i  # index of the first such pair inside the chunk
-        raise err
-    views = [[(Lease(leased[r][m], int(out_len[r][m])) if leased[r][m] is not None
-               else memoryview(bufs[r][m])[: out_len[r][m]]) for m in range(2)] for r in range(3)]
-    if copy:
-        return [[bytes(v) for v in row] for row in views], [int(c) for c in counts]
-    return views, [int(c) for c in counts]
-
-
 def _format_params(chunk: Chunk, plan) -> _FormatParams:
     fp = _FormatParams()
     fp.paired = 1 if chunk.paired else 0
@@ -532,83 +487,96 @@ def _format_params(chunk: Chunk, plan) -> _FormatParams:
     return fp
 
 
-def format_chunk_bins(chunk: Chunk, plan, res1, cap2, res2, bc: np.ndarray, n_bins: int, xflags=None):
-    """Demultiplexed formatting: -> (binned[mate] uint8 array, bin_off[mate][n_bins + 1], bin_counts[n_bins],
-    views[route][mate] (routes 1 and 2 in use), counts[route]).  The arrays in ``binned`` are arena buffers
-    the caller gives back."""
+def _chunk_args(chunk: Chunk, res1, cap2, res2, xflags, n_bins: int, bc) -> _ChunkArgs:
+    """``xflags``: None, or the (mate 1, mate 2 | None) uint8 arrays of ``cs_reads.xflags`` (CS_X_* bits)."""
+    def flat_u8(name, x):
+        if x.dtype != np.uint8 or x.shape != (chunk.n,) or not x.flags.c_contiguous:
+            raise ValueError(f"{name}: expected C-contiguous uint8 arrays of shape ({chunk.n},)")
+        return x.ctypes.data
+
+    ck = _ChunkArgs(n=chunk.n, stride=chunk.stride, n_bins=n_bins)
+    mates = ((chunk.raw1, chunk.name_off1, chunk.name_len1, chunk.seq1, chunk.qual1, res1),
+             (chunk.raw2, chunk.name_off2, chunk.name_len2, chunk.seq2, chunk.qual2, res2))
+    for m, (raw, name_off, name_len, seq, qual, res) in enumerate(mates[: 2 if chunk.paired else 1]):
+        xf = xflags[m] if xflags is not None else None
+        ck.mate[m] = _Mate(_raw_pointer(raw), name_off.ctypes.data, name_len.ctypes.data, seq.ctypes.data,
+                           qual.ctypes.data, res.ctypes.data, flat_u8("xflags", xf) if xf is not None else None)
+    ck.cap2 = cap2.ctypes.data if cap2 is not None else None
+    ck.bin = flat_u8("bc", bc) if n_bins else None
+    return ck
+
+
+def format_chunk(chunk: Chunk, plan, res1: np.ndarray, cap2: Optional[np.ndarray], res2: Optional[np.ndarray],
+                 copy: bool = True, lease=None, xflags=None, n_bins: int = 0, bc: Optional[np.ndarray] = None):
+    """-> (data[stream][mate], counts[stream]) with the streams 0 trimmed, 1 short, 2 untrimmed and, with ``n_bins``
+    (demultiplexed output; ``bc``, by default ``chunk.bc``, holds a barcode index per record), one stream 3 + b per
+    barcode: the trimmed records go there, stream 0 stays empty, and a trimmed record whose index is out of range
+    goes to stream 2.  ``xflags`` (the per-read ``cs_reads.xflags`` of both mates, or None): pairs TooLong / TooManyN /
+    TooManyExpectedErrors take are written nowhere and counted in no stream (``chunk.n - sum(counts)`` of them).
+    ``data`` holds ``bytes``; with ``copy=False`` it holds memoryviews into this thread's reusable buffers, valid
+    until the thread formats its next chunk -- except the streams 0 .. 2 flagged in ``lease[stream][mate]``,
+    which are formatted straight into arena buffers and come back as :class:`Lease` objects."""
     L = _lib()
     fp = _format_params(chunk, plan)
+    ck = _chunk_args(chunk, res1, cap2, res2, xflags, n_bins, chunk.bc if bc is None else bc)
+    # what csh_format_chunk asks of every buffer of a mate (cutseq_host.c)
     cap_bytes = [len(chunk.raw1) + 528 * chunk.n + 16, (len(chunk.raw2) + 528 * chunk.n + 16) if chunk.paired else 16]
     bufs = _out_buffers(cap_bytes)
-    out_ptrs = ((C.c_void_p * 2) * 3)()
+    leased = [[None, None] for _ in range(3)]
+    out = _FormatOut()
     for r in range(3):
         for m in range(2):
-            out_ptrs[r][m] = bufs[r][m].ctypes.data
-    binned = [ARENA.take(cap_bytes[0]), ARENA.take(cap_bytes[1])]
-    binned_ptrs = (C.c_void_p * 2)(binned[0].ctypes.data, binned[1].ctypes.data)
+            if lease is not None and lease[r][m] and not copy and not (n_bins and r == 0):
+                leased[r][m] = ARENA.take(cap_bytes[m])
+            out.out[r][m] = (bufs[r][m] if leased[r][m] is None else leased[r][m]).ctypes.data
     bin_off = np.zeros((2, n_bins + 1), dtype=np.int64)
     bin_counts = np.zeros(n_bins, dtype=np.int64)
-    out_len = ((C.c_int64 * 2) * 3)()
-    counts = (C.c_int64 * 3)()
-    xp1, xp2 = _xflags_pointers(chunk, xflags)
-    rc = L.csh_format_chunk_bins(
-        C.byref(fp), chunk.n, chunk.stride, _raw_pointer(chunk.raw1), chunk.name_off1.ctypes.data,
-        chunk.name_len1.ctypes.data, chunk.seq1.ctypes.data, chunk.qual1.ctypes.data, res1.ctypes.data,
-        cap2.ctypes.data if cap2 is not None else None,
-        _raw_pointer(chunk.raw2) if chunk.paired else None,
-        chunk.name_off2.ctypes.data if chunk.paired else None, chunk.name_len2.ctypes.data if chunk.paired else None,
-        chunk.seq2.ctypes.data if chunk.paired else None, chunk.qual2.ctypes.data if chunk.paired else None,
-        res2.ctypes.data if res2 is not None else None, bc.ctypes.data, n_bins, binned_ptrs, bin_off.ctypes.data,
-        bin_counts.ctypes.data, out_ptrs, out_len, counts, xp1, xp2)
+    if n_bins:  # the bins of a mate share the buffer that stream 0 leaves unused
+        out.binned[0], out.binned[1] = bufs[0][0].ctypes.data, bufs[0][1].ctypes.data
+        out.bin_off, out.bin_counts = bin_off.ctypes.data, bin_counts.ctypes.data
+    rc = L.csh_format_chunk(C.byref(fp), C.byref(ck), C.byref(out))
     if rc < 0:
-        for arr in binned:
-            ARENA.give(arr)
-        if -rc > chunk.n:
-            raise ValueError("demultiplexed formatting failed (bad arguments)")
-        raise ValueError(f"Input read IDs not identical in record {int(-rc)} of the chunk")
-    views = [[memoryview(bufs[r][m])[: out_len[r][m]] for m in range(2)] for r in range(3)]
-    return binned, bin_off, bin_counts, views, [int(c) for c in counts]
+        for row in leased:
+            for arr in row:
+                if arr is not None:
+                    ARENA.give(arr)
+        i = int(-rc - 1)
+        if i >= chunk.n:
+            raise ValueError("csh_format_chunk: bad arguments")
+        n1 = bytes(chunk.raw1[chunk.name_off1[i]: chunk.name_off1[i] + chunk.name_len1[i]]).decode(errors="replace")
+        n2 = bytes(chunk.raw2[chunk.name_off2[i]: chunk.name_off2[i] + chunk.name_len2[i]]).decode(errors="replace")
+        err = ValueError(f"Input read IDs not identical: '{n1.split()[0] if n1.split() else n1}' != "
+                         f"'{n2.split()[0] if n2.split() else n2}'")
+        err.record = i  # index of the first such pair inside the chunk
+        raise err
+    views = [[(Lease(leased[r][m], int(out.out_len[r][m])) if leased[r][m] is not None
+               else memoryview(bufs[r][m])[: out.out_len[r][m]]) for m in range(2)] for r in range(3)]
+    views += [[memoryview(bufs[0][m])[bin_off[m][b]: bin_off[m][b + 1]] for m in range(2)] for b in range(n_bins)]
+    counts = [int(c) for c in out.counts] + [int(c) for c in bin_counts]
+    if copy:
+        return [[bytes(v) for v in row] for row in views], counts
+    return views, counts
 
 
 def finish_chunk(chunk: Chunk, plan, res1, cap2, res2, gz: Sequence[Sequence[Optional[bool]]], level: int = 1,
                  n_bins: int = 0, xflags=None):
     """Worker-thread job of the CLI: format one chunk and turn each wanted stream into what goes to disk:
-    one gzip member (bytes), or the plain text in an arena buffer (:class:`Lease`).  ``gz[route][mate]`` is
-    True / False for compressed / plain outputs and None where no file is open.  With ``n_bins`` (a
-    demultiplexing run, ``chunk.bc`` filled) the trimmed route is split by barcode: streams 3 .. 3 + n_bins - 1.
-    -> (blobs[stream][mate], counts per stream)."""
-    if n_bins:
-        binned, bin_off, bin_counts, views, counts = format_chunk_bins(chunk, plan, res1, cap2, res2, chunk.bc, n_bins,
-                                                                       xflags=xflags)
-        blobs = [[None, None] for _ in range(3 + n_bins)]
-        try:
-            for r in (1, 2):
-                for m in range(2):
-                    if gz[r][m] is not None and len(views[r][m]):
-                        blobs[r][m] = codec.gzip_member(views[r][m], level) if gz[r][m] else bytes(views[r][m])
-            for b in range(n_bins):
-                for m in range(2 if chunk.paired else 1):
-                    lo, hi = int(bin_off[m][b]), int(bin_off[m][b + 1])
-                    if hi > lo and gz[3 + b][m] is not None:
-                        piece = memoryview(binned[m])[lo:hi]
-                        blobs[3 + b][m] = codec.gzip_member(piece, level) if gz[3 + b][m] else bytes(piece)
-        finally:
-            for arr in binned:
-                ARENA.give(arr)
-        return blobs, [0, counts[1], counts[2]] + [int(c) for c in bin_counts]
+    one gzip member (bytes), or the plain text (a :class:`Lease` on an arena buffer, or bytes for a barcode's
+    stream).  ``gz[stream][mate]`` is True / False for compressed / plain outputs and None where no file is open.
+    With ``n_bins`` (a demultiplexing run, ``chunk.bc`` filled) the trimmed route is split by barcode: streams
+    3 .. 3 + n_bins - 1.  -> (blobs[stream][mate], counts per stream)."""
     lease = [[gz[r][m] is False for m in range(2)] for r in range(3)]
-    views, counts = format_chunk(chunk, plan, res1, cap2, res2, copy=False, lease=lease, xflags=xflags)
-    blobs = [[None, None] for _ in range(3)]
-    for r in range(3):
-        for m in range(2):
-            v = views[r][m]
+    views, counts = format_chunk(chunk, plan, res1, cap2, res2, copy=False, lease=lease, xflags=xflags, n_bins=n_bins)
+    blobs = [[None, None] for _ in views]
+    for s, row in enumerate(views):
+        for m, v in enumerate(row):
             if isinstance(v, Lease):
                 if v.n:
-                    blobs[r][m] = v
+                    blobs[s][m] = v
                 else:
                     v.release()
-            elif gz[r][m] is not None and len(v):
-                blobs[r][m] = codec.gzip_member(v, level)
+            elif gz[s][m] is not None and len(v):
+                blobs[s][m] = codec.gzip_member(v, level) if gz[s][m] else bytes(v)
     return blobs, counts
 
 

@@ -197,12 +197,10 @@ def test_host_formatter_precedence(paired, bins):
     xflags = (xf1, xf2 if paired else None)
     if bins:
         bc = np.zeros(n, dtype=np.uint8)  # every pair carries barcode 0
-        binned, _bin_off, bin_counts, _views, counts = fastq.format_chunk_bins(c, tp, res1, None, res2, bc, 1, xflags=xflags)
-        for arr in binned:
-            fastq.ARENA.give(arr)
-        assert int(bin_counts[0]) == want.count(0)
+        _data, counts = fastq.format_chunk(c, tp, res1, None, res2, xflags=xflags, n_bins=1, bc=bc)
+        assert counts[3] == want.count(0)
         assert counts[1] == want.count(1) and counts[2] == want.count(2)
-        written = int(bin_counts[0]) + counts[1] + counts[2]
+        written = counts[3] + counts[1] + counts[2]
     else:
         data, counts = fastq.format_chunk(c, tp, res1, None, res2, xflags=xflags)
         assert counts == [want.count(0), want.count(1), want.count(2)]

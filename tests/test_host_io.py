@@ -369,6 +369,129 @@ class SynthLike:
         self.seq2, self.qual2, self.len2 = c.seq2, c.qual2, c.len2
 
 
+_BIN_RECORDS, _BINS, _EMPTY_BIN = 300, 3, 1
+
+
+def _hand_made_chunk(tmp_path, paired, seed):
+    """300 records through read_chunks: lengths 0 .. 40, names with and without a second field and /1, /2 suffixes;
+    hand-drawn results (start <= stop <= len, captures inside the read), flags, xflags and barcodes."""
+    rng = np.random.default_rng(seed)
+    n = _BIN_RECORDS
+    forms = ("r%d", "r%d 1:N:0:ACGT", "r%d/{m}", "r%d/{m} with\ttab", "r%d\tfield")
+    names, recs = [[], []], [[], []]
+    for i in range(n):
+        form = forms[int(rng.integers(len(forms)))]
+        for m in range(2):
+            ln = 0 if i % 37 == 5 else int(rng.integers(0, 41))
+            names[m].append((form % i).format(m=m + 1).encode())
+            recs[m].append((names[m][-1], bytes(rng.choice(list(b"ACGTN"), ln).astype(np.uint8)),
+                            bytes(rng.integers(33, 75, ln).astype(np.uint8))))
+    write_fq(tmp_path / "1.fq", recs[0], gz=False)
+    write_fq(tmp_path / "2.fq", recs[1], gz=False)
+    (c,) = list(fastq.read_chunks(str(tmp_path / "1.fq"), str(tmp_path / "2.fq") if paired else None))
+    assert c.n == n
+
+    def results(lens):
+        res = np.zeros(n, dtype=abi.RESULT_DTYPE)
+        cap2 = np.zeros(n, dtype=abi.CAP2_DTYPE)
+        for i in range(n):
+            ln = int(lens[i])
+            stop = int(rng.integers(0, ln + 1))
+            start = int(rng.integers(0, stop + 1))
+            off = int(rng.integers(0, ln + 1))
+            off2 = int(rng.integers(0, ln + 1))
+            flags = int(rng.integers(0, 256)) & ~(abi.CS_F_TOO_SHORT | abi.CS_F_UNTRIMMED)
+            flags |= abi.CS_F_TOO_SHORT if rng.random() < 0.12 else 0
+            flags |= abi.CS_F_UNTRIMMED if rng.random() < 0.15 else 0
+            res[i] = (start, stop, off, int(rng.integers(0, ln - off + 1)), flags)
+            cap2[i] = (off2, int(rng.integers(0, ln - off2 + 1)), 0)
+        return res, cap2
+
+    res1, cap2 = results(c.len1)
+    res2 = results(c.len2)[0] if paired else None
+    xf = [np.where(rng.random(n) < 0.15, rng.integers(1, 8, n), 0).astype(np.uint8) for _ in range(2)]
+    bc = rng.choice([b for b in range(_BINS) if b != _EMPTY_BIN], n).astype(np.uint8)
+    bc[rng.random(n) < 0.1] = abi.CS_DEMUX_NONE
+    return c, names, res1, cap2, res2, (xf[0], xf[1] if paired else None), bc
+
+
+@pytest.mark.parametrize("n_bins", [_BINS, 0])
+@pytest.mark.parametrize("paired,has_umi,two_captures,rc,gz", [
+    (True, True, False, False, False),
+    (True, False, False, False, False),
+    (False, True, True, False, False),
+    (False, False, False, True, False),
+    (True, True, False, False, True),
+])
+def test_finish_chunk_bytes_plain_and_binned(tmp_path, paired, has_umi, two_captures, rc, gz, n_bins):
+    """finish_chunk's bytes per (stream, mate) and counts per stream against the record logic (util.format_batch) on
+    hand-made records, with and without bins.  The route rule: filters_rule.route first (short, the discarding
+    filters, untrimmed); then a trimmed record with bc < n_bins goes to stream 3 + bc, one with bc >= n_bins (no
+    barcode) to stream 2.  Without bins trimmed records stay in stream 0."""
+    import filters_rule
+
+    tp = util.compile_plan(BUILDIN_ADAPTERS["TAKARAV3"], planmod.CutadaptConfig(), paired)
+    tp.has_umi, tp.untrimmed_filter, tp.reverse_complement = has_umi, True, rc
+    c, names, res1, cap2, res2, xflags, bc = _hand_made_chunk(tmp_path, paired, seed=20 + paired)
+    if not two_captures:
+        cap2 = None
+    c.bc = bc
+    n, streams = c.n, 3 + n_bins
+    recs = util.format_batch(tp, SynthLike(c), names[0], names[1], res1, cap2, res2)
+    want = [[b"", b""] for _ in range(streams)]
+    want_counts, discarded = [0] * streams, {name: 0 for name, _bit in filters_rule.ORDER}
+    for i, (_rt, rec1, rec2) in enumerate(recs):
+        where = filters_rule.route(int(res1[i]["flags"]), int(res2[i]["flags"]) if paired else 0, int(xflags[0][i]),
+                                   int(xflags[1][i]) if paired else 0, tp.untrimmed_filter)
+        if where in discarded:
+            discarded[where] += 1
+            continue
+        if where == 0 and n_bins:
+            where = 3 + int(bc[i]) if bc[i] < n_bins else 2
+        want[where][0] += rec1
+        want[where][1] += rec2 or b""
+        want_counts[where] += 1
+    # what the case claims to cover occurs
+    empty = {0, 3 + _EMPTY_BIN} if n_bins else set()
+    assert all((want_counts[s] > 0) == (s not in empty) for s in range(streams)), want_counts
+    assert all(discarded.values()), discarded
+    assert (c.len1 == 0).any() and int(c.len1.max()) == 40 and (bc == abi.CS_DEMUX_NONE).any()
+
+    blobs, counts = fastq.finish_chunk(c, tp, res1, cap2, res2, [[gz, gz] for _ in range(streams)], n_bins=n_bins,
+                                       xflags=xflags)
+    assert list(counts) == want_counts and n - sum(counts) == sum(discarded.values())
+    assert len(blobs) == streams
+    for s in range(streams):
+        for m in range(2):
+            blob = blobs[s][m]
+            if not want[s][m]:  # nothing for this file: no blob at all (the unused mate, stream 0, the empty bin)
+                assert blob is None, (s, m)
+                continue
+            if isinstance(blob, fastq.Lease):
+                text = bytes(blob.view())
+                blob.release()
+            else:
+                text = bytes(blob)
+            assert (gzip.decompress(text) if gz else text) == want[s][m], (s, m)
+
+
+@pytest.mark.parametrize("k", [0, 17, 39])
+def test_binned_chunk_with_differing_ids_raises_the_plain_message(tmp_path, k):
+    """A demultiplexing run reports mates whose ids differ like any other run: both ids, and the record's index."""
+    tp = util.compile_plan(BUILDIN_ADAPTERS["TAKARAV3"], planmod.CutadaptConfig(), True)
+    recs1 = [(b"r%d/1" % i, b"ACGT" * 5, b"I" * 20) for i in range(40)]
+    recs2 = [(b"r%d/2" % i if i != k else b"other/2", b"ACGT" * 5, b"I" * 20) for i in range(40)]
+    write_fq(tmp_path / "1.fq", recs1, gz=False)
+    write_fq(tmp_path / "2.fq", recs2, gz=False)
+    (c,) = list(fastq.read_chunks(str(tmp_path / "1.fq"), str(tmp_path / "2.fq")))
+    c.bc = (np.arange(40) % 3).astype(np.uint8)
+    res = np.zeros(40, dtype=abi.RESULT_DTYPE)
+    res["stop"] = 20
+    with pytest.raises(ValueError, match=r"Input read IDs not identical: 'r%d/1' != 'other/2'" % k) as err:
+        fastq.finish_chunk(c, tp, res, None, res.copy(), [[False, False] for _ in range(6)], n_bins=3)
+    assert err.value.record == k
+
+
 # ---------------------------------------------------------------- gzip codec (libdeflate / BGZF / zlib)
 
 
@@ -532,6 +655,22 @@ print("ok")
     for _ in range(4):
         out = subprocess.run([sys.executable, "-c", code], cwd=root, capture_output=True, text=True, timeout=120)
         assert out.returncode == 0 and out.stdout.strip() == "ok", (out.returncode, out.stdout, out.stderr[-500:])
+
+
+def test_library_with_other_struct_sizes_is_refused_at_bind_time(monkeypatch):
+    """A mirror of csh_format_chunk's argument structs that is not the size the library reports (a stale library, or
+    a field added on one side only) raises when the prototypes are bound, before any call is made."""
+    import ctypes
+
+    class Grown(ctypes.Structure):
+        _fields_ = list(fastq._FormatOut._fields_) + [("more", ctypes.c_void_p)]
+
+    fastq._lib()
+    monkeypatch.setattr(fastq, "_bound", None)
+    monkeypatch.setattr(fastq, "_FormatOut", Grown)
+    with pytest.raises(ImportError, match="csh_format_chunk takes structs of"):
+        fastq._lib()
+    assert fastq._bound is None
 
 
 def test_threads_flag_bounds_the_host_pool(monkeypatch):

@@ -116,11 +116,9 @@ def test_host_formatter_precedence(paired, bins):
                             int(xf2[i]) if paired else 0, True) for i in range(n)]
     if bins:
         bc = np.zeros(n, dtype=np.uint8)  # every pair carries barcode 0
-        binned, bin_off, bin_counts, views, counts = fastq.format_chunk_bins(c, tp, res1, None, res2, bc, 1,
-                                                                            xflags=(xf1, xf2 if paired else None))
-        for arr in binned:
-            fastq.ARENA.give(arr)
-        assert int(bin_counts[0]) == want.count(0)
+        _data, counts = fastq.format_chunk(c, tp, res1, None, res2, xflags=(xf1, xf2 if paired else None), n_bins=1,
+                                           bc=bc)
+        assert counts[3] == want.count(0)
         assert counts[1] == want.count(1) and counts[2] == want.count(2)
     else:
         data, counts = fastq.format_chunk(c, tp, res1, None, res2, xflags=(xf1, xf2 if paired else None))
