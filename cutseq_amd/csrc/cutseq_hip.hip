@@ -238,8 +238,16 @@ int build_dev_op(const cs_op &in, csdev::DevOp &out, int index, int mate) {
       if (op.capture && (op.cut_len > 255 || op.cut_len < -255))
         return fail(CS_ERR_ARG, "mate %d op %d: capturing cuts are limited to 255 bases", mate, index);
       break;
-    case CS_OP_QTRIM:
+    case CS_OP_QTRIM: {
+      // A base adds cutoff + base - quality byte.  Once cutoff + base leaves [-1, 256] every term has one sign for
+      // every byte 0..255 (all negative: nothing kept is trimmed, stop n; all positive: stop 0), so the cutoff clamps
+      // to [-1 - base, 256 - base] without changing a result, and every term is within +-256: a tile kernel's running
+      // sum stays below 256 * CS_MAX_STRIDE (trim_kernel.hip.inc, kPosBits), the long-read kernel's below
+      // 256 * CS_MAX_READ = 2^32 (long_kernel.hip.inc, quality_stop: 64-bit).
+      const int lo = csdev::kQCutoffLow - (int)op.q_base, hi = csdev::kQCutoffHigh - (int)op.q_base;
+      op.q_cutoff = (int16_t)std::min(std::max((int)op.q_cutoff, lo), hi);
       break;
+    }
     case CS_OP_DEMUX:
       if (op.m < 1 || op.k > op.m || op.m + op.k > CS_DEMUX_MAX_LONG)
         return fail(CS_ERR_ARG, "mate %d op %d: demux barcode length %u with %u errors (m + k <= %d)", mate, index, op.m,

@@ -177,9 +177,12 @@ __device__ __forceinline__ bool find_exact(const cs_op &op, const Env &v, const 
   return false;
 }
 
-// cutadapt quality_trim_index (cutoff_front = 0) on qual[0, n): BWA running sum from the 3' end, first strict maximum
+// cutadapt quality_trim_index (cutoff_front = 0) on qual[0, n): BWA running sum from the 3' end, first strict maximum.
+// A term is at most 256 in size (cs_plan_create clamps the cutoff), a read at most CS_MAX_READ = 2^24 bases: the sum
+// reaches 2^32, so it is a 64-bit sum.
 __device__ __forceinline__ int quality_stop(const cs_op &op, const uint8_t *qual, int n) {
-  int sum = 0, best = 0, stop = n;
+  long long sum = 0, best = 0;
+  int stop = n;
   for (int i = n - 1; i >= 0; --i) {
     sum += (int)op.q_cutoff - ((int)qual[i] - (int)op.q_base);
     if (sum < 0) break;

@@ -75,6 +75,9 @@ __host__ __device__ constexpr uint32_t base_code(uint32_t ascii) {
 constexpr int kEqTableBytes = 64;
 constexpr int kWaveItemDwords = 4;  // queue entry per survivor: row|j0, j1|do_end|rmax, s|e, result
 constexpr int kCutRun = 4;          // most CUT ops walked in one turn of the op loop (DevOp::cut_pack)
+// QTRIM: cutoff + base as cs_plan_create clamps it (build_dev_op: outside [-1, 256] every term has one sign, the result
+// is that of the nearest end), and the largest |term| = |cutoff + base - quality byte| that leaves
+constexpr int kQCutoffLow = -1, kQCutoffHigh = 256, kQTermMax = 256;
 
 // The scalar fields of a cs_op as dwords (filled when the engine uploads the plan): a wave-uniform dword comes through
 // the scalar cache, a byte or a halfword through a VECTOR load with a wait for everything the wave has in flight --
@@ -3301,6 +3304,11 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
         const bool live = on && n > 0;
         const int p_last = s + n - 1;
         constexpr int kPosBits = 11;  // positions < 2048 (CS_MAX_STRIDE = 1536)
+        // the key is an int: position below the start key's 2047, running sum (at most kQTermMax a base over a row,
+        // the cutoff clamped by cs_plan_create) in the 31 - kPosBits bits above it
+        static_assert(CS_MAX_STRIDE < (1 << kPosBits) - 1 && kQCutoffHigh <= kQTermMax && 255 - kQCutoffLow <= kQTermMax &&
+                          (long long)kQTermMax * CS_MAX_STRIDE < (1ll << (31 - kPosBits)),
+                      "QTRIM key: sum << kPosBits | position must fit an int");
         int sum = 0, bestkey = (1 << kPosBits) - 1;  // sum 0 at a position beyond every real one: only sums > 0 replace it
         bool alive = live;
         auto exact4 = [&](uint32_t w, int pbase, bool take) {  // the four bases of one dword, 3' -> 5', with range checks

@@ -278,9 +278,13 @@ int cs_oracle_match(const cs_op *op, int select_rule, const uint8_t *read, int n
 
 /* cutadapt qualtrim.pyx quality_trim_index(qualities, cutoff_front=0, cutoff_back, base):
  * BWA-style running sum from the 3' end.  With cutoff_front == 0 the 5' loop never moves
- * `start` (first base with q > 0 makes the sum negative), so only `stop` is computed. */
+ * `start` (first base with q > 0 makes the sum negative), so only `stop` is computed.
+ * The cutoff is taken as given (any int16, cs_op.q_cutoff: the product clamps it, the reference
+ * does not): a term is below 2^16 in size, a read at most CS_MAX_READ = 2^24 bases, the sum
+ * below 2^40 -- a 64-bit sum. */
 int cs_oracle_quality_trim_index(const uint8_t *qual, int n, int cutoff_back, int base) {
-  int s = 0, max_qual = 0, stop = n;
+  int64_t s = 0, max_qual = 0;
+  int stop = n;
   for (int i = n - 1; i >= 0; i--) {
     s += cutoff_back - ((int)qual[i] - base);
     if (s < 0) break;
