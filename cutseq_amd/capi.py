@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 from pathlib import Path
 
-from . import abi
+from . import abi, switches
 
 LIB_PATH = Path(__file__).with_name("libcutseq_hip.so")
 
@@ -41,8 +41,7 @@ def load() -> C.CDLL:
     global _lib
     if _lib is not None:
         return _lib
-    import os
-    lib_path = Path(os.environ.get("CUTSEQ_HIP_LIB", str(LIB_PATH)))  # A/B builds when tuning
+    lib_path = Path(switches.path("HIP_LIB", str(LIB_PATH)))  # A/B builds when tuning
     if not lib_path.exists():
         raise HipUnavailable(
             f"{lib_path} not found: build it with `python -m cutseq_amd.build` "

@@ -15,12 +15,13 @@ from __future__ import annotations
 
 import ctypes as C
 import mmap
-import os
 import struct
 import sys
 import threading
 import zlib
 from typing import Iterator
+
+from . import switches
 
 # Largest decompressed member taken in one libdeflate call.  A member that does not fit the first buffer is tried
 # ONCE more at this size and then streamed through zlib: a multi-gigabyte single-member file (the usual sequencer
@@ -319,7 +320,7 @@ class GzipSource:
         not fit ``_MEMBER_CAP`` (``grow`` False: does not fit ``cap``), anything else = no gzip member starts here (or
         it is corrupt)."""
         base = _view_address(memoryview(self.map))
-        H = _pinflate() if os.environ.get("CUTSEQ_OWN_INFLATE", "1") != "0" else None
+        H = _pinflate() if switches.enabled("OWN_INFLATE") else None
         if H is not None:
             # the host library's byte-mode decoder (csrc/pinflate.c: whole matches in one table entry; 1.06 GB/s per
             # thread with the CRC behind it where libdeflate 1.10 does 0.93 -- tools/micro/member_rate.py); header,
@@ -509,7 +510,7 @@ class GzipSource:
         with whatever follows it); without one, or without the host library: stream everything from here through zlib."""
         H = _pinflate() if self.pool is not None else None
         hdr = _gzip_header_size(self.map, head) if H is not None else 0
-        if H is None or hdr == 0 or os.environ.get("CUTSEQ_PARALLEL_INFLATE", "1") == "0":
+        if H is None or hdr == 0 or not switches.enabled("PARALLEL_INFLATE"):
             end = yield from self._from_head(self._zlib_member(head), head)
         else:
             end = yield from self._from_head(self._parallel_member(H, head + hdr), head)
@@ -620,7 +621,7 @@ class GzipSource:
                 self.stats["chunks"] = self.stats.get("chunks", 0) + 1
                 if start != pos or rc != 0:
                     self.stats["serial"] = self.stats.get("serial", 0) + 1
-                    if os.environ.get("CUTSEQ_DEBUG_INFLATE") == "1":  # diagnostic: which chunk lost its proof, and how
+                    if switches.enabled("DEBUG_INFLATE"):  # diagnostic: which chunk lost its proof, and how
                         import sys
                         print(f"inflate: chunk {i} of {n_chunks} (S = {S}): proven bit {pos}, speculative start {start}, rc {rc}", file=sys.stderr)
                     # not proven (finder missed the boundary, saw a false one, or the chunk overflowed): from the proven

@@ -21,7 +21,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import abi, codec
+from . import abi, codec, switches
 from .synth import host_lib as _host_lib
 
 CHUNK_READS = 1 << 16
@@ -104,7 +104,7 @@ class _Arena:
         self._pinned = pinned
         # pinned arena: cs_alloc_pinned_huge (page-locked memory on huge pages: 17 instead of 7.5 GB/s to get, same
         # copy bandwidth) unless CUTSEQ_PINNED_THP=0
-        self.huge = os.environ.get("CUTSEQ_PINNED_THP", "1") != "0"
+        self.huge = switches.enabled("PINNED_THP")
         self._all_pinned: list = []  # (address, array) of every pinned buffer ever handed out
 
     @staticmethod

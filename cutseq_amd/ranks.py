@@ -36,7 +36,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import codec, fastq, report
+from . import codec, fastq, report, switches
 
 _PIECE = 8 << 20
 
@@ -365,8 +365,7 @@ def output_groups(args) -> dict:
 
 
 def _run_ranks(argv: List[str], args, world: int, shares, t0: float, how: str) -> dict:
-    want = os.environ.get("CUTSEQ_DEVICES")
-    devices = [int(x) for x in want.split(",")] if want else list(range(world))
+    devices = switches.device_list("DEVICES", world)
     groups = output_groups(args)
     work = tempfile.mkdtemp(prefix="cutseq_ranks_")
     children, specs = [], []

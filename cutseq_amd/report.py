@@ -19,7 +19,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import __version__, abi
+from . import __version__, abi, switches
 from .plan import AdapterOp, MateChain, TrimPlan
 
 # cutadapt's filter identifiers, in report order
@@ -255,13 +255,12 @@ class Progress:
     is.  ``CUTSEQ_PROGRESS=0`` silences both."""
 
     def __init__(self, stream=None):
-        import os
         import sys
         import threading
         import time
         self._time = time
         self.stream = stream if stream is not None else sys.stderr
-        self.enabled = os.environ.get("CUTSEQ_PROGRESS", "1") != "0"
+        self.enabled = switches.enabled("PROGRESS")
         self.live = self.enabled and hasattr(self.stream, "isatty") and self.stream.isatty()
         self.t0 = time.time()
         self.last = self.t0
@@ -296,7 +295,7 @@ class Progress:
 
 def phase(tag: str) -> None:
     """Diagnostic (CUTSEQ_PROFILE=1): seconds since the interpreter started, per phase of the run."""
-    if os.environ.get("CUTSEQ_PROFILE") == "1":
+    if switches.enabled("PROFILE"):
         print(f'{{"cutseq_phase": "{tag}", "process_seconds": {time.perf_counter() - _T_IMPORT + _IMPORT_OFFSET:.3f}}}', file=sys.stderr)
 
 

@@ -20,7 +20,7 @@ import time
 from collections import deque
 from typing import List, Optional
 
-from . import __version__, abi, fanout, report
+from . import __version__, abi, fanout, report, switches
 from .abi import ReadTooLong
 from .common import BUILDIN_ADAPTERS, BarcodeConfig, print_builtin_adapters, remove_fq_suffix
 from .plan import CutadaptConfig, TrimPlan, compile_paired, compile_single
@@ -174,7 +174,7 @@ def resolve_args(args):
         if args.demux_barcodes:
             _fail("--info-file cannot be combined with --demux-barcodes: the table form of the demultiplexing op has "
                   "no error count to report.")
-        if os.environ.get("CUTSEQ_TEXT_PATH", "1") == "0":
+        if not switches.enabled("TEXT_PATH"):
             _fail("--info-file needs the text path: the table is written on the GPU (CUTSEQ_TEXT_PATH=0 is set).")
     if not inputs:
         # the reference dies with an IndexError here (run.py:1079-1083); same exit class, clearer message
@@ -344,8 +344,7 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
             fastq.set_threads(args.threads)
         except RuntimeError:  # a second run in one process (tests): the pool of the first run stays
             logging.warning("-t/--threads ignored: the host thread pool of this process is already running.")
-    want = os.environ.get("CUTSEQ_DEVICES")  # e.g. "0,1,2,3"; a device may be listed twice (two engines on it)
-    devices = [int(x) for x in want.split(",")] if want else list(range(n_dev))
+    devices = switches.device_list("DEVICES", n_dev)  # e.g. "0,1,2,3"; a device may be listed twice (two engines on it)
     if any(d < 0 or d >= n_dev for d in devices):
         _fail(f"GPU {max(devices)} does not exist: this process sees {n_dev} (--ranks N puts rank r on GPU r; "
               "CUTSEQ_DEVICES=0,0,... lists the GPUs to use, one entry per rank or worker, repeats allowed).")
@@ -353,7 +352,7 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
     # runs included.  The record path below is the second host implementation (native parser / formatter of
     # cutseq_host.c in a thread pool), selected by CUTSEQ_TEXT_PATH=0 and held to the same outputs by the tests.
     from . import textio
-    if os.environ.get("CUTSEQ_TEXT_PATH", "1") != "0":
+    if switches.enabled("TEXT_PATH"):
         return textio.run_text_pipeline(args, tp, devices, _block_records(args, len(devices)),
                                         shares=shares)
     if shares is not None:
@@ -363,7 +362,9 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
         container, first, _ = codec.sniff_input(name) if name != "-" else ("stdin", b"", None)
         if container not in ("plain", "gzip") or first in (b">", b"#"):
             _fail(f"{name}: FASTA input, standard input and bzip2 / xz / zstandard files need the text path (CUTSEQ_TEXT_PATH unset).")
-    chunk_reads = int(os.environ.get("CUTSEQ_CHUNK_READS", fastq.CHUNK_READS))
+    chunk_reads = switches.int_value("CHUNK_READS")
+    if chunk_reads is None:
+        chunk_reads = fastq.CHUNK_READS
     paired = tp.paired
     n_bins = len(tp.demux.barcodes) if tp.demux is not None else 0
     # the open file (or None) per [stream][mate]
@@ -479,7 +480,7 @@ def run_cutseq(args, argv=None):
         ranks.dump_totals(spec, totals)
         return totals
     if getattr(args, "ranks", 1) > 1:
-        if os.environ.get("CUTSEQ_TEXT_PATH", "1") == "0":
+        if not switches.enabled("TEXT_PATH"):
             logging.warning("--ranks ignored: it needs the text path.")
         else:
             from . import ranks
@@ -508,8 +509,9 @@ def _block_records(args, n_devices: int) -> int:
     plain text with blocks of 65 536 to 262 144 records, and gzip input likes the big ones: 1.33 against 1.51 s;
     profiles/r03_cold_runs.log.)"""
     from . import textio
-    if os.environ.get("CUTSEQ_CHUNK_READS"):
-        return int(os.environ["CUTSEQ_CHUNK_READS"])
+    fixed = switches.int_value("CHUNK_READS")
+    if fixed is not None:
+        return fixed
     try:
         size = os.path.getsize(args.input_file[0])
     except OSError:
@@ -550,7 +552,7 @@ def console_main():
     exit; so does anybody who sets CUTSEQ_FAST_EXIT=0."""
     traced = any("rocprof" in os.environ.get(k, "").lower() or "roctracer" in os.environ.get(k, "").lower()
                  for k in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "HSA_TOOLS_LIB", "ROCPROFILER_REGISTER_FORCE_LOAD"))
-    if traced or os.environ.get("CUTSEQ_FAST_EXIT", "1") == "0":
+    if traced or not switches.enabled("FAST_EXIT"):
         return main()
     code = 0
     try:

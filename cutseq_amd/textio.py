@@ -30,7 +30,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import abi, codec, fanout, fastq, report, textpath
+from . import abi, codec, fanout, fastq, report, switches, textpath
 from .abi import ReadTooLong
 
 CHUNK_READS = 1 << 18
@@ -41,7 +41,7 @@ _MAP_MIN = 8 << 20        # ... used from this size on (smaller pieces go throug
 _PAGE = mmap.ALLOCATIONGRANULARITY
 
 
-PROFILE = os.environ.get("CUTSEQ_PROFILE") == "1"
+PROFILE = switches.enabled("PROFILE")  # (sampled once, when the module is imported)
 _DISCARD = False
 _prof = {}
 _prof_lock = threading.Lock()
@@ -632,13 +632,6 @@ class TextWorker(fanout.Worker):
 
     def submit(self, slot: int, item):
         b1, b2 = item
-        if os.environ.get("CUTSEQ_DEBUG_BLOCKS") == "1":  # diagnostic: what goes to the device
-            import sys
-            L = _host()
-            print(f"block at record {b1.first_record}: slot {slot} records {b1.n}/{b2.n if b2 is not None else '-'} bytes {b1.nbytes}/"
-                  f"{b2.nbytes if b2 is not None else '-'} newlines {L.csh_count_newlines(b1.buf.ctypes.data, b1.nbytes)}/"
-                  f"{L.csh_count_newlines(b2.buf.ctypes.data, b2.nbytes) if b2 is not None else '-'} capacity {self.capacity}",
-                  file=sys.stderr, flush=True)
         self.text.submit(slot, b1.buf, b1.nbytes, b2.buf if b2 is not None else None, b2.nbytes if b2 is not None else 0, b1.n)
         return item
 
@@ -775,7 +768,7 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
     """The CLI's run on the text path -> the run statistics ``report`` expects.  ``shares``: per input file the part
     of it this process takes (``ranks.py``)."""
     global _DISCARD
-    _DISCARD = os.environ.get("CUTSEQ_DISCARD_OUTPUT") == "1"  # diagnostic: the writers drop their bytes
+    _DISCARD = switches.enabled("DISCARD_OUTPUT")  # diagnostic: the writers drop their bytes
     paired = tp.paired
     share = shares or [{}, {}]
     r1 = TextReader(args.input_file[0], chunk_reads, **share[0])  # (a missing input file raises here, before anything else exists)
@@ -791,7 +784,8 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         # every output a ".gz" file: the device compresses (deflate_kernels.hip.inc) and the writers pass the members
         # through; otherwise text comes back and ".gz" outputs are deflated in the host pool (CUTSEQ_GPU_DEFLATE=0 too)
         names_all = [n for group in name_groups for n in group if n]
-        compress = bool(names_all) and all(n != "-" and codec.container_of_name(n) == "gzip" for n in names_all) and os.environ.get("CUTSEQ_GPU_DEFLATE", "1") != "0"
+        gpu_deflate = switches.enabled("GPU_DEFLATE")
+        compress = gpu_deflate and bool(names_all) and all(n != "-" and codec.container_of_name(n) == "gzip" for n in names_all)
         if r2 is not None and r1.fasta != r2.fasta:
             raise fastq.FastqFormatError("the two input files are in different formats (one FASTA, one FASTQ)")
         if r1.fasta and tp.max_ee is not None:
@@ -808,7 +802,7 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         info_name = getattr(args, "info_file", None)
         info_flags, info_out = 0, None
         if info_name:
-            info_gz = info_name != "-" and codec.container_of_name(info_name) == "gzip" and os.environ.get("CUTSEQ_GPU_DEFLATE", "1") != "0"
+            info_gz = gpu_deflate and info_name != "-" and codec.container_of_name(info_name) == "gzip"
             info_flags = abi.CS_INFO_ON | (abi.CS_INFO_GZIP if info_gz else 0) | (abi.CS_INFO_NO_QUAL if r1.fasta else 0)
             info_out = writer(info_name, info_gz)
     except BaseException:
