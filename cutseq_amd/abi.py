@@ -14,7 +14,7 @@ CS_MAX_STRIDE = 1536
 CS_LEN_SKIP = 0xFFFF
 CS_MAX_READ = 1 << 24
 
-CS_OP_ADAPTER, CS_OP_CUT, CS_OP_QTRIM, CS_OP_DEMUX = 1, 2, 3, 4
+CS_OP_ADAPTER, CS_OP_CUT, CS_OP_QTRIM, CS_OP_DEMUX, CS_OP_NTRIM = 1, 2, 3, 4, 5
 CS_DEMUX_NONE = 0xFF
 CS_DEMUX_MAX_PREFIX = 11
 CS_DEMUX_MAX_LONG = 24
@@ -75,7 +75,8 @@ class cs_op(C.Structure):
         ("q_cutoff", C.c_int16),
         ("seq", C.c_uint8 * CS_MAX_ADAPTER),
         ("thr", C.c_uint8 * (CS_MAX_ADAPTER + 1)),
-        ("_pad", C.c_uint8 * 3),
+        ("_pad", C.c_uint8 * 1),
+        ("q_cutoff_front", C.c_int16),
     ]
 
 
@@ -178,7 +179,7 @@ class cs_text_result(C.Structure):
 
 
 assert C.sizeof(cs_text_params) == 48 and C.sizeof(cs_text_result) == 176
-assert C.sizeof(cs_op) == 284, C.sizeof(cs_op)
+assert C.sizeof(cs_op) == 284 and cs_op.q_cutoff_front.offset == 282, C.sizeof(cs_op)
 assert C.sizeof(cs_result) == 8
 assert C.sizeof(cs_cap2) == 4
 assert C.sizeof(cs_params) == 32

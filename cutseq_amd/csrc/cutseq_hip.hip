@@ -134,6 +134,7 @@ struct cs_engine {
   bool coded = false;
   bool wide = false;  // some adapter needs 64-bit bit-vectors
   uint32_t filters = 0;  // CS_X_* bits of the plan's filters (cs_plan_set_max_length / _max_n / _max_ee)
+  bool ends = false;     // some CS_OP_QTRIM op has a front cutoff, or the plan has a CS_OP_NTRIM op (FILT_ENDS kernels)
   int n_cus = 256;
   uint32_t n_table_ops = 1;
   uint32_t col_dwords = 0;   // per-wave DP scratch the plan needs (resolve kernel)
@@ -246,8 +247,12 @@ int build_dev_op(const cs_op &in, csdev::DevOp &out, int index, int mate) {
       // 256 * CS_MAX_READ = 2^32 (long_kernel.hip.inc, quality_stop: 64-bit).
       const int lo = csdev::kQCutoffLow - (int)op.q_base, hi = csdev::kQCutoffHigh - (int)op.q_base;
       op.q_cutoff = (int16_t)std::min(std::max((int)op.q_cutoff, lo), hi);
+      // the 5' cutoff: the same terms, the same clamp (0, "no front walk", lies inside for every base)
+      op.q_cutoff_front = (int16_t)std::min(std::max((int)op.q_cutoff_front, lo), hi);
       break;
     }
+    case CS_OP_NTRIM:
+      break;
     case CS_OP_DEMUX:
       if (op.m < 1 || op.k > op.m || op.m + op.k > CS_DEMUX_MAX_LONG)
         return fail(CS_ERR_ARG, "mate %d op %d: demux barcode length %u with %u errors (m + k <= %d)", mate, index, op.m,
@@ -278,6 +283,7 @@ const void *kernel_variant(const cs_engine *eng) {
 }
 template <int MODE>
 const void *kernel_of(const cs_engine *eng) {  // plans with filters take the kernels that decide them
+  if (eng->ends) return kernel_variant<MODE, csdev::FILT_ENDS>(eng);  // (... and whatever filters the plan has)
   if (!eng->filters) return kernel_variant<MODE, csdev::FILT_NONE>(eng);
   if (eng->filters == CS_X_TOO_MANY_N) return kernel_variant<MODE, csdev::FILT_MAXN>(eng);
   return kernel_variant<MODE, csdev::FILT_ALL>(eng);
@@ -978,6 +984,7 @@ int cs_engine_create(const cs_plan *plan, int device, uint32_t n_slots, uint32_t
     for (int i = 0; i < plan->host.n_ops[mt]; ++i) {
       const csdev::DevOp &d = plan->host.ops[mt][i];
       if (d.op.kind == CS_OP_DEMUX) eng->demux_mate = mt;
+      if (d.op.kind == CS_OP_NTRIM || (d.op.kind == CS_OP_QTRIM && d.op.q_cutoff_front != 0)) eng->ends = true;
       if (d.op.kind == CS_OP_DEMUX && d.filter_mode) {
         // the resolve kernel runs the barcodes' own ops, one column per lane
         has_long_demux = true;
@@ -1820,7 +1827,9 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
       la.plan_slot = (uint32_t)eng->plan_slot;
       la.mate = m;
       la.gate = &s.d_meta->err;
-      if (eng->filters & (CS_X_TOO_LONG | CS_X_TOO_MANY_EE))
+      if (eng->ends)  // (a front cutoff or a CS_OP_NTRIM op: the walk that knows them, with every filter)
+        hipLaunchKernelGGL((cslong::long_kernel<true, true>), dim3(256), dim3(64), 0, st, la);
+      else if (eng->filters & (CS_X_TOO_LONG | CS_X_TOO_MANY_EE))
         hipLaunchKernelGGL(cslong::long_kernel<true>, dim3(256), dim3(64), 0, st, la);
       else
         hipLaunchKernelGGL(cslong::long_kernel<false>, dim3(256), dim3(64), 0, st, la);
@@ -1880,7 +1889,11 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
       ia.cap = t->info_cap;
       HIP_TRY(hipMemsetAsync(s.d_imeta, 0, sizeof(csinfo::InfoMeta), rs));
       const dim3 rec_grid((n_records + 63u) / 64u);
-      if (eng->info_max_m <= 48u)
+      if (eng->ends && eng->info_max_m <= 48u)
+        hipLaunchKernelGGL((csinfo::info_record<48, true>), rec_grid, dim3(64), 0, rs, fa, t->tp, ia);
+      else if (eng->ends)
+        hipLaunchKernelGGL((csinfo::info_record<CS_MAX_ADAPTER, true>), rec_grid, dim3(64), 0, rs, fa, t->tp, ia);
+      else if (eng->info_max_m <= 48u)
         hipLaunchKernelGGL(csinfo::info_record<48>, rec_grid, dim3(64), 0, rs, fa, t->tp, ia);
       else
         hipLaunchKernelGGL(csinfo::info_record<CS_MAX_ADAPTER>, rec_grid, dim3(64), 0, rs, fa, t->tp, ia);

@@ -138,7 +138,7 @@ struct Recorder {  // what info_record keeps of a walk: every match, and the byt
   __device__ __forceinline__ void quality_trimmed(int) {}
 };
 
-template <int kMaxM>
+template <int kMaxM, bool ENDS = false>
 __global__ void __launch_bounds__(64) info_record(FormatArgs a, TextParams tp, InfoArgs ia) {
   if (a.meta->err != ~0ull) return;
   const uint32_t r = blockIdx.x * 64u + threadIdx.x;
@@ -150,7 +150,7 @@ __global__ void __launch_bounds__(64) info_record(FormatArgs a, TextParams tp, I
   const ReadView v = cstext::read_view(a, 0, r);  // what the trimming kernels made of the record
   const uint32_t per_base = ia.no_qual ? 1u : 2u;
   Recorder ev{ia.match + (size_t)r * ia.n_adapters, ia.n_adapters, ia.uniq_flags, v.flags, per_base, kMaxM};
-  const cslong::Walk w = cslong::walk_chain<kMaxM>(plan, 0, env, a.text[0] + rc.seq_off, a.text[0] + rc.qual_off,
+  const cslong::Walk w = cslong::walk_chain<kMaxM, ENDS>(plan, 0, env, a.text[0] + rc.seq_off, a.text[0] + rc.qual_off,
                                                    (int)(slot != cstext::kNotLong ? a.lrec[0][slot].len : (uint32_t)rc.len), ev);
   // the table must not disagree with the records next to it
   if ((uint32_t)w.s != v.start || (uint32_t)w.e != v.stop || w.flags != v.flags) cstext::report(a.meta, r, ERR_INFO_MISMATCH);

@@ -177,7 +177,7 @@ __device__ __forceinline__ bool find_exact(const cs_op &op, const Env &v, const 
   return false;
 }
 
-// cutadapt quality_trim_index (cutoff_front = 0) on qual[0, n): BWA running sum from the 3' end, first strict maximum.
+// cutadapt quality_trim_index, the 3' walk on qual[0, n): BWA running sum from the 3' end, first strict maximum.
 // A term is at most 256 in size (cs_plan_create clamps the cutoff), a read at most CS_MAX_READ = 2^24 bases: the sum
 // reaches 2^32, so it is a 64-bit sum.
 __device__ __forceinline__ int quality_stop(const cs_op &op, const uint8_t *qual, int n) {
@@ -192,6 +192,22 @@ __device__ __forceinline__ int quality_stop(const cs_op &op, const uint8_t *qual
     }
   }
   return stop;
+}
+
+// ... and its 5' walk (cs_op.q_cutoff_front != 0 only): forward over the same qual[0, n), whatever the 3' walk decided;
+// start = one behind the first strict maximum.  The same terms, the same 64-bit sum.
+__device__ __forceinline__ int quality_start(const cs_op &op, const uint8_t *qual, int n) {
+  long long sum = 0, best = 0;
+  int start = 0;
+  for (int i = 0; i < n; ++i) {
+    sum += (int)op.q_cutoff_front - ((int)qual[i] - (int)op.q_base);
+    if (sum < 0) break;
+    if (sum > best) {
+      best = sum;
+      start = i + 1;
+    }
+  }
+  return start;
 }
 
 // Where a demultiplexing table keeps the first `depth` bases of q[0, n) -- read from the 5' end, or backwards from the
@@ -224,7 +240,9 @@ struct Walk {  // a read on its way through the chain
 //   cut(op, off, c)            a cutter took c bases at off
 //   quality_trimmed(k)         the quality trimmer took k bases
 //   demux(d, v, seq, w)        a CS_OP_DEMUX op, the caller's to apply (Events::kDemux; compiled out where false)
-template <int kMaxM, class Events>
+// ENDS: the instantiation for plans with a front cutoff or a CS_OP_NTRIM op (cs_engine::ends), the only one that holds
+// their code; every other plan runs the walk it ran before they came.
+template <int kMaxM, bool ENDS, class Events>
 __device__ __forceinline__ Walk walk_chain(const DevPlan *plan, int mate, const Env &v, const uint8_t *seq, const uint8_t *qual,
                                            int len, Events &ev) {
   Walk w = {0, len, 0u, 0};
@@ -273,10 +291,28 @@ __device__ __forceinline__ Walk walk_chain(const DevPlan *plan, int mate, const 
     } else if (op.kind == CS_OP_DEMUX) {
       if constexpr (Events::kDemux) ev.demux(d, v, seq, w);
     } else if (op.kind == CS_OP_QTRIM) {
-      const int stop = quality_stop(op, qual + w.s, n);
-      if (stop < n) w.flags |= CS_F_QTRIMMED;
-      ev.quality_trimmed(n - stop);
+      int stop = quality_stop(op, qual + w.s, n), start = 0;
+      if constexpr (ENDS) {
+        if (op.q_cutoff_front != 0) {  // cutadapt -q FRONT,BACK; 0: the reference's op, no front walk
+          start = quality_start(op, qual + w.s, n);
+          if (start >= stop) start = stop = 0;  // the two walks crossed: nothing is left, reported as [s, s)
+        }
+      }
+      if (stop - start < n) w.flags |= CS_F_QTRIMMED;
+      ev.quality_trimmed(n - (stop - start));
       w.e = w.s + stop;
+      w.s += start;
+    } else if (op.kind == CS_OP_NTRIM) {  // cutadapt's NEndTrimmer: the runs of 'N' (upper case only) at both ends
+      if constexpr (ENDS) {
+        int lead = 0;
+        while (lead < n && seq[w.s + lead] == 0x4Eu) ++lead;
+        if (lead == n) {
+          w.e = w.s;
+        } else {
+          while (seq[w.e - 1] == 0x4Eu) --w.e;
+          w.s += lead;
+        }
+      }
     }
   }
   if (w.e - w.s < (int)plan->params.min_length) w.flags |= CS_F_TOO_SHORT;
@@ -375,7 +411,7 @@ struct LongEvents {  // what long_kernel keeps of a walk besides the interval an
 
 // MORE: the instantiation that also decides TooLong and TooManyExpectedErrors (plans with cs_plan_set_max_length or
 // cs_plan_set_max_ee); every other plan runs the kernel it ran before those filters came.
-template <bool MORE>
+template <bool MORE, bool ENDS = false>
 __global__ void __launch_bounds__(64) long_kernel(LongArgs a) {
   if (a.gate && *a.gate != ~0ull) return;
   const DevPlan *plan = &csdev::c_plans[a.plan_slot];
@@ -385,7 +421,7 @@ __global__ void __launch_bounds__(64) long_kernel(LongArgs a) {
     const LongRec lr = a.rec[it];
     const uint8_t *seq = a.text + lr.seq_off;
     LongEvents ev{a.stats};
-    const Walk w = walk_chain<CS_MAX_ADAPTER>(plan, a.mate, v, seq, a.text + lr.qual_off, (int)lr.len, ev);
+    const Walk w = walk_chain<CS_MAX_ADAPTER, ENDS>(plan, a.mate, v, seq, a.text + lr.qual_off, (int)lr.len, ev);
     uint32_t xflags = 0;
     if (plan->max_n_on) {  // TooManyN on the final interval: the read's own bytes, up to CS_MAX_READ of them
       uint32_t nn = 0;

@@ -25,7 +25,8 @@
 //              - otherwise: one lane per survivor, column in LDS
 //              both compute cutadapt's exact (cost, score, origin) cells inside the window
 //   CUT / conditional CUT: interval arithmetic on [s, e);  DEMUX: table look-up on the first m + k bases
-//   QTRIM: BWA running sum on packed (sum, position) keys
+//   QTRIM: BWA running sum on packed (sum, position) keys; with a front cutoff (FILT_ENDS kernels only) a second,
+//          forward walk from the 5' end.  NTRIM (FILT_ENDS kernels only): the runs of 'N' at both ends of [s, e)
 //
 // No block-wide barrier is needed after staging.  Result: 8 bytes per read.  Integer work: no MFMA.
 
@@ -2498,8 +2499,10 @@ enum { MODE_SCAN = 0, MODE_RESOLVE = 1 };
 #endif
 // FILT: the filters of the final interval this instantiation decides.  0: none (the code every plan without a filter
 // runs); 1: TooManyN alone (what a plan with cs_plan_set_max_n and nothing else runs); 2: any set of TooLong, TooManyN
-// and TooManyExpectedErrors, chosen at run time from the plan.
-enum { FILT_NONE = 0, FILT_MAXN = 1, FILT_ALL = 2 };
+// and TooManyExpectedErrors, chosen at run time from the plan; 3: the same, plus the two read-end modifiers of
+// include/cutseq_hip.h -- the quality trimmer's front walk (CS_OP_QTRIM with a q_cutoff_front) and CS_OP_NTRIM -- for the
+// plans that hold one (cutadapt -q FRONT,BACK and --trim-n): their code exists in these instantiations alone.
+enum { FILT_NONE = 0, FILT_MAXN = 1, FILT_ALL = 2, FILT_ENDS = 3 };
 template <bool CODED, bool WIDE, int MODE, int FILT>
 __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) trim_kernel(KArgs a) {
   if (a.gate && *a.gate != ~0ull) return;  // (wave-uniform: one wave per block)
@@ -3405,12 +3408,80 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
         }
         if (live && (bestkey >> kPosBits) > 0) stop = (bestkey & ((1 << kPosBits) - 1)) - s;
       }
-      if (on) {
+      if constexpr (FILT == FILT_ENDS) {
+        // The 5' walk of quality_trim_index (cutoff_front), for ops that have one: forward from s over the WHOLE interval
+        // the op saw, whatever the 3' walk above decided -- sum += cutoff_front - (q[i] - base), stop at the first
+        // negative sum, start = one behind the first strict maximum.  One lane per read, dwords straight from the read's
+        // row like the walk above, the bytes of the first and last dword outside [s, e) passed over; 5' ends are the
+        // good end of a read, a walk is expected to end in its first dword.  A plain int sum: at most kQTermMax a base
+        // over a row, the bound of the 3' key's sum.  (The cutoff is the high half of the op's last dword: a scalar load.)
+        static_assert(offsetof(cs_op, q_cutoff_front) == 282 && sizeof(cs_op) == 284, "cs_op: q_cutoff_front ends the struct");
+        const int front = (int)reinterpret_cast<const uint32_t *>(&d.op)[70] >> 16;
+        int start = 0;
+        if (front != 0) {  // wave-uniform; 0: the reference's op, no byte is looked at
+          const int cf = front + (int)op.q_base;
+          if (on && n > 0) {
+            const int d_last = (e - 1) >> 2;
+            int sum = 0, best = 0;
+            bool dead = false;
+            for (int dwf = s >> 2; dwf <= d_last && !dead; ++dwf) {
+              const uint32_t w = q[dwf];
+#pragma unroll
+              for (int b = 0; b < 4; ++b) {
+                const int p = 4 * dwf + b;
+                const bool in = !dead && p >= s && p < e;
+                const int nsum = sum + cf - (int)((w >> (b * 8)) & 0xffu);
+                dead = dead || (in && nsum < 0);
+                const bool on_b = in && !dead;
+                sum = on_b ? nsum : sum;
+                const bool up = on_b && sum > best;
+                best = up ? sum : best;
+                start = up ? p + 1 - s : start;
+              }
+            }
+          }
+          if (start >= stop) start = stop = 0;  // (the two walks crossed: nothing is left, reported as [s, s))
+        }
+        if (on) {
+          if (stop - start < n) fm |= CS_F_QTRIMMED;
+          qc += (uint32_t)(n - (stop - start));
+          e = s + stop;
+          s += start;
+        }
+      } else if (on) {
         if (stop < n) fm |= CS_F_QTRIMMED;
         qc += (uint32_t)(n - stop);
         e = s + stop;
       }
       CS_T_MARK(pt, 5);
+    } else if (kind == CS_OP_NTRIM) {
+      if constexpr (FILT == FILT_ENDS) {
+        // cutadapt's NEndTrimmer: the runs of 'N' (upper case only) at both ends of [s, e) go.  A fast-form coded tile
+        // vouches for every byte being A, C, G, T or N, code 7 is 'N' and nothing else (count_n_nibbles); everywhere else
+        // -- raw tiles fold case, exact-form tiles and the resolve kernel's mix codes 4..7 -- the read's own bytes decide.
+        // A read without an N at either end, nearly every read, costs one test per end.
+        // (The choice is made ONCE, on a scalar: as a wave-uniform bool tested inside the two loops below it was kept in a
+        // lane mask that the first loop rewrote under its shrinking exec mask, and lanes that had left that loop early
+        // took the tile's codes on an exact-form tile in the second one -- an 'n' next to a trimmed 'N' went with it.)
+        const bool vouched = __builtin_amdgcn_readfirstlane((SCAN && CODED && a.fast_recode == 1u && !fast_failed) ? 1 : 0) != 0;
+        const uint8_t *bytes = reinterpret_cast<const uint8_t *>(ma.seq + (size_t)gr * a.stride_dw);
+        auto trim_ends = [&](auto is_n) {
+          if (on && n > 0) {
+            int lead = 0;
+            while (lead < n && is_n(s + lead)) ++lead;
+            if (lead == n) {
+              e = s;
+            } else {  // (some base of the interval is no N: the walk from the end stops there at the latest)
+              s += lead;
+              while (e > s && is_n(e - 1)) --e;
+            }
+          }
+        };
+        if (vouched)
+          trim_ends([&](int pos) -> bool { return ((myrow[pos >> 3] >> ((pos & 7) << 2)) & 7u) == 7u; });
+        else
+          trim_ends([&](int pos) -> bool { return bytes[pos] == 0x4Eu; });
+      }
     }
   }
 
@@ -3477,7 +3548,7 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
     const uint32_t w_many = wave_count(many);
     if (lane == 0 && w_many) atomicAdd(&sacc[ST_TOO_MANY_N], w_many);
     uint32_t xf = many ? (uint32_t)CS_X_TOO_MANY_N : 0u;
-    if constexpr (FILT == FILT_ALL) {
+    if constexpr (FILT == FILT_ALL || FILT == FILT_ENDS) {
       const bool is_long = fin && plan->max_length_on && e > s && (uint32_t)(e - s) > plan->max_length;
       bool errs = false;
       if (plan->max_ee_on && ma.qual) {  // the read's own quality row, as the quality trimmer reads it

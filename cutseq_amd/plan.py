@@ -3,7 +3,7 @@
 Counterpart of the modifier-list assembly in the reference's ``pipeline_single``
 (cutseq/run.py:326-426) and ``pipeline_paired`` (cutseq/run.py:533-731).  Where the
 reference instantiates cutadapt ``Modifier`` objects, this module emits plain
-descriptors (:class:`AdapterOp`, :class:`CutOp`, :class:`QTrimOp`) in the same order;
+descriptors (:class:`AdapterOp`, :class:`CutOp`, :class:`QTrimOp`, :class:`NTrimOp`) in the same order;
 ``TrimPlan.pack()`` turns them into the ``cs_op`` POD table of ``include/cutseq_hip.h``.
 Header work (SuffixRemover, Renamer) stays on the host and is described by
 ``MateChain.name_suffixes`` / ``TrimPlan.has_umi``.
@@ -52,6 +52,10 @@ class CutadaptConfig:
         # cutadapt -M / --max-length and --max-ee: TooLong(max_length), TooManyExpectedErrors(max_ee), both mates
         self.max_length = None
         self.max_ee = None
+        # cutadapt -q FRONT,BACK: the quality trimmer's 5' cutoff (0 = the reference's op); --trim-n: an NEndTrimmer
+        # behind the quality trimmer of every mate
+        self.min_quality_front = 0
+        self.trim_n = False
 
 
 @dataclass
@@ -128,9 +132,18 @@ class CutOp:
 class QTrimOp:
     cutoff_back: int
     base: int = 33
+    cutoff_front: int = 0
 
     def __repr__(self):
-        return f"QualityTrimmer(cutoff_front=0, cutoff_back={self.cutoff_back}, base={self.base})"
+        return f"QualityTrimmer(cutoff_front={self.cutoff_front}, cutoff_back={self.cutoff_back}, base={self.base})"
+
+
+@dataclass
+class NTrimOp:
+    """cutadapt's ``NEndTrimmer()`` (``--trim-n``): the runs of upper-case ``N`` at both ends of the read go."""
+
+    def __repr__(self):
+        return "NEndTrimmer()"
 
 
 @dataclass
@@ -185,7 +198,7 @@ class DemuxOp:
                 f"max_error_rate={self.max_error_rate}))")
 
 
-Op = Union[AdapterOp, CutOp, QTrimOp, DemuxOp]
+Op = Union[AdapterOp, CutOp, QTrimOp, DemuxOp, NTrimOp]
 
 
 def info_adapter_names(ops: Sequence["Op"]) -> dict:
@@ -321,7 +334,10 @@ def pack_ops(ops: Sequence[Op], limit: int = abi.CS_MAX_OPS):
         elif isinstance(op, QTrimOp):
             c.kind = abi.CS_OP_QTRIM
             c.q_cutoff = max(-0x8000, min(int(op.cutoff_back), 0x7FFF))
+            c.q_cutoff_front = max(-0x8000, min(int(op.cutoff_front), 0x7FFF))
             c.q_base = op.base
+        elif isinstance(op, NTrimOp):
+            c.kind = abi.CS_OP_NTRIM
         else:  # pragma: no cover
             raise TypeError(op)
     return arr
@@ -436,7 +452,9 @@ def compile_single(barcode: BarcodeConfig, settings: CutadaptConfig, untrimmed_r
         else:
             logging.info("No strand information provided, skip polyA trimming.")
     # step 8
-    ops.append(QTrimOp(settings.min_quality))
+    ops.append(QTrimOp(settings.min_quality, cutoff_front=getattr(settings, "min_quality_front", 0)))
+    if getattr(settings, "trim_n", False):  # (cutadapt puts --trim-n behind the adapter work; here: behind step 8)
+        ops.append(NTrimOp())
     # step 9
     rc = False
     if settings.auto_rc:
@@ -519,8 +537,12 @@ def compile_paired(barcode: BarcodeConfig, settings: CutadaptConfig, untrimmed_r
         else:
             logging.info("No strand information provided, skip polyA trimming.")
     # step 8
-    o1.append(QTrimOp(settings.min_quality))
-    o2.append(QTrimOp(settings.min_quality))
+    front = getattr(settings, "min_quality_front", 0)
+    o1.append(QTrimOp(settings.min_quality, cutoff_front=front))
+    o2.append(QTrimOp(settings.min_quality, cutoff_front=front))
+    if getattr(settings, "trim_n", False):
+        o1.append(NTrimOp())
+        o2.append(NTrimOp())
     # step 9: no modifier in paired mode, only the output files swap
     swap = False
     if settings.auto_rc:

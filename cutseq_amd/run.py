@@ -51,8 +51,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("-u", "--untrimmed-file", type=str, nargs="+",
                    help="Output file path(s) for reads discarded because expected inline barcodes were not found.")
     p.add_argument("--json-file", type=str, help="Output JSON file for trimming statistics.")
-    p.add_argument("-q", "--min-quality", type=int, default=20,
-                   help="Minimum quality score for trimming read tails. (Default: 20)")
+    p.add_argument("-q", "--min-quality", action=_QualityCutoffs, default=20, metavar="[5'CUTOFF,]3'CUTOFF",
+                   help="Minimum quality score for trimming read tails. (Default: 20) Extension (cutadapt's form of "
+                        "the option): two values separated by a comma trim the 5' end with the first cutoff and the "
+                        "3' end with the second.")
+    p.set_defaults(min_quality_front=0)
     p.add_argument("-m", "--min-length", type=int, default=20,
                    help="Minimum length of reads to keep after trimming. (Default: 20)")
     p.add_argument("--with-rname-suffix", action="store_true",
@@ -98,6 +101,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Extension (cutadapt's option): discard reads whose expected number of errors, the sum of "
                         "10^(-Q/10) over the trimmed read's qualities, exceeds ERRORS. A pair is discarded if either "
                         "read has too many. Needs an input with qualities.")
+    p.add_argument("--trim-n", action="store_true",
+                   help="Extension (cutadapt's option): trim N's at both ends of the reads, after adapter and quality "
+                        "trimming and before the length and N filters.")
     p.add_argument("--info-file", type=str, default=None, metavar="FILE",
                    help="Extension (cutadapt's option; a TODO of the reference): write a tab-separated table of the "
                         "adapter matches of read 1 to FILE, one row per match, in input order; reads without a match "
@@ -109,6 +115,22 @@ def build_parser() -> argparse.ArgumentParser:
                         "reads without any of the barcodes to the untrimmed files. Equals one --ensure-inline-barcode "
                         "run per barcode.")
     return p
+
+
+class _QualityCutoffs(argparse.Action):
+    """``-q BACK`` or ``-q FRONT,BACK`` (cutadapt's ``-q [5'CUTOFF,]3'CUTOFF``): ``min_quality`` stays the 3' int, the 5'
+    value goes to ``min_quality_front``.  Anything else is an argparse error, like a non-integer was before."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        parts = values.split(",")
+        try:
+            cutoffs = [int(part) for part in parts]
+        except ValueError:
+            raise argparse.ArgumentError(self, f"invalid int value: {values!r}")
+        if len(cutoffs) > 2:
+            raise argparse.ArgumentError(self, f"expected one value or two separated by a comma: {values!r}")
+        namespace.min_quality = cutoffs[-1]
+        namespace.min_quality_front = cutoffs[0] if len(cutoffs) == 2 else 0
 
 
 # Output naming (user-visible contract of the reference CLI, run.py:1058-1107): for every output class the
@@ -210,6 +232,8 @@ def settings_from_args(args) -> CutadaptConfig:
     st.threads = args.threads if args.threads is not None else 0
     st.min_length = args.min_length
     st.min_quality = args.min_quality
+    st.min_quality_front = getattr(args, "min_quality_front", 0)
+    st.trim_n = getattr(args, "trim_n", False)
     st.dry_run = args.dry_run
     st.auto_rc = args.auto_rc
     st.json_file = args.json_file

@@ -50,7 +50,26 @@ typedef enum cs_status {
 
 /* ---- op table: what cutseq/run.py:305-433 (single) and :493-731 (paired) compile -- */
 
-enum { CS_OP_ADAPTER = 1, CS_OP_CUT = 2, CS_OP_QTRIM = 3, CS_OP_DEMUX = 4 };
+enum { CS_OP_ADAPTER = 1, CS_OP_CUT = 2, CS_OP_QTRIM = 3, CS_OP_DEMUX = 4, CS_OP_NTRIM = 5 };
+
+/* CS_OP_QTRIM -- cutadapt's QualityTrimmer(cutoff_front, cutoff_back, base), quality_trim_index on the interval [s, e)
+ * the op sees (n = e - s, qualities q[0..n)):
+ *     back:   sum = best = 0, stop = n;  for i = n - 1 down to 0: sum += q_cutoff - (q[i] - q_base); break if sum < 0;
+ *             if sum > best: best = sum, stop = i
+ *     front:  sum = best = 0, start = 0; for i = 0 .. n - 1: sum += q_cutoff_front - (q[i] - q_base); break if sum < 0;
+ *             if sum > best: best = sum, start = i + 1
+ * Both walks run over the WHOLE interval, independently.  start >= stop: the read is empty, reported as [s, s);
+ * otherwise [s + start, s + stop) is left.  cs_stats.qualtrim_bp gains n - (stop - start), CS_F_QTRIMMED says that it is
+ * more than 0.  q_cutoff_front == 0 is the reference's op (cutseq installs cutoff_front = 0): the front walk does not run
+ * at all -- its result would be start = 0 for every quality byte >= q_base -- and the kernels launched are those of a
+ * plan without it.  cs_plan_create clamps both cutoffs to cutoff + q_base in [-1, 256] (outside, every term has one sign:
+ * no result changes).
+ *
+ * CS_OP_NTRIM -- cutadapt's NEndTrimmer (--trim-n), no fields: the leading run a and the trailing run b of the byte 'N'
+ * (0x4E; upper case only: cutadapt's patterns are ^N+ and N+$ without IGNORECASE -- TooManyN counts 'n' too) of
+ * seq[s:e) go: a == e - s leaves [s, s), anything else [s + a, e - b).  No counter and no flag of its own: out_bp,
+ * TooShort and the filters see the result.  A plan with a non-zero q_cutoff_front or a CS_OP_NTRIM op runs kernels of
+ * its own; every other plan the kernels it ran before these came. */
 
 /* CS_OP_DEMUX -- extension, not a reference capability (BASELINE.json config 5): ONE pass
  * decides which of up to 255 equally long inline barcodes starts the read, where the reference would
@@ -144,10 +163,12 @@ typedef struct cs_op {
   uint16_t min_overlap;  /* ADAPTER: already capped to m                              */
   int16_t cut_len;       /* CUT: >0 from the 5' end, <0 from the 3' end               */
   uint16_t force_min_len;/* CUT (conditional): force_trim_min_length                  */
-  int16_t q_cutoff;      /* QTRIM: cutoff_back (cutoff_front is 0 in cutseq)          */
+  int16_t q_cutoff;      /* QTRIM: cutoff_back (3' end); cutoff_front: q_cutoff_front below */
   uint8_t seq[CS_MAX_ADAPTER];     /* ADAPTER: upper-cased bases                      */
   uint8_t thr[CS_MAX_ADAPTER + 1]; /* ADAPTER: thr[L] = floor(L * max_error_rate) in IEEE double */
-  uint8_t _pad[3];
+  uint8_t _pad[1];
+  int16_t q_cutoff_front; /* QTRIM: cutoff_front (5' end); 0 = the reference's op, no front walk (carved out of the
+                             padding: a table written before the field existed holds 0 here) */
 } cs_op;
 
 typedef struct cs_params {

@@ -5,6 +5,12 @@ with each filter alone and with all three, alternating.  Prints one JSON line pe
 scan and resolve kernel ms per call, reads flagged per call and mate.
 
   python tools/filters_ab.py [--pairs 20000000] [--steps 20] [--warmup 5] [--rounds 3] [--max-length 100] [--max-ee 1]
+
+--ends: the read-end modifiers instead (-q FRONT,BACK and --trim-n): the plan without them, with -q FRONT,20, with
+--trim-n and with both, and -- from a sample of the same reads -- the share of reads whose 5' walk leaves the first
+quality dword of the interval the trimmer sees (the walk is one lane per read: tools/README.md).
+
+  python tools/filters_ab.py --ends [--front 20] [--sample 1000000]
 """
 from __future__ import annotations
 
@@ -25,9 +31,53 @@ from cutseq_amd import abi, synth, workloads  # noqa: E402
 from cutseq_amd.engine import TrimEngine  # noqa: E402
 
 
-def leg(d, n, stride, filters, steps, warmup, with_xflags):
+def plan_for(filters):
+    from cutseq_amd import plan as planmod
     tp = workloads.make_plan("config3")
     tp.max_length, tp.max_n, tp.max_ee = filters.get("max_length"), filters.get("max_n"), filters.get("max_ee")
+    for chain in (tp.r1, tp.r2):
+        if filters.get("drop_qtrim"):
+            chain.ops = [o for o in chain.ops if not isinstance(o, planmod.QTrimOp)]
+        for o in chain.ops:
+            if isinstance(o, planmod.QTrimOp):
+                o.cutoff_front = filters.get("front", 0)
+        if filters.get("trim_n"):
+            chain.ops = chain.ops + [planmod.NTrimOp()]
+    return tp
+
+
+def front_walk_share(d, n, stride, front, base=33):
+    """Of the first n pairs: the share of reads (both mates) whose front walk under ``front`` reads more than the first
+    quality dword of the interval the trimmer sees -- its sum is not negative anywhere in that dword and the interval
+    goes on behind it.  The intervals come from the plan without its quality trimmer."""
+    import numpy as np
+    dev = torch.device("cuda:0")
+    outs = [torch.empty((n, 8), dtype=torch.uint8, device=dev) for _ in range(2)]
+    rr = [abi.cs_reads(d[f"seq{m}"].data_ptr(), d[f"qual{m}"].data_ptr(), d[f"len{m}"].data_ptr(), outs[m - 1].data_ptr(),
+                       None, None, None) for m in (1, 2)]
+    with TrimEngine(plan_for({"drop_qtrim": True}), device=0, slots=0) as eng:
+        eng.trim_device(rr[0], rr[1], n, stride)
+        torch.cuda.synchronize(dev)
+    beyond = total = 0
+    for m in (1, 2):
+        res = outs[m - 1].cpu().numpy().view(abi.RESULT_DTYPE).reshape(-1)
+        q = d[f"qual{m}"][:n].cpu().numpy().astype(np.int64)
+        s, e = res["start"].astype(np.int64), res["stop"].astype(np.int64)
+        first_end = np.minimum(e, (s | 3) + 1)  # end of the interval's part inside its first dword
+        alive = e > s
+        run = np.zeros(n, dtype=np.int64)
+        for b in range(4):
+            p = s + b
+            inside = alive & (p < first_end)
+            run = np.where(inside, run + front + base - q[np.arange(n), np.minimum(p, stride - 1)], run)
+            alive = alive & ~(inside & (run < 0))
+        beyond += int((alive & (e > first_end)).sum())
+        total += int((e > s).sum())
+    return beyond / max(total, 1)
+
+
+def leg(d, n, stride, filters, steps, warmup, with_xflags):
+    tp = plan_for(filters)
     dev = torch.device("cuda:0")
     sets = []
     for _ in range(3):
@@ -72,6 +122,9 @@ def main():
     ap.add_argument("--max-length", type=int, default=100)
     ap.add_argument("--max-ee", type=float, default=1.0)
     ap.add_argument("--xflags", action="store_true", help="also write cs_reads.xflags (the text path does)")
+    ap.add_argument("--ends", action="store_true", help="the legs of -q FRONT,20 and --trim-n instead of the filters'")
+    ap.add_argument("--front", type=int, default=20, help="--ends: the 5' cutoff")
+    ap.add_argument("--sample", type=int, default=1_000_000, help="--ends: pairs the front-walk share is counted on")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     n = args.pairs
@@ -84,6 +137,12 @@ def main():
     legs = (("off", {}), ("max_n", {"max_n": args.max_n}), ("max_length", {"max_length": args.max_length}),
             ("max_ee", {"max_ee": args.max_ee}),
             ("all", {"max_length": args.max_length, "max_n": args.max_n, "max_ee": args.max_ee}))
+    if args.ends:
+        legs = (("off", {}), ("q_front", {"front": args.front}), ("trim_n", {"trim_n": True}),
+                ("both", {"front": args.front, "trim_n": True}))
+        share = front_walk_share(d, min(n, args.sample), stride, args.front)
+        print(json.dumps({"front_walk_beyond_first_dword": round(share, 5), "front": args.front,
+                          "sample_pairs": min(n, args.sample)}), flush=True)
     res = {key: [] for key, _ in legs}
     for _ in range(args.rounds):
         for key, filters in legs:

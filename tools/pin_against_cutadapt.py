@@ -172,7 +172,10 @@ def build_chain(barcode, settings, paired: bool, untrimmed_requested: bool = Fal
             each(head(), tail())
     # step 8
     q = _get(settings, "min_quality", 20)
-    each(M.QualityTrimmer(cutoff_front=0, cutoff_back=q), M.QualityTrimmer(cutoff_front=0, cutoff_back=q))
+    qf = _get(settings, "min_quality_front", 0)  # (-q FRONT,BACK; 0: the reference's trimmer)
+    each(M.QualityTrimmer(cutoff_front=qf, cutoff_back=q), M.QualityTrimmer(cutoff_front=qf, cutoff_back=q))
+    if _get(settings, "trim_n", False):  # --trim-n: behind the quality trimmer, as cutseq_amd.plan compiles it
+        each(M.NEndTrimmer(), M.NEndTrimmer())
     # step 9
     swap = False
     if _get(settings, "auto_rc", False) and barcode.strand == "-":
@@ -302,7 +305,9 @@ def collect_cases(n_synth: int = 2000):
     from test_oracle import CHAIN_CASES
     cases = []
     rec1, rec2 = fixture_records()
-    for flags in ({}, {"trim_polyA": True}):
+    # (the last two: QualityTrimmer(cutoff_front=F, ...) and NEndTrimmer(), -q F,B and --trim-n -- recalled rules)
+    for flags in ({}, {"trim_polyA": True}, {"min_quality_front": 15, "min_quality": 10},
+                  {"min_quality_front": 20, "trim_n": True}):
         cases.append(chain_case(f"fixture10k/TAKARAV3/{sorted(flags)}", BUILDIN_ADAPTERS["TAKARAV3"], flags, True,
                                 {"fixture": "fixture10k"}, rec1, rec2))
     for idx, (name, flags, paired) in enumerate(CHAIN_CASES):
