@@ -14,7 +14,9 @@ CS_MAX_STRIDE = 1536
 CS_LEN_SKIP = 0xFFFF
 CS_MAX_READ = 1 << 24
 
-CS_OP_ADAPTER, CS_OP_CUT, CS_OP_QTRIM, CS_OP_DEMUX, CS_OP_NTRIM = 1, 2, 3, 4, 5
+CS_OP_ADAPTER, CS_OP_CUT, CS_OP_QTRIM, CS_OP_DEMUX, CS_OP_NTRIM, CS_OP_NEXTSEQ = 1, 2, 3, 4, 5, 6
+# cutoff + base of a quality-trimming op: CS_OP_QTRIM is clamped to this range, CS_OP_NEXTSEQ refused outside it
+CS_Q_SUM_LOW, CS_Q_SUM_HIGH = -1, 256
 CS_DEMUX_NONE = 0xFF
 CS_DEMUX_MAX_PREFIX = 11
 CS_DEMUX_MAX_LONG = 24

@@ -135,6 +135,7 @@ struct cs_engine {
   bool wide = false;  // some adapter needs 64-bit bit-vectors
   uint32_t filters = 0;  // CS_X_* bits of the plan's filters (cs_plan_set_max_length / _max_n / _max_ee)
   bool ends = false;     // some CS_OP_QTRIM op has a front cutoff, or the plan has a CS_OP_NTRIM op (FILT_ENDS kernels)
+  bool nextseq = false;  // the plan has a CS_OP_NEXTSEQ op: `ends` is set too (the ENDS walks), tile kernels FILT_NEXTSEQ
   int n_cus = 256;
   uint32_t n_table_ops = 1;
   uint32_t col_dwords = 0;   // per-wave DP scratch the plan needs (resolve kernel)
@@ -253,6 +254,16 @@ int build_dev_op(const cs_op &in, csdev::DevOp &out, int index, int mate) {
     }
     case CS_OP_NTRIM:
       break;
+    case CS_OP_NEXTSEQ: {
+      // No clamp here: a 'G' adds +1 whatever the cutoff, so the terms never all have one sign and a clamped cutoff
+      // changes results (include/cutseq_hip.h).  Inside the range CS_OP_QTRIM is clamped to, every term is within
+      // kQTermMax, the bound both kernels' sums are built for; outside it the op is refused.
+      const int cq = (int)op.q_cutoff + (int)op.q_base;
+      if (cq < csdev::kQCutoffLow || cq > csdev::kQCutoffHigh)
+        return fail(CS_ERR_ARG, "mate %d op %d: nextseq cutoff %d with base %u (cutoff + base in [%d, %d])", mate, index,
+                    (int)op.q_cutoff, (unsigned)op.q_base, csdev::kQCutoffLow, csdev::kQCutoffHigh);
+      break;
+    }
     case CS_OP_DEMUX:
       if (op.m < 1 || op.k > op.m || op.m + op.k > CS_DEMUX_MAX_LONG)
         return fail(CS_ERR_ARG, "mate %d op %d: demux barcode length %u with %u errors (m + k <= %d)", mate, index, op.m,
@@ -283,6 +294,7 @@ const void *kernel_variant(const cs_engine *eng) {
 }
 template <int MODE>
 const void *kernel_of(const cs_engine *eng) {  // plans with filters take the kernels that decide them
+  if (eng->nextseq) return kernel_variant<MODE, csdev::FILT_NEXTSEQ>(eng);  // (the read-end ops' code plus CS_OP_NEXTSEQ)
   if (eng->ends) return kernel_variant<MODE, csdev::FILT_ENDS>(eng);  // (... and whatever filters the plan has)
   if (!eng->filters) return kernel_variant<MODE, csdev::FILT_NONE>(eng);
   if (eng->filters == CS_X_TOO_MANY_N) return kernel_variant<MODE, csdev::FILT_MAXN>(eng);
@@ -984,7 +996,9 @@ int cs_engine_create(const cs_plan *plan, int device, uint32_t n_slots, uint32_t
     for (int i = 0; i < plan->host.n_ops[mt]; ++i) {
       const csdev::DevOp &d = plan->host.ops[mt][i];
       if (d.op.kind == CS_OP_DEMUX) eng->demux_mate = mt;
-      if (d.op.kind == CS_OP_NTRIM || (d.op.kind == CS_OP_QTRIM && d.op.q_cutoff_front != 0)) eng->ends = true;
+      if (d.op.kind == CS_OP_NTRIM || d.op.kind == CS_OP_NEXTSEQ || (d.op.kind == CS_OP_QTRIM && d.op.q_cutoff_front != 0))
+        eng->ends = true;
+      if (d.op.kind == CS_OP_NEXTSEQ) eng->nextseq = true;
       if (d.op.kind == CS_OP_DEMUX && d.filter_mode) {
         // the resolve kernel runs the barcodes' own ops, one column per lane
         has_long_demux = true;

@@ -210,6 +210,23 @@ __device__ __forceinline__ int quality_start(const cs_op &op, const uint8_t *qua
   return start;
 }
 
+// cutadapt nextseq_trim_index (CS_OP_NEXTSEQ) on seq[0, n) / qual[0, n): quality_stop's walk in which a 'G' (upper case
+// only) adds 1 whatever its quality byte says.  The terms are within the same bound (cs_plan_create refuses a cutoff
+// outside the range it clamps CS_OP_QTRIM's to), the sum is the same 64-bit sum.
+__device__ __forceinline__ int quality_stop_nextseq(const cs_op &op, const uint8_t *seq, const uint8_t *qual, int n) {
+  long long sum = 0, best = 0;
+  int stop = n;
+  for (int i = n - 1; i >= 0; --i) {
+    sum += seq[i] == 0x47u ? 1 : (int)op.q_cutoff - ((int)qual[i] - (int)op.q_base);
+    if (sum < 0) break;
+    if (sum > best) {
+      best = sum;
+      stop = i;
+    }
+  }
+  return stop;
+}
+
 // Where a demultiplexing table keeps the first `depth` bases of q[0, n) -- read from the 5' end, or backwards from the
 // 3' end -- : the block of the prefixes of min(n, depth) bases, then the prefix in base 5 (A, C, G, T, anything else).
 __device__ __forceinline__ uint32_t prefix_index(const uint8_t *q, int n, int depth, bool from_end, bool fold) {
@@ -240,8 +257,8 @@ struct Walk {  // a read on its way through the chain
 //   cut(op, off, c)            a cutter took c bases at off
 //   quality_trimmed(k)         the quality trimmer took k bases
 //   demux(d, v, seq, w)        a CS_OP_DEMUX op, the caller's to apply (Events::kDemux; compiled out where false)
-// ENDS: the instantiation for plans with a front cutoff or a CS_OP_NTRIM op (cs_engine::ends), the only one that holds
-// their code; every other plan runs the walk it ran before they came.
+// ENDS: the instantiation for plans with a front cutoff, a CS_OP_NTRIM or a CS_OP_NEXTSEQ op (cs_engine::ends), the only
+// one that holds their code; every other plan runs the walk it ran before they came.
 template <int kMaxM, bool ENDS, class Events>
 __device__ __forceinline__ Walk walk_chain(const DevPlan *plan, int mate, const Env &v, const uint8_t *seq, const uint8_t *qual,
                                            int len, Events &ev) {
@@ -302,6 +319,13 @@ __device__ __forceinline__ Walk walk_chain(const DevPlan *plan, int mate, const 
       ev.quality_trimmed(n - (stop - start));
       w.e = w.s + stop;
       w.s += start;
+    } else if (op.kind == CS_OP_NEXTSEQ) {  // cutadapt's NextseqQualityTrimmer: the 3' walk that sees through 'G'
+      if constexpr (ENDS) {
+        const int stop = quality_stop_nextseq(op, seq + w.s, qual + w.s, n);
+        if (stop < n) w.flags |= CS_F_QTRIMMED;
+        ev.quality_trimmed(n - stop);
+        w.e = w.s + stop;
+      }
     } else if (op.kind == CS_OP_NTRIM) {  // cutadapt's NEndTrimmer: the runs of 'N' (upper case only) at both ends
       if constexpr (ENDS) {
         int lead = 0;

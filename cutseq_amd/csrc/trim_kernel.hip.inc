@@ -27,6 +27,7 @@
 //   CUT / conditional CUT: interval arithmetic on [s, e);  DEMUX: table look-up on the first m + k bases
 //   QTRIM: BWA running sum on packed (sum, position) keys; with a front cutoff (FILT_ENDS kernels only) a second,
 //          forward walk from the 5' end.  NTRIM (FILT_ENDS kernels only): the runs of 'N' at both ends of [s, e)
+//   NEXTSEQ (FILT_NEXTSEQ kernels only): QTRIM's 3' walk with the read's bases beside its qualities, a 'G' adds 1
 //
 // No block-wide barrier is needed after staging.  Result: 8 bytes per read.  Integer work: no MFMA.
 
@@ -2501,8 +2502,11 @@ enum { MODE_SCAN = 0, MODE_RESOLVE = 1 };
 // runs); 1: TooManyN alone (what a plan with cs_plan_set_max_n and nothing else runs); 2: any set of TooLong, TooManyN
 // and TooManyExpectedErrors, chosen at run time from the plan; 3: the same, plus the two read-end modifiers of
 // include/cutseq_hip.h -- the quality trimmer's front walk (CS_OP_QTRIM with a q_cutoff_front) and CS_OP_NTRIM -- for the
-// plans that hold one (cutadapt -q FRONT,BACK and --trim-n): their code exists in these instantiations alone.
-enum { FILT_NONE = 0, FILT_MAXN = 1, FILT_ALL = 2, FILT_ENDS = 3 };
+// plans that hold one (cutadapt -q FRONT,BACK and --trim-n): their code exists in these instantiations alone; 4: FILT 3's
+// code plus CS_OP_NEXTSEQ (cutadapt --nextseq-trim), for the plans that hold that op.  It has a value of its own because
+// inside FILT 3 its walk cost the -q 20,20 --trim-n plan 1.1 % of its throughput, three times the spread of the parent's
+// own runs (profiles/nextseq_ab.log).
+enum { FILT_NONE = 0, FILT_MAXN = 1, FILT_ALL = 2, FILT_ENDS = 3, FILT_NEXTSEQ = 4 };
 template <bool CODED, bool WIDE, int MODE, int FILT>
 __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) trim_kernel(KArgs a) {
   if (a.gate && *a.gate != ~0ull) return;  // (wave-uniform: one wave per block)
@@ -3408,7 +3412,7 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
         }
         if (live && (bestkey >> kPosBits) > 0) stop = (bestkey & ((1 << kPosBits) - 1)) - s;
       }
-      if constexpr (FILT == FILT_ENDS) {
+      if constexpr (FILT >= FILT_ENDS) {
         // The 5' walk of quality_trim_index (cutoff_front), for ops that have one: forward from s over the WHOLE interval
         // the op saw, whatever the 3' walk above decided -- sum += cutoff_front - (q[i] - base), stop at the first
         // negative sum, start = one behind the first strict maximum.  One lane per read, dwords straight from the read's
@@ -3454,8 +3458,126 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
         e = s + stop;
       }
       CS_T_MARK(pt, 5);
+    } else if (kind == CS_OP_NEXTSEQ) {
+      if constexpr (FILT == FILT_NEXTSEQ) {
+        // cutadapt's NextseqQualityTrimmer (--nextseq-trim): the 3' walk of the CS_OP_QTRIM branch above with one more
+        // input, the read's base at each position -- a 'G' adds 1 whatever its quality byte says.  The same top-dword
+        // exact step, the same wave walk (four live reads, 16 lanes each), the same (sum, position) key; wherever a
+        // quality dword is loaded the sequence dword at the same index of the same row is loaded with it.  The read's
+        // OWN bytes decide on every tile: raw tiles fold case for the aligner and 'g' must not count, and in the wave
+        // walk a lane serves other lanes' reads, whose codes are not in its row -- so no choice between codes and bytes
+        // is made at all (compare CS_OP_NTRIM below).  A G's term lies within kQTermMax like every other one
+        // (cs_plan_create refuses a cutoff outside [kQCutoffLow, kQCutoffHigh] - base): the key's static_assert holds.
+        // The op never moves s.  (FILT_NEXTSEQ, not FILT_ENDS: see the enum.)
+        const uint32_t *q = reinterpret_cast<const uint32_t *>(ma.qual + (size_t)gr * a.stride_dw * 4u);
+        const uint32_t *bs = ma.seq + (size_t)gr * a.stride_dw;
+        const int cq = (int)op.q_cutoff + (int)op.q_base;
+        auto term = [&](uint32_t w, uint32_t g, int b) -> int {  // what byte b of a dword adds
+          return ((g >> (b * 8)) & 0xffu) == 0x47u ? 1 : cq - (int)((w >> (b * 8)) & 0xffu);
+        };
+        int stop = n;
+        const bool live = on && n > 0;
+        const int p_last = s + n - 1;
+        constexpr int kPosBits = 11;
+        static_assert(CS_MAX_STRIDE < (1 << kPosBits) - 1 && kQTermMax >= 1 &&
+                          (long long)kQTermMax * CS_MAX_STRIDE < (1ll << (31 - kPosBits)),
+                      "NEXTSEQ key: sum << kPosBits | position must fit an int");
+        int sum = 0, bestkey = (1 << kPosBits) - 1;
+        bool alive = live;
+        const int dw_top = p_last >> 2;
+        uint32_t w_top = 0, g_top = 0;
+        if (live) {
+          w_top = q[max(dw_top, 0)];
+          g_top = bs[max(dw_top, 0)];
+        }
+#pragma unroll
+        for (int b = 3; b >= 0; --b) {  // the top dword, 3' -> 5', with range checks
+          const int p = 4 * dw_top + b;
+          const bool in = live && (p <= p_last) && (p >= s);
+          const int nsum = sum + term(w_top, g_top, b);
+          alive = alive && !(in && nsum < 0);
+          const bool on_b = in && alive;
+          sum = on_b ? nsum : sum;
+          const int key = (nsum << kPosBits) | p;
+          bestkey = on_b ? max(bestkey, key) : bestkey;
+        }
+        int dw = dw_top - 1;
+        bool run = alive && (4 * dw_top > s);
+        const int grp = lane >> 4, idx = lane & 15;
+        unsigned long long todo = __ballot(run);
+        while (todo) {  // wave-uniform
+          unsigned long long tt = todo;
+          const int l0 = __builtin_ctzll(tt);
+          tt &= tt - 1ull;
+          const int l1 = tt ? __builtin_ctzll(tt) : -1;
+          tt &= tt - 1ull;
+          const int l2 = tt ? __builtin_ctzll(tt) : -1;
+          tt &= tt - 1ull;
+          const int l3 = tt ? __builtin_ctzll(tt) : -1;
+          const int src = grp == 0 ? l0 : grp == 1 ? l1 : grp == 2 ? l2 : l3;
+          const int from = max(src, 0);
+          const int r_sum = __shfl(sum, from, 64);
+          const int r_pk = __shfl((s << 16) | (dw & 0xffff), from, 64);
+          const uint32_t r_gr = SCAN ? row0 + (uint32_t)from : (uint32_t)__shfl((int)gr, from, 64);
+          const int r_s = r_pk >> 16, r_dw = r_pk & 0xffff;
+          const int dd = r_dw - idx;  // this lane's dword of that read
+          const bool ok = src >= 0 && dd >= (r_s >> 2);
+          uint32_t w = 0, g = 0;
+          if (ok) {
+            w = reinterpret_cast<const uint32_t *>(ma.qual + (size_t)r_gr * a.stride_dw * 4u)[dd];
+            g = (ma.seq + (size_t)r_gr * a.stride_dw)[dd];
+          }
+          const int skip = r_s - 4 * dd;  // low bytes outside the interval: they add nothing, 'G' or not
+          const int c3 = term(w, g, 3);
+          const int c2 = skip > 2 ? 0 : term(w, g, 2);
+          const int c1 = skip > 1 ? 0 : term(w, g, 1);
+          const int c0 = skip > 0 ? 0 : term(w, g, 0);
+          const int p3 = c3, p2 = p3 + c2, p1 = p2 + c1, p0 = p1 + c0;
+          const int tot = ok ? p0 : 0;
+          int incl = tot;
+          incl += __builtin_amdgcn_update_dpp(0, incl, 0x111 /* row_shr:1 */, 0xf, 0xf, false);
+          incl += __builtin_amdgcn_update_dpp(0, incl, 0x112 /* row_shr:2 */, 0xf, 0xf, false);
+          incl += __builtin_amdgcn_update_dpp(0, incl, 0x114 /* row_shr:4 */, 0xf, 0xf, false);
+          incl += __builtin_amdgcn_update_dpp(0, incl, 0x118 /* row_shr:8 */, 0xf, 0xf, false);
+          const int off = r_sum + incl - tot;
+          const int a3 = off + p3, a2 = off + p2, a1 = off + p1, a0 = off + p0;
+          const int o2 = a3 | a2, o1 = o2 | a1, o0 = o1 | a0;
+          const unsigned long long nm = __ballot(ok && o0 < 0);
+          const uint32_t seg = ((grp & 2) ? (uint32_t)(nm >> 32) : (uint32_t)nm) >> ((grp & 1) * 16) & 0xffffu;
+          const int first = seg ? __builtin_ctz(seg) : 16;
+          const bool before = ok && idx < first, at = ok && idx == first;
+          const int pb = 4 * dd;
+          const int k3 = (before || (at && a3 >= 0)) ? ((a3 << kPosBits) | (pb + 3)) : 0;
+          const int k2 = (before || (at && o2 >= 0)) ? ((a2 << kPosBits) | (pb + 2)) : 0;
+          const int k1 = (before || (at && o1 >= 0)) ? ((a1 << kPosBits) | (pb + 1)) : 0;
+          const int k0 = before ? ((a0 << kPosBits) | pb) : 0;
+          int kmax = max(max(k3, k2), max(k1, k0));
+          kmax = max(kmax, __builtin_amdgcn_update_dpp(0, kmax, 0x121 /* row_ror:1 */, 0xf, 0xf, false));
+          kmax = max(kmax, __builtin_amdgcn_update_dpp(0, kmax, 0x122 /* row_ror:2 */, 0xf, 0xf, false));
+          kmax = max(kmax, __builtin_amdgcn_update_dpp(0, kmax, 0x124 /* row_ror:4 */, 0xf, 0xf, false));
+          kmax = max(kmax, __builtin_amdgcn_update_dpp(0, kmax, 0x128 /* row_ror:8 */, 0xf, 0xf, false));
+          const int mine = lane == l0 ? 0 : lane == l1 ? 1 : lane == l2 ? 2 : lane == l3 ? 3 : -1;
+          const int back = 16 * max(mine, 0) + 15;
+          const int g_key = __shfl(kmax, back, 64);
+          const int g_end = __shfl((max(r_sum + incl, 0) << 5) | first, back, 64);
+          if (mine >= 0) {
+            bestkey = max(bestkey, g_key);
+            const bool stopped = (g_end & 31) < 16;
+            sum = g_end >> 5;
+            dw -= 16;
+            run = !stopped && dw >= (s >> 2);
+          }
+          todo = __ballot(run);
+        }
+        if (live && (bestkey >> kPosBits) > 0) stop = (bestkey & ((1 << kPosBits) - 1)) - s;
+        if (on) {
+          if (stop < n) fm |= CS_F_QTRIMMED;
+          qc += (uint32_t)(n - stop);
+          e = s + stop;
+        }
+      }
     } else if (kind == CS_OP_NTRIM) {
-      if constexpr (FILT == FILT_ENDS) {
+      if constexpr (FILT >= FILT_ENDS) {
         // cutadapt's NEndTrimmer: the runs of 'N' (upper case only) at both ends of [s, e) go.  A fast-form coded tile
         // vouches for every byte being A, C, G, T or N, code 7 is 'N' and nothing else (count_n_nibbles); everywhere else
         // -- raw tiles fold case, exact-form tiles and the resolve kernel's mix codes 4..7 -- the read's own bytes decide.
@@ -3548,7 +3670,7 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
     const uint32_t w_many = wave_count(many);
     if (lane == 0 && w_many) atomicAdd(&sacc[ST_TOO_MANY_N], w_many);
     uint32_t xf = many ? (uint32_t)CS_X_TOO_MANY_N : 0u;
-    if constexpr (FILT == FILT_ALL || FILT == FILT_ENDS) {
+    if constexpr (FILT >= FILT_ALL) {
       const bool is_long = fin && plan->max_length_on && e > s && (uint32_t)(e - s) > plan->max_length;
       bool errs = false;
       if (plan->max_ee_on && ma.qual) {  // the read's own quality row, as the quality trimmer reads it

@@ -3,7 +3,7 @@
 Counterpart of the modifier-list assembly in the reference's ``pipeline_single``
 (cutseq/run.py:326-426) and ``pipeline_paired`` (cutseq/run.py:533-731).  Where the
 reference instantiates cutadapt ``Modifier`` objects, this module emits plain
-descriptors (:class:`AdapterOp`, :class:`CutOp`, :class:`QTrimOp`, :class:`NTrimOp`) in the same order;
+descriptors (:class:`AdapterOp`, :class:`CutOp`, :class:`NextSeqTrimOp`, :class:`QTrimOp`, :class:`NTrimOp`) in the same order;
 ``TrimPlan.pack()`` turns them into the ``cs_op`` POD table of ``include/cutseq_hip.h``.
 Header work (SuffixRemover, Renamer) stays on the host and is described by
 ``MateChain.name_suffixes`` / ``TrimPlan.has_umi``.
@@ -56,6 +56,11 @@ class CutadaptConfig:
         # behind the quality trimmer of every mate
         self.min_quality_front = 0
         self.trim_n = False
+        # cutadapt --nextseq-trim CUTOFF: a NextseqQualityTrimmer in front of the quality trimmer of every mate (None =
+        # off); -Q [FRONT,]BACK: mate 2's quality trimmer gets cutoffs of its own (None = it follows -q)
+        self.nextseq_trim = None
+        self.min_quality_r2 = None
+        self.min_quality_front_r2 = None
 
 
 @dataclass
@@ -139,6 +144,18 @@ class QTrimOp:
 
 
 @dataclass
+class NextSeqTrimOp:
+    """cutadapt's ``NextseqQualityTrimmer(cutoff, base)`` (``--nextseq-trim``): the quality trimmer's 3' walk in which an
+    upper-case ``G`` counts as a base of quality ``cutoff - 1``, whatever its quality byte says (CS_OP_NEXTSEQ)."""
+
+    cutoff: int
+    base: int = 33
+
+    def __repr__(self):
+        return f"NextseqQualityTrimmer(cutoff={self.cutoff}, base={self.base})"
+
+
+@dataclass
 class NTrimOp:
     """cutadapt's ``NEndTrimmer()`` (``--trim-n``): the runs of upper-case ``N`` at both ends of the read go."""
 
@@ -198,7 +215,7 @@ class DemuxOp:
                 f"max_error_rate={self.max_error_rate}))")
 
 
-Op = Union[AdapterOp, CutOp, QTrimOp, DemuxOp, NTrimOp]
+Op = Union[AdapterOp, CutOp, QTrimOp, DemuxOp, NTrimOp, NextSeqTrimOp]
 
 
 def info_adapter_names(ops: Sequence["Op"]) -> dict:
@@ -248,6 +265,11 @@ class TrimPlan:
     def has_filters(self) -> bool:
         """Some filter writes ``cs_reads.xflags`` (and discards pairs on the output paths)."""
         return self.max_n is not None or self.max_length is not None or self.max_ee is not None
+
+    @property
+    def has_nextseq(self) -> bool:
+        """Some chain holds a NextSeqTrimOp: its result depends on real quality values, FASTA input is refused."""
+        return any(isinstance(o, NextSeqTrimOp) for c in (self.r1, self.r2) if c is not None for o in c.ops)
 
     @property
     def paired(self) -> bool:
@@ -338,6 +360,10 @@ def pack_ops(ops: Sequence[Op], limit: int = abi.CS_MAX_OPS):
             c.q_base = op.base
         elif isinstance(op, NTrimOp):
             c.kind = abi.CS_OP_NTRIM
+        elif isinstance(op, NextSeqTrimOp):  # (no clamp: cs_plan_create refuses what the kernels' sums cannot hold)
+            c.kind = abi.CS_OP_NEXTSEQ
+            c.q_cutoff = max(-0x8000, min(int(op.cutoff), 0x7FFF))
+            c.q_base = op.base
         else:  # pragma: no cover
             raise TypeError(op)
     return arr
@@ -451,7 +477,9 @@ def compile_single(barcode: BarcodeConfig, settings: CutadaptConfig, untrimmed_r
             ops.append(_poly_t())
         else:
             logging.info("No strand information provided, skip polyA trimming.")
-    # step 8
+    # step 8 (--nextseq-trim: cutadapt runs its NextseqQualityTrimmer in front of the QualityTrimmer)
+    if getattr(settings, "nextseq_trim", None) is not None:
+        ops.append(NextSeqTrimOp(settings.nextseq_trim))
     ops.append(QTrimOp(settings.min_quality, cutoff_front=getattr(settings, "min_quality_front", 0)))
     if getattr(settings, "trim_n", False):  # (cutadapt puts --trim-n behind the adapter work; here: behind step 8)
         ops.append(NTrimOp())
@@ -537,9 +565,15 @@ def compile_paired(barcode: BarcodeConfig, settings: CutadaptConfig, untrimmed_r
         else:
             logging.info("No strand information provided, skip polyA trimming.")
     # step 8
+    if getattr(settings, "nextseq_trim", None) is not None:
+        o1.append(NextSeqTrimOp(settings.nextseq_trim))
+        o2.append(NextSeqTrimOp(settings.nextseq_trim))
     front = getattr(settings, "min_quality_front", 0)
     o1.append(QTrimOp(settings.min_quality, cutoff_front=front))
-    o2.append(QTrimOp(settings.min_quality, cutoff_front=front))
+    if getattr(settings, "min_quality_r2", None) is not None:  # -Q: mate 2's own cutoffs, both of them
+        o2.append(QTrimOp(settings.min_quality_r2, cutoff_front=getattr(settings, "min_quality_front_r2", None) or 0))
+    else:
+        o2.append(QTrimOp(settings.min_quality, cutoff_front=front))
     if getattr(settings, "trim_n", False):
         o1.append(NTrimOp())
         o2.append(NTrimOp())

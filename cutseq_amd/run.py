@@ -55,7 +55,15 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Minimum quality score for trimming read tails. (Default: 20) Extension (cutadapt's form of "
                         "the option): two values separated by a comma trim the 5' end with the first cutoff and the "
                         "3' end with the second.")
-    p.set_defaults(min_quality_front=0)
+    p.add_argument("-Q", dest="min_quality_r2", action=_QualityCutoffs, default=None, metavar="[5'CUTOFF,]3'CUTOFF",
+                   help="Extension (cutadapt's option): quality-trimming cutoff(s) for the second read of a pair, in the "
+                        "form -q takes. (Default: the second read follows -q)")
+    p.set_defaults(min_quality_front=0, min_quality_front_r2=None)
+    p.add_argument("--nextseq-trim", type=int, default=None, metavar="3'CUTOFF",
+                   help="Extension (cutadapt's option): NextSeq/NovaSeq-specific quality trimming of the 3' end, in front "
+                        "of -q's: the same walk with this cutoff, in which a G counts as a base of quality CUTOFF - 1 "
+                        "whatever its quality value says (the dark cycles of two-colour instruments read as high-quality "
+                        "G). Needs an input with qualities.")
     p.add_argument("-m", "--min-length", type=int, default=20,
                    help="Minimum length of reads to keep after trimming. (Default: 20)")
     p.add_argument("--with-rname-suffix", action="store_true",
@@ -119,7 +127,8 @@ def build_parser() -> argparse.ArgumentParser:
 
 class _QualityCutoffs(argparse.Action):
     """``-q BACK`` or ``-q FRONT,BACK`` (cutadapt's ``-q [5'CUTOFF,]3'CUTOFF``): ``min_quality`` stays the 3' int, the 5'
-    value goes to ``min_quality_front``.  Anything else is an argparse error, like a non-integer was before."""
+    value goes to ``min_quality_front``.  Anything else is an argparse error, like a non-integer was before.  ``-Q``, the
+    same for the second read of a pair, fills ``min_quality_r2`` / ``min_quality_front_r2``."""
 
     def __call__(self, parser, namespace, values, option_string=None):
         parts = values.split(",")
@@ -129,8 +138,10 @@ class _QualityCutoffs(argparse.Action):
             raise argparse.ArgumentError(self, f"invalid int value: {values!r}")
         if len(cutoffs) > 2:
             raise argparse.ArgumentError(self, f"expected one value or two separated by a comma: {values!r}")
-        namespace.min_quality = cutoffs[-1]
-        namespace.min_quality_front = cutoffs[0] if len(cutoffs) == 2 else 0
+        # (-q: min_quality / min_quality_front; -Q: min_quality_r2 / min_quality_front_r2)
+        front = self.dest.replace("min_quality", "min_quality_front")
+        setattr(namespace, self.dest, cutoffs[-1])
+        setattr(namespace, front, cutoffs[0] if len(cutoffs) == 2 else 0)
 
 
 # Output naming (user-visible contract of the reference CLI, run.py:1058-1107): for every output class the
@@ -192,6 +203,12 @@ def resolve_args(args):
         _fail(f"-M/--max-length: the length must not be negative (got {max_length}).")
     if max_ee is not None and not max_ee >= 0:  # (NaN fails the comparison too)
         _fail(f"--max-ee: the number of expected errors must not be negative (got {max_ee}).")
+    nextseq = getattr(args, "nextseq_trim", None)
+    if nextseq is not None and not abi.CS_Q_SUM_LOW <= nextseq + 33 <= abi.CS_Q_SUM_HIGH:
+        # (unlike -q's, this cutoff is not clamped: a G's term is +1 whatever it is -- include/cutseq_hip.h, CS_OP_NEXTSEQ)
+        _fail(f"--nextseq-trim: the cutoff must lie in [{abi.CS_Q_SUM_LOW - 33}, {abi.CS_Q_SUM_HIGH - 33}] (got {nextseq}).")
+    if getattr(args, "min_quality_r2", None) is not None and len(inputs) == 1:
+        _fail("-Q sets the quality cutoff of the second read: it needs two input files.")
     if getattr(args, "info_file", None):
         if args.demux_barcodes:
             _fail("--info-file cannot be combined with --demux-barcodes: the table form of the demultiplexing op has "
@@ -234,6 +251,9 @@ def settings_from_args(args) -> CutadaptConfig:
     st.min_quality = args.min_quality
     st.min_quality_front = getattr(args, "min_quality_front", 0)
     st.trim_n = getattr(args, "trim_n", False)
+    st.nextseq_trim = getattr(args, "nextseq_trim", None)
+    st.min_quality_r2 = getattr(args, "min_quality_r2", None)
+    st.min_quality_front_r2 = getattr(args, "min_quality_front_r2", None)
     st.dry_run = args.dry_run
     st.auto_rc = args.auto_rc
     st.json_file = args.json_file
@@ -475,11 +495,13 @@ def run_cutseq(args, argv=None):
     if settings.dry_run:
         dry_run(tp, barcode)
         return None
-    if tp.max_ee is not None:  # (standard input: the text path checks once it has seen the first byte)
-        from . import codec
-        for name in args.input_file:
-            if name != "-" and codec.sniff_input(name)[1] in (b">", b"#"):
-                _fail(f"--max-ee needs qualities: {name} is a FASTA file.")
+    # (standard input: the text path checks once it has seen the first byte)
+    for option, wanted in (("--max-ee", tp.max_ee is not None), ("--nextseq-trim", tp.has_nextseq)):
+        if wanted:
+            from . import codec
+            for name in args.input_file:
+                if name != "-" and codec.sniff_input(name)[1] in (b">", b"#"):
+                    _fail(f"{option} needs qualities: {name} is a FASTA file.")
     totals = None
     if getattr(args, "rank_spec", None):  # a child of --ranks: its share, its part files, its totals; the parent reports
         from . import ranks

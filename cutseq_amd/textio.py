@@ -790,6 +790,8 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
             raise fastq.FastqFormatError("the two input files are in different formats (one FASTA, one FASTQ)")
         if r1.fasta and tp.max_ee is not None:
             raise fastq.FastqFormatError("--max-ee needs qualities: the input is FASTA")
+        if r1.fasta and tp.has_nextseq:  # (the qualities the FASTA re-shaper invents would not stop the Gs from going)
+            raise fastq.FastqFormatError(f"--nextseq-trim needs qualities: {args.input_file[0]} is a FASTA file.")
         fasta_routes = output_formats(name_groups, has_qualities=not r1.fasta)
 
         def writer(name, precompressed):

@@ -50,7 +50,7 @@ typedef enum cs_status {
 
 /* ---- op table: what cutseq/run.py:305-433 (single) and :493-731 (paired) compile -- */
 
-enum { CS_OP_ADAPTER = 1, CS_OP_CUT = 2, CS_OP_QTRIM = 3, CS_OP_DEMUX = 4, CS_OP_NTRIM = 5 };
+enum { CS_OP_ADAPTER = 1, CS_OP_CUT = 2, CS_OP_QTRIM = 3, CS_OP_DEMUX = 4, CS_OP_NTRIM = 5, CS_OP_NEXTSEQ = 6 };
 
 /* CS_OP_QTRIM -- cutadapt's QualityTrimmer(cutoff_front, cutoff_back, base), quality_trim_index on the interval [s, e)
  * the op sees (n = e - s, qualities q[0..n)):
@@ -69,7 +69,21 @@ enum { CS_OP_ADAPTER = 1, CS_OP_CUT = 2, CS_OP_QTRIM = 3, CS_OP_DEMUX = 4, CS_OP
  * (0x4E; upper case only: cutadapt's patterns are ^N+ and N+$ without IGNORECASE -- TooManyN counts 'n' too) of
  * seq[s:e) go: a == e - s leaves [s, s), anything else [s + a, e - b).  No counter and no flag of its own: out_bp,
  * TooShort and the filters see the result.  A plan with a non-zero q_cutoff_front or a CS_OP_NTRIM op runs kernels of
- * its own; every other plan the kernels it ran before these came. */
+ * its own; every other plan the kernels it ran before these came.
+ *
+ * CS_OP_NEXTSEQ -- cutadapt's NextseqQualityTrimmer(cutoff, base) (--nextseq-trim), nextseq_trim_index on the interval
+ * [s, e) the op sees (n = e - s, bases b[0..n), qualities q[0..n)); fields q_cutoff and q_base:
+ *     sum = best = 0, stop = n;  for i = n - 1 down to 0:
+ *         sum += (b[i] == 'G') ? 1 : q_cutoff - (q[i] - q_base);  break if sum < 0;  if sum > best: best = sum, stop = i
+ * [s, s + stop) is left: CS_OP_QTRIM's back walk in which a 'G' (0x47; upper case only, 'g' is an ordinary base) is a
+ * base of quality q_cutoff - 1 whatever its quality byte says -- the dark cycles of two-colour instruments read as G
+ * of high quality.  cs_stats.qualtrim_bp gains n - stop, CS_F_QTRIMMED says that it is more than 0 (cutadapt counts both
+ * trimmers under quality_trimmed).  The cutoff is NOT clamped: a G's term is +1 whatever the cutoff, so the walk over
+ * 100 x 'G', one 'A' of quality 'I', 300 x 'G' breaks at the 'A' under cutoff -5000 (stop 101) and goes past it under
+ * -34 (stop 0).  cs_plan_create refuses an op with q_cutoff + q_base outside [-1, 256] (CS_ERR_ARG); inside, every term
+ * is within the bound CS_OP_QTRIM's sums are built for.  A plan with the op runs the read-end instantiations of the
+ * long-read and info kernels and tile kernels that hold the read-end modifiers' code and this op's; every other plan
+ * the kernels it ran before (cutadapt's order: this op in front of the chain's CS_OP_QTRIM). */
 
 /* CS_OP_DEMUX -- extension, not a reference capability (BASELINE.json config 5): ONE pass
  * decides which of up to 255 equally long inline barcodes starts the read, where the reference would

@@ -11,6 +11,12 @@ scan and resolve kernel ms per call, reads flagged per call and mate.
 quality dword of the interval the trimmer sees (the walk is one lane per read: tools/README.md).
 
   python tools/filters_ab.py --ends [--front 20] [--sample 1000000]
+
+--nextseq: the cost of --nextseq-trim CUTOFF: the plan without it against the plan with a NextSeqTrimOp in front of the
+quality trimmer of both mates.  --only LEG[,LEG]: these legs alone (an A/B of two libraries runs one leg under each,
+CUTSEQ_HIP_LIB choosing the library).
+
+  python tools/filters_ab.py --nextseq [--cutoff 20]
 """
 from __future__ import annotations
 
@@ -43,6 +49,9 @@ def plan_for(filters):
                 o.cutoff_front = filters.get("front", 0)
         if filters.get("trim_n"):
             chain.ops = chain.ops + [planmod.NTrimOp()]
+        if filters.get("nextseq") is not None:  # immediately in front of the chain's quality trimmer
+            at = next(i for i, o in enumerate(chain.ops) if isinstance(o, planmod.QTrimOp))
+            chain.ops = chain.ops[:at] + [planmod.NextSeqTrimOp(filters["nextseq"])] + chain.ops[at:]
     return tp
 
 
@@ -125,6 +134,9 @@ def main():
     ap.add_argument("--ends", action="store_true", help="the legs of -q FRONT,20 and --trim-n instead of the filters'")
     ap.add_argument("--front", type=int, default=20, help="--ends: the 5' cutoff")
     ap.add_argument("--sample", type=int, default=1_000_000, help="--ends: pairs the front-walk share is counted on")
+    ap.add_argument("--nextseq", action="store_true", help="the legs of --nextseq-trim instead of the filters'")
+    ap.add_argument("--cutoff", type=int, default=20, help="--nextseq: the cutoff")
+    ap.add_argument("--only", type=str, default=None, help="run these legs alone (comma-separated)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     n = args.pairs
@@ -143,6 +155,10 @@ def main():
         share = front_walk_share(d, min(n, args.sample), stride, args.front)
         print(json.dumps({"front_walk_beyond_first_dword": round(share, 5), "front": args.front,
                           "sample_pairs": min(n, args.sample)}), flush=True)
+    if args.nextseq:
+        legs = (("off", {}), ("nextseq", {"nextseq": args.cutoff}))
+    if args.only:
+        legs = tuple(leg_ for leg_ in legs if leg_[0] in args.only.split(","))
     res = {key: [] for key, _ in legs}
     for _ in range(args.rounds):
         for key, filters in legs:
@@ -150,7 +166,7 @@ def main():
             res[key].append(r)
             print(json.dumps({"leg": key, **r}), flush=True)
     med = {k: {f: statistics.median(x[f] for x in v) for f in ("mpairs_s", "scan_ms", "resolve_ms")} for k, v in res.items()}
-    slow = {k: round(100.0 * (1.0 - med[k]["mpairs_s"] / med["off"]["mpairs_s"]), 2) for k in med if k != "off"}
+    slow = {k: round(100.0 * (1.0 - med[k]["mpairs_s"] / med["off"]["mpairs_s"]), 2) for k in med if k != "off" and "off" in med}
     print(json.dumps({"summary": med, "slowdown_pct": slow, "pairs": n, "steps": args.steps, "rounds": args.rounds}),
           flush=True)
 

@@ -170,10 +170,15 @@ def build_chain(barcode, settings, paired: bool, untrimmed_requested: bool = Fal
             each(tail(), head())
         elif barcode.strand == "-":
             each(head(), tail())
-    # step 8
+    # step 8 (--nextseq-trim: cutadapt's order of its two trimmers, NextseqQualityTrimmer first)
+    ns = _get(settings, "nextseq_trim", None)
+    if ns is not None:
+        each(M.NextseqQualityTrimmer(ns, 33), M.NextseqQualityTrimmer(ns, 33))
     q = _get(settings, "min_quality", 20)
     qf = _get(settings, "min_quality_front", 0)  # (-q FRONT,BACK; 0: the reference's trimmer)
-    each(M.QualityTrimmer(cutoff_front=qf, cutoff_back=q), M.QualityTrimmer(cutoff_front=qf, cutoff_back=q))
+    q2 = _get(settings, "min_quality_r2", None)  # (-Q: read 2's own cutoffs, both of them)
+    second = (qf, q) if q2 is None else (_get(settings, "min_quality_front_r2", None) or 0, q2)
+    each(M.QualityTrimmer(cutoff_front=qf, cutoff_back=q), M.QualityTrimmer(cutoff_front=second[0], cutoff_back=second[1]))
     if _get(settings, "trim_n", False):  # --trim-n: behind the quality trimmer, as cutseq_amd.plan compiles it
         each(M.NEndTrimmer(), M.NEndTrimmer())
     # step 9
@@ -305,9 +310,11 @@ def collect_cases(n_synth: int = 2000):
     from test_oracle import CHAIN_CASES
     cases = []
     rec1, rec2 = fixture_records()
-    # (the last two: QualityTrimmer(cutoff_front=F, ...) and NEndTrimmer(), -q F,B and --trim-n -- recalled rules)
+    # (the last four: QualityTrimmer(cutoff_front=F, ...) and NEndTrimmer(), -q F,B and --trim-n; NextseqQualityTrimmer and
+    # read 2's own cutoffs, --nextseq-trim and -Q -- recalled rules)
     for flags in ({}, {"trim_polyA": True}, {"min_quality_front": 15, "min_quality": 10},
-                  {"min_quality_front": 20, "trim_n": True}):
+                  {"min_quality_front": 20, "trim_n": True}, {"nextseq_trim": 20},
+                  {"nextseq_trim": 10, "min_quality": 25, "min_quality_r2": 5, "min_quality_front_r2": 3, "trim_n": True}):
         cases.append(chain_case(f"fixture10k/TAKARAV3/{sorted(flags)}", BUILDIN_ADAPTERS["TAKARAV3"], flags, True,
                                 {"fixture": "fixture10k"}, rec1, rec2))
     for idx, (name, flags, paired) in enumerate(CHAIN_CASES):
