@@ -159,7 +159,7 @@ class cs_text_params(C.Structure):
         ("fasta_out", C.c_uint8),
         ("fasta_routes", C.c_uint8),
         ("info", C.c_uint8),
-        ("_reserved", C.c_uint8 * 1),
+        ("too_long_route", C.c_uint8),  # the one byte that was reserved: 0 keeps what it meant then
     ]
 
 

@@ -1415,7 +1415,7 @@ int cs_copy_to_host(int device, void *dst, const void *src, size_t bytes) {
 
 namespace {
 
-struct RouteBlock {  // demultiplexing plans: per route what TextMeta holds for the three ordinary routes
+struct RouteBlock {  // demultiplexing and too-long plans: per route what TextMeta holds for the three ordinary routes
   unsigned long long bytes[cstext::kMaxRoutes][2];
   unsigned long long gz_bytes[cstext::kMaxRoutes][2];
   uint32_t count[cstext::kMaxRoutes];
@@ -1479,7 +1479,8 @@ struct cs_text {
   bool mixed_formats = false; // the streams differ in format (tp.fasta_routes): format_copy decides per record
   bool literal_only = false;  // ... from literal-only blocks (CUTSEQ_GPU_LZ=0: no run / record-name matches)
   uint32_t max_chunks = 0;
-  uint32_t n_routes = 3;      // 3 + cs_text_params.n_bins
+  uint32_t n_routes = 3;      // 3 + cs_text_params.n_bins; 4 with cs_text_params.too_long_route
+  bool route_block = false;   // more than three routes: their sizes and counts live in the slots' RouteBlock
   uint8_t info = 0;           // CS_INFO_* (cs_text_params.info)
   uint64_t info_cap = 0;      // bytes of a batch's info table at most
   uint32_t info_chunks = 0;   // ... and deflate chunks
@@ -1600,11 +1601,11 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
   t->tp.reverse_complement = params->reverse_complement ? 1 : 0;
   {
     // which (route class, mate) streams exist at all: a bit for one that does not is the caller's mistake
-    const uint8_t exist = (uint8_t)((eng->paired ? 0xffu : 0x55u) & (params->n_bins ? 0xffu : 0x3fu));
+    const uint8_t exist = (uint8_t)((eng->paired ? 0xffu : 0x55u) & (params->n_bins || params->too_long_route ? 0xffu : 0x3fu));
     if (params->fasta_routes & ~exist) {
       delete t;
       return fail(CS_ERR_ARG, "fasta_routes = 0x%02x names a stream this plan does not have (mate 2 of a single-end plan, "
-                  "or the barcode class without bins)", params->fasta_routes);
+                  "or class 3 without bins or a too-long route)", params->fasta_routes);
     }
     const uint8_t mask = params->fasta_out ? exist : params->fasta_routes;
     // one format over all streams: every bit set or none, and format_copy keeps its uniform instance
@@ -1641,6 +1642,17 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
     t->tp.n_bins = (uint16_t)params->n_bins;
     t->tp.demux_mate = (uint8_t)eng->demux_mate;
     t->n_routes = 3u + params->n_bins;
+    t->route_block = true;
+  }
+  if (params->too_long_route) {  // class 3 is the barcodes' in a demultiplexing plan, and TooLong must be there to catch
+    if (params->n_bins || !(eng->filters & CS_X_TOO_LONG)) {
+      delete t;
+      return fail(CS_ERR_ARG, params->n_bins ? "too_long_route: route class 3 belongs to the barcodes of a plan with n_bins"
+                                             : "too_long_route needs a plan with cs_plan_set_max_length");
+    }
+    t->tp.too_long_route = 1;
+    t->n_routes = 4u;
+    t->route_block = true;
   }
   t->max_chunks = (uint32_t)((out_cap + csdefl::kChunk - 1) / csdefl::kChunk) + t->n_routes;
   if (params->info) {
@@ -1738,10 +1750,8 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
       c.take(s.d_blk, (size_t)2 * (t->seg_blocks + 1) + (size_t)2 * t->n_routes * (t->fmt_blocks + 1));
       c.take(s.d_totals, 2 + 2 * (size_t)t->n_routes);
       c.take(s.d_meta, 1);
-      if (t->tp.n_bins) {
-        c.take(s.d_bc, max_records);
-        c.take(s.d_routes, 1);
-      }
+      if (t->tp.n_bins) c.take(s.d_bc, max_records);
+      if (t->route_block) c.take(s.d_routes, 1);
       if (t->tp.filters)
         for (int m = 0; m < mates; ++m) c.take(s.d_xf[m], max_records);
       if (t->info) {
@@ -1760,7 +1770,7 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
     carve(s.d_arena);
     TXT_TRY(hipMemsetAsync(s.d_arena, 0, zero_bytes, t->h2d));
     TXT_TRY(hipMemsetAsync(s.d_arena + zero_bytes, 0xff, ones_bytes, t->h2d));
-    if (t->tp.n_bins) TXT_TRY(hipHostMalloc(&s.h_routes, sizeof(RouteBlock), hipHostMallocPortable));
+    if (t->route_block) TXT_TRY(hipHostMalloc(&s.h_routes, sizeof(RouteBlock), hipHostMallocPortable));
     if (t->info) {
       TXT_TRY(hipHostMalloc(&s.h_imeta, sizeof(csinfo::InfoMeta), hipHostMallocPortable));
       memset(s.h_imeta, 0, sizeof(csinfo::InfoMeta));
@@ -1921,10 +1931,17 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
       hipLaunchKernelGGL(cstext::format_sizes_bins, dim3(fb), dim3(256), 0, rs, fa, t->tp);
       hipLaunchKernelGGL(cstext::text_scan_blocks, dim3(cols < 64u ? cols : 64u), dim3(1024), 0, rs, blk_fmt, fb, cols, fa.totals);
       hipLaunchKernelGGL(cstext::format_offsets_bins, dim3(fb), dim3(256), 0, rs, fa, t->tp);
+    } else if (t->tp.too_long_route) {  // four routes: the plain block scans over eight columns
+      fa.route_bytes = &s.d_routes->bytes[0][0];
+      fa.route_count = s.d_routes->count;
+      HIP_TRY(hipMemsetAsync(s.d_routes, 0, sizeof(RouteBlock), rs));
+      hipLaunchKernelGGL(cstext::format_sizes<4>, dim3(fb), dim3(256), 0, rs, fa, t->tp);
+      hipLaunchKernelGGL(cstext::text_scan_blocks, dim3(1), dim3(1024), 0, rs, blk_fmt, fb, 8u, fa.totals);
+      hipLaunchKernelGGL(cstext::format_offsets<4>, dim3(fb), dim3(256), 0, rs, fa, t->tp);
     } else {
-      hipLaunchKernelGGL(cstext::format_sizes, dim3(fb), dim3(256), 0, rs, fa, t->tp);
+      hipLaunchKernelGGL(cstext::format_sizes<3>, dim3(fb), dim3(256), 0, rs, fa, t->tp);
       hipLaunchKernelGGL(cstext::text_scan_blocks, dim3(1), dim3(1024), 0, rs, blk_fmt, fb, 6u, fa.totals);
-      hipLaunchKernelGGL(cstext::format_offsets, dim3(fb), dim3(256), 0, rs, fa, t->tp);
+      hipLaunchKernelGGL(cstext::format_offsets<3>, dim3(fb), dim3(256), 0, rs, fa, t->tp);
     }
     const unsigned long long items = (unsigned long long)n_records * mates;
     const unsigned long long want = (items * 32ull + 255ull) / 256ull;
@@ -1950,8 +1967,8 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
       for (int m = 0; m < mates; ++m) {
         uint32_t fasta_classes = 0;
         for (uint32_t c = 0; c < 4u; ++c) fasta_classes |= ((t->tp.fasta_routes >> (2u * c + m)) & 1u) << c;
-        launch_deflate(rs, s.gz[m], s.d_out[m], t->tp.n_bins ? &s.d_routes->bytes[0][m] : &s.d_meta->route_bytes[0][m],
-                       t->tp.n_bins ? &s.d_routes->gz_bytes[0][m] : &s.d_meta->gz_route_bytes[0][m], t->n_routes,
+        launch_deflate(rs, s.gz[m], s.d_out[m], t->route_block ? &s.d_routes->bytes[0][m] : &s.d_meta->route_bytes[0][m],
+                       t->route_block ? &s.d_routes->gz_bytes[0][m] : &s.d_meta->gz_route_bytes[0][m], t->n_routes,
                        &s.d_meta->gz_bytes[m], fasta_classes, t->literal_only, &s.d_meta->err);
       }
       HIP_TRY(hipGetLastError());
@@ -1963,7 +1980,7 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
   }
   HIP_TRY(hipMemcpyAsync(s.h_meta, s.d_meta, sizeof(cstext::TextMeta), hipMemcpyDeviceToHost, rs));
   if (t->info) HIP_TRY(hipMemcpyAsync(s.h_imeta, s.d_imeta, sizeof(csinfo::InfoMeta), hipMemcpyDeviceToHost, rs));
-  if (t->tp.n_bins) {
+  if (t->route_block) {
     if (!n_records) HIP_TRY(hipMemsetAsync(s.d_routes, 0, sizeof(RouteBlock), rs));
     HIP_TRY(hipMemcpyAsync(s.h_routes, s.d_routes, sizeof(RouteBlock), hipMemcpyDeviceToHost, rs));
   }
@@ -2002,13 +2019,13 @@ int cs_text_wait(cs_text *t, uint32_t slot, cs_text_result *res) {
       }
     res->out_bytes[0] = m.gz_bytes[0];
     res->out_bytes[1] = m.gz_bytes[1];
-    if (t->tp.n_bins)  // (the gzip sizes of a demultiplexing plan live in the route block: [0] = every barcode together)
-      for (int k = 0; k < 2; ++k) {
+    if (t->route_block)  // (the gzip sizes of such a plan live in the route block: [0] = every barcode together; the
+      for (int k = 0; k < 2; ++k) {  // too-long route is in none of the three)
         const RouteBlock &rb = *s.h_routes;
         res->route_bytes[1][k] = rb.gz_bytes[1][k];
         res->route_bytes[2][k] = rb.gz_bytes[2][k];
         res->route_bytes[0][k] = rb.gz_bytes[0][k];
-        for (uint32_t q = 3; q < t->n_routes; ++q) res->route_bytes[0][k] += rb.gz_bytes[q][k];
+        for (uint32_t q = 3; q < t->n_routes && t->tp.n_bins; ++q) res->route_bytes[0][k] += rb.gz_bytes[q][k];
       }
   }
   res->written_bp[0] = m.written_bp[0];
@@ -2033,13 +2050,13 @@ int cs_text_routes(cs_text *t, uint32_t slot, uint64_t *bytes, uint64_t *text_by
   const cstext::TextMeta &m = *s.h_meta;
   for (uint32_t q = 0; q < t->n_routes; ++q)
     for (int k = 0; k < 2; ++k) {
-      const unsigned long long raw = t->tp.n_bins ? s.h_routes->bytes[q][k] : m.route_bytes[q][k];
-      const unsigned long long gz = t->tp.n_bins ? s.h_routes->gz_bytes[q][k] : m.gz_route_bytes[q][k];
+      const unsigned long long raw = t->route_block ? s.h_routes->bytes[q][k] : m.route_bytes[q][k];
+      const unsigned long long gz = t->route_block ? s.h_routes->gz_bytes[q][k] : m.gz_route_bytes[q][k];
       if (text_bytes) text_bytes[q * 2 + k] = raw;
       if (bytes) bytes[q * 2 + k] = t->compress ? gz : raw;
     }
   if (count)
-    for (uint32_t q = 0; q < t->n_routes; ++q) count[q] = t->tp.n_bins ? s.h_routes->count[q] : m.route_count[q];
+    for (uint32_t q = 0; q < t->n_routes; ++q) count[q] = t->route_block ? s.h_routes->count[q] : m.route_count[q];
   return CS_OK;
 }
 

@@ -310,7 +310,9 @@ typedef struct csh_format_params {
   int32_t has_umi;          /* Renamer template carries the captured bases */
   int32_t untrimmed_filter; /* IsUntrimmedAny filter installed */
   int32_t reverse_complement; /* single-end --auto-rc on a '-' library */
-  uint8_t flag_too_short, flag_untrimmed, pad[2];
+  uint8_t flag_too_short, flag_untrimmed;
+  uint8_t too_long_route; /* --too-long-output: a pair TooLong catches is written to stream 3, not discarded (no bins then) */
+  uint8_t pad[1];
   const char *suffix1[2]; /* SuffixRemover literals of mate 1, applied in order */
   const char *suffix2[2];
 } csh_format_params;
@@ -386,11 +388,12 @@ typedef struct csh_chunk {
   int32_t n_bins;
 } csh_chunk;
 
-/* binned, bin_off ([2][n_bins + 1]) and bin_counts ([n_bins]) are read only when n_bins > 0 */
+/* binned, bin_off ([2][n_bins + 1]) and bin_counts ([n_bins]) are read only when n_bins > 0; out[3], out_len[3] and
+ * counts[3] belong to the too-long stream (csh_format_params.too_long_route) and are left alone without it */
 typedef struct csh_format_out {
-  uint8_t *out[3][2];
-  int64_t out_len[3][2];
-  int64_t counts[3];
+  uint8_t *out[4][2];
+  int64_t out_len[4][2];
+  int64_t counts[4];
   uint8_t *binned[2];
   int64_t *bin_off;
   int64_t *bin_counts;
@@ -405,10 +408,12 @@ void csh_format_struct_sizes(int64_t sizes[3]) {
 
 /* The discarding filters (cs_reads.xflags: CS_X_TOO_MANY_N 1, CS_X_TOO_LONG 2, CS_X_TOO_MANY_EE 4), pair filter "any":
  * behind TooShort, in front of IsUntrimmedAny.  Whichever of them catches the pair, it goes nowhere (which one it
- * counts under is report.account_chunk's business). */
+ * counts under is report.account_chunk's business) -- except that with too_long_route a pair TooLong catches, the
+ * first of the three in cutadapt's order, goes to stream 3. */
 #define CSH_ROUTE_DISCARD (-1)
 static int route_of(const csh_format_params *fp, unsigned flags, unsigned xflags) {
   if (flags & fp->flag_too_short) return 1;
+  if (fp->too_long_route && (xflags & 2u)) return 3;
   if (xflags & 7u) return CSH_ROUTE_DISCARD;
   return (fp->untrimmed_filter && (flags & fp->flag_untrimmed)) ? 2 : 0;
 }
@@ -496,7 +501,8 @@ static int64_t record_bytes(const csh_rec *r, int m, int has_umi, int32_t s, int
 /* Format one chunk: header rewriting, pair check, routing, FASTQ text.  out->out[route][mate] are the caller's buffers
  * for the routes 0 trimmed, 1 short, 2 untrimmed; out_len[route][mate] receives the bytes written and counts[route]
  * the records (pairs).  The pairs a discarding filter takes (xflags) are written nowhere and counted nowhere: n - the
- * sum of all counts.
+ * sum of all counts.  With fp->too_long_route (and no bins) the pairs TooLong catches are stream 3: out->out[3][mate],
+ * out_len[3][mate], counts[3], like the other three.
  *
  * With ck->n_bins > 0 (demultiplexed output, BASELINE.json config 5) route 0 stays empty: its records are split by
  * ck->bin[i].  The bins of one mate lie back to back in out->binned[mate], bin b at
@@ -514,6 +520,8 @@ int64_t csh_format_chunk(const csh_format_params *fp, const csh_chunk *ck, csh_f
   const int n_bins = ck->n_bins, mates = fp->paired ? 2 : 1, has_umi = fp->has_umi;
   const int rc = !fp->paired && fp->reverse_complement;
   if (n_bins < 0 || n_bins > CSH_MAX_BINS) return -(n + 1);
+  const int too_long = fp->too_long_route != 0, plain = too_long ? 4 : 3; /* streams with buffers of their own */
+  if (too_long && (n_bins || !out->out[3][0] || !out->out[3][mates - 1])) return -(n + 1); /* (stream 3 is a bin's there) */
   if (n_bins && !(ck->bin && out->bin_off && out->bin_counts && out->binned[0] && out->binned[mates - 1])) return -(n + 1);
   const int64_t per_mate = n_bins + 1;
   csh_rec r;
@@ -534,10 +542,10 @@ int64_t csh_format_chunk(const csh_format_params *fp, const csh_chunk *ck, csh_f
   }
   uint8_t *w[2][3 + CSH_MAX_BINS]; /* write position per mate and stream */
   for (int m = 0; m < 2; m++)
-    for (int s = 0; s < 3; s++) w[m][s] = out->out[s][m];
+    for (int s = 0; s < plain; s++) w[m][s] = out->out[s][m];
   for (int m = 0; m < mates; m++)
     for (int b = 0; b < n_bins; b++) w[m][3 + b] = out->binned[m] + out->bin_off[m * per_mate + b];
-  for (int s = 0; s < 3; s++) out->counts[s] = 0;
+  for (int s = 0; s < plain; s++) out->counts[s] = 0;
   for (int64_t i = 0; i < n; i++) {
     if (prep_record(fp, ck, i, &r)) return -(i + 1);
     if (r.stream == CSH_ROUTE_DISCARD) continue;
@@ -546,9 +554,9 @@ int64_t csh_format_chunk(const csh_format_params *fp, const csh_chunk *ck, csh_f
       w[m][r.stream] = emit(w[m][r.stream], &r, m, has_umi, mt->seq + (size_t)i * ck->stride,
                             mt->qual + (size_t)i * ck->stride, mt->res[i].start, mt->res[i].stop, rc);
     }
-    if (r.stream < 3) out->counts[r.stream]++;
+    if (r.stream < plain) out->counts[r.stream]++;
   }
-  for (int s = 0; s < 3; s++)
+  for (int s = 0; s < plain; s++)
     for (int m = 0; m < 2; m++) out->out_len[s][m] = w[m][s] - out->out[s][m];
   /* every bin ends where pass 1 said the next one starts */
   for (int m = 0; m < mates; m++)

@@ -17,7 +17,8 @@
 //   format_sizes / format_scan / format_offsets   route of every record (TooShort -> TooLong -> TooManyN ->
 //                         TooManyExpectedErrors -> IsUntrimmedAny -> sink, pair filter "any"; the three in the middle
 //                         discard the pair: no route, no bytes) and the byte offset of its output record inside the route's stream: block
-//                         sums, exclusive scan, block-local scans -- output order = input order
+//                         sums, exclusive scan, block-local scans -- output order = input order.  <3>: the three routes;
+//                         <4>: cs_text_params.too_long_route, the pairs TooLong catches are a fourth route, not discarded
 //   format_copy           32 lanes per output record: '@' id ['_' UMI] '\n' seq[start:stop] "\n+\n" qual[start:stop] '\n'
 //
 // Everything a kernel rejects (malformed record, read longer than the row stride, mate ids that differ) lands in
@@ -72,7 +73,7 @@ struct TextParams {  // constant per engine
                                      // every barcode's route).  cs_text_create folds cs_text_params.fasta_out into it
   uint8_t filters;                   // the plan has some of TooLong / TooManyN / TooManyExpectedErrors (CS_X_* bits):
                                      // FormatArgs.xf holds the per-read flags
-  uint8_t _pad;
+  uint8_t too_long_route;            // cs_text_params.too_long_route: a pair TooLong catches forms route 3 (no bins then)
 };
 
 __device__ __forceinline__ void report(TextMeta *meta, uint32_t record, uint32_t code) {
@@ -364,12 +365,13 @@ struct FormatArgs {
   const cslong::LongRes *lres[2];
   const uint8_t *xf[2];    // TextParams.filters: cs_reads.xflags of the tile kernels (long reads: LongRes.xflags)
   uint32_t n, stride;
-  uint32_t *blk;           // [n_blocks][6] block sums, then their exclusive scan (column = route * 2 + mate)
-  unsigned long long *totals;  // [6] column sums
+  uint32_t *blk;           // [n_blocks][6] block sums (8 with a too-long route), then their exclusive scan (column = route * 2 + mate)
+  unsigned long long *totals;  // [6] column sums (8 with a too-long route)
   uint32_t *dst[2];        // per mate: byte offset of every record's output inside the mate's buffer | route class << 30
   uint8_t *out[2];
   TextMeta *meta;
-  // demultiplexing plans (TextParams.n_bins > 0): routes 0 .. 2 + n_bins
+  // demultiplexing plans (TextParams.n_bins > 0): routes 0 .. 2 + n_bins; too-long plans (TextParams.too_long_route):
+  // routes 0 .. 3, no bc
   const uint8_t *bc;                  // per record: barcode index (CS_DEMUX_NONE: none)
   unsigned long long *route_bytes;    // out [route][mate]: bytes of every route stream
   uint32_t *route_count;              // out [route]: records (pairs) per route
@@ -433,6 +435,8 @@ __device__ __forceinline__ bool fasta_stream(const TextParams &tp, uint32_t cls,
   return (tp.fasta_routes >> (2u * cls + m)) & 1u;
 }
 
+// kTooLong (TextParams.too_long_route; the four-route kernels): the pair TooLong catches is written, as route 3
+template <bool kTooLong = false>
 __device__ __forceinline__ RecordShape record_shape(const FormatArgs &a, const TextParams &tp, uint32_t r) {
   RecordShape s;
   const ReadView r1 = read_view(a, 0, r);
@@ -445,12 +449,13 @@ __device__ __forceinline__ RecordShape record_shape(const FormatArgs &a, const T
   if (tp.has_umi) tag = 1u + r1.cap_len + (tp.paired ? r2.cap_len : r1.cap2_len);
   s.route = (flags & tp.flag_too_short) ? 1u : ((tp.untrimmed_filter && (flags & tp.flag_untrimmed)) ? 2u : 0u);
   // TooLong -> TooManyN -> TooManyExpectedErrors (pair filter "any": the OR of the mates' bits), behind TooShort and
-  // in front of IsUntrimmedAny: no file for any of them, the pair counts under the first that catches it
+  // in front of IsUntrimmedAny: no file for any of them (kTooLong: route 3 for the first), the pair counts under the
+  // first that catches it
   s.why = 0;
   if (tp.filters && s.route != 1u) {
     const uint32_t xf = (xflags_of(a, 0, r) | (tp.paired ? xflags_of(a, 1, r) : 0u)) & tp.filters;
     if (xf) {
-      s.route = kRouteDiscard;
+      s.route = (kTooLong && (xf & CS_X_TOO_LONG)) ? 3u : kRouteDiscard;  // (why counts the pair either way)
       s.why = (xf & CS_X_TOO_LONG) ? 1u : ((xf & CS_X_TOO_MANY_N) ? 1u << 10 : 1u << 20);
     }
   }
@@ -476,43 +481,49 @@ __device__ __forceinline__ void add_discards(TextMeta *meta, uint32_t packed) {
 }
 
 // (a rejected batch is not formatted: sizes derived from half-parsed records could exceed the output buffers)
+// kRoutes = 3: the plain plan.  kRoutes = 4: a too-long plan (TextParams.too_long_route), route 3 = the pairs TooLong
+// caught; 2 * kRoutes columns in blk / totals.  A lane behind the last record holds route kRoutes: in no column.
+// No plan but a too-long plan launches the <4> pair.
+template <uint32_t kRoutes>
 __global__ void __launch_bounds__(256) format_sizes(FormatArgs a, TextParams tp) {
   __shared__ uint32_t sh[8];
   if (a.meta->err != ~0ull) return;
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  RecordShape s = {3u, {0u, 0u}, 0u};
-  if (r < a.n) s = record_shape(a, tp, r);
+  RecordShape s = {kRoutes, {0u, 0u}, 0u};
+  if (r < a.n) s = record_shape<kRoutes == 4u>(a, tp, r);
 #pragma unroll
-  for (uint32_t c = 0; c < 6; ++c) {
+  for (uint32_t c = 0; c < 2u * kRoutes; ++c) {
     uint32_t total;
     (void)block_scan_256(s.route == (c >> 1) ? s.len[c & 1] : 0u, total, sh);
-    if (threadIdx.x == 0) a.blk[blockIdx.x * 6u + c] = total;
+    if (threadIdx.x == 0) a.blk[blockIdx.x * (2u * kRoutes) + c] = total;
   }
 }
 
+template <uint32_t kRoutes>
 __global__ void __launch_bounds__(256) format_offsets(FormatArgs a, TextParams tp) {
   __shared__ uint32_t sh[8];
   if (a.meta->err != ~0ull) return;
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  RecordShape s = {3u, {0u, 0u}, 0u};
-  if (r < a.n) s = record_shape(a, tp, r);
+  RecordShape s = {kRoutes, {0u, 0u}, 0u};
+  if (r < a.n) s = record_shape<kRoutes == 4u>(a, tp, r);
   // where a route's stream starts inside the mate's buffer: behind the routes in front of it
-  unsigned long long base[3][2];
+  unsigned long long base[kRoutes][2];
   for (int m = 0; m < 2; ++m) {
     base[0][m] = 0;
     base[1][m] = a.totals[0 * 2 + m];
     base[2][m] = base[1][m] + a.totals[1 * 2 + m];
+    if (kRoutes == 4u) base[kRoutes - 1u][m] = base[2][m] + a.totals[2 * 2 + m];
   }
   uint32_t mine[2] = {0, 0};
 #pragma unroll
-  for (uint32_t c = 0; c < 6; ++c) {
+  for (uint32_t c = 0; c < 2u * kRoutes; ++c) {
     uint32_t total;
     const uint32_t local = block_scan_256(s.route == (c >> 1) ? s.len[c & 1] : 0u, total, sh);
-    if (s.route == (c >> 1)) mine[c & 1] = (uint32_t)base[c >> 1][c & 1] + a.blk[blockIdx.x * 6u + c] + local;
+    if (s.route == (c >> 1)) mine[c & 1] = (uint32_t)base[c >> 1][c & 1] + a.blk[blockIdx.x * (2u * kRoutes) + c] + local;
   }
-  uint32_t counts[3];
+  uint32_t counts[kRoutes];
 #pragma unroll
-  for (uint32_t q = 0; q < 3; ++q) {
+  for (uint32_t q = 0; q < kRoutes; ++q) {
     uint32_t total;
     (void)block_scan_256(s.route == q ? 1u : 0u, total, sh);
     counts[q] = total;
@@ -538,13 +549,18 @@ __global__ void __launch_bounds__(256) format_offsets(FormatArgs a, TextParams t
   if (threadIdx.x == 0) {
     for (uint32_t q = 0; q < 3; ++q)
       if (counts[q]) atomicAdd(&a.meta->route_count[q], counts[q]);
+    if (kRoutes == 4u)  // (the summary keeps its three routes; the fourth is in the route block alone)
+      for (uint32_t q = 0; q < kRoutes; ++q)
+        if (counts[q]) atomicAdd(&a.route_count[q], counts[q]);
     add_discards(a.meta, discarded);
     for (uint32_t m = 0; m < 2; ++m)
       if (kept_bp[m]) atomicAdd(&a.meta->written_bp[m], (unsigned long long)kept_bp[m]);
     if (blockIdx.x == 0) {
       for (int m = 0; m < 2; ++m) {
-        a.meta->out_bytes[m] = a.totals[m] + a.totals[2 + m] + a.totals[4 + m];
+        a.meta->out_bytes[m] = a.totals[m] + a.totals[2 + m] + a.totals[4 + m] + (kRoutes == 4u ? a.totals[2u * (kRoutes - 1u) + m] : 0ull);
         for (int q = 0; q < 3; ++q) a.meta->route_bytes[q][m] = a.totals[q * 2 + m];
+        if (kRoutes == 4u)
+          for (uint32_t q = 0; q < kRoutes; ++q) a.route_bytes[q * 2u + m] = a.totals[q * 2u + m];
       }
     }
   }

@@ -37,7 +37,7 @@ class _FormatParams(C.Structure):
     _fields_ = [
         ("paired", C.c_int32), ("has_umi", C.c_int32), ("untrimmed_filter", C.c_int32),
         ("reverse_complement", C.c_int32), ("flag_too_short", C.c_uint8), ("flag_untrimmed", C.c_uint8),
-        ("pad", C.c_uint8 * 2), ("suffix1", C.c_char_p * 2), ("suffix2", C.c_char_p * 2),
+        ("too_long_route", C.c_uint8), ("pad", C.c_uint8 * 1), ("suffix1", C.c_char_p * 2), ("suffix2", C.c_char_p * 2),
     ]
 
 
@@ -51,7 +51,7 @@ class _ChunkArgs(C.Structure):  # csh_chunk
 
 
 class _FormatOut(C.Structure):  # csh_format_out
-    _fields_ = [("out", (C.c_void_p * 2) * 3), ("out_len", (C.c_int64 * 2) * 3), ("counts", C.c_int64 * 3),
+    _fields_ = [("out", (C.c_void_p * 2) * 4), ("out_len", (C.c_int64 * 2) * 4), ("counts", C.c_int64 * 4),
                 ("binned", C.c_void_p * 2), ("bin_off", C.c_void_p), ("bin_counts", C.c_void_p)]
 
 
@@ -445,12 +445,13 @@ def read_chunks(path1: str, path2: Optional[str] = None, chunk_reads: int = CHUN
 _tls = threading.local()
 
 
-def _out_buffers(cap_bytes: Sequence[int]):
-    """Six output buffers (route x mate) of this thread, grown on demand and reused between chunks."""
+def _out_buffers(cap_bytes: Sequence[int], routes: int = 3):
+    """The output buffers (route x mate) of this thread, grown on demand and reused between chunks; the fourth row
+    (the too-long stream) only for a chunk that has such a route."""
     bufs = getattr(_tls, "bufs", None)
     if bufs is None:
-        bufs = _tls.bufs = [[np.empty(0, dtype=np.uint8) for _ in range(2)] for _ in range(3)]
-    for r in range(3):
+        bufs = _tls.bufs = [[np.empty(0, dtype=np.uint8) for _ in range(2)] for _ in range(4)]
+    for r in range(routes):
         for m in range(2):
             if bufs[r][m].size < cap_bytes[m]:
                 bufs[r][m] = np.empty(int(cap_bytes[m] * 1.25) + 4096, dtype=np.uint8)
@@ -507,24 +508,31 @@ def _chunk_args(chunk: Chunk, res1, cap2, res2, xflags, n_bins: int, bc) -> _Chu
 
 
 def format_chunk(chunk: Chunk, plan, res1: np.ndarray, cap2: Optional[np.ndarray], res2: Optional[np.ndarray],
-                 copy: bool = True, lease=None, xflags=None, n_bins: int = 0, bc: Optional[np.ndarray] = None):
+                 copy: bool = True, lease=None, xflags=None, n_bins: int = 0, bc: Optional[np.ndarray] = None,
+                 too_long_route: bool = False):
     """-> (data[stream][mate], counts[stream]) with the streams 0 trimmed, 1 short, 2 untrimmed and, with ``n_bins``
     (demultiplexed output; ``bc``, by default ``chunk.bc``, holds a barcode index per record), one stream 3 + b per
     barcode: the trimmed records go there, stream 0 stays empty, and a trimmed record whose index is out of range
     goes to stream 2.  ``xflags`` (the per-read ``cs_reads.xflags`` of both mates, or None): pairs TooLong / TooManyN /
     TooManyExpectedErrors take are written nowhere and counted in no stream (``chunk.n - sum(counts)`` of them).
+    ``too_long_route`` (``--too-long-output``; not with ``n_bins``): the pairs TooLong catches -- behind TooShort, in
+    front of the other two -- are written as trimmed to a fourth stream, 3, and counted there: four streams, four counts.
     ``data`` holds ``bytes``; with ``copy=False`` it holds memoryviews into this thread's reusable buffers, valid
     until the thread formats its next chunk -- except the streams 0 .. 2 flagged in ``lease[stream][mate]``,
     which are formatted straight into arena buffers and come back as :class:`Lease` objects."""
     L = _lib()
     fp = _format_params(chunk, plan)
+    if too_long_route and n_bins:
+        raise ValueError("too_long_route: stream 3 is the first barcode's in a demultiplexing run")
+    fp.too_long_route = 1 if too_long_route else 0
+    plain = 4 if too_long_route else 3  # streams with buffers of their own
     ck = _chunk_args(chunk, res1, cap2, res2, xflags, n_bins, chunk.bc if bc is None else bc)
     # what csh_format_chunk asks of every buffer of a mate (cutseq_host.c)
     cap_bytes = [len(chunk.raw1) + 528 * chunk.n + 16, (len(chunk.raw2) + 528 * chunk.n + 16) if chunk.paired else 16]
-    bufs = _out_buffers(cap_bytes)
-    leased = [[None, None] for _ in range(3)]
+    bufs = _out_buffers(cap_bytes, plain)
+    leased = [[None, None] for _ in range(plain)]
     out = _FormatOut()
-    for r in range(3):
+    for r in range(plain):
         for m in range(2):
             if lease is not None and lease[r][m] and not copy and not (n_bins and r == 0):
                 leased[r][m] = ARENA.take(cap_bytes[m])
@@ -550,23 +558,25 @@ def format_chunk(chunk: Chunk, plan, res1: np.ndarray, cap2: Optional[np.ndarray
         err.record = i  # index of the first such pair inside the chunk
         raise err
     views = [[(Lease(leased[r][m], int(out.out_len[r][m])) if leased[r][m] is not None
-               else memoryview(bufs[r][m])[: out.out_len[r][m]]) for m in range(2)] for r in range(3)]
+               else memoryview(bufs[r][m])[: out.out_len[r][m]]) for m in range(2)] for r in range(plain)]
     views += [[memoryview(bufs[0][m])[bin_off[m][b]: bin_off[m][b + 1]] for m in range(2)] for b in range(n_bins)]
-    counts = [int(c) for c in out.counts] + [int(c) for c in bin_counts]
+    counts = [int(c) for c in out.counts][:plain] + [int(c) for c in bin_counts]
     if copy:
         return [[bytes(v) for v in row] for row in views], counts
     return views, counts
 
 
 def finish_chunk(chunk: Chunk, plan, res1, cap2, res2, gz: Sequence[Sequence[Optional[bool]]], level: int = 1,
-                 n_bins: int = 0, xflags=None):
+                 n_bins: int = 0, xflags=None, too_long_route: bool = False):
     """Worker-thread job of the CLI: format one chunk and turn each wanted stream into what goes to disk:
     one gzip member (bytes), or the plain text (a :class:`Lease` on an arena buffer, or bytes for a barcode's
     stream).  ``gz[stream][mate]`` is True / False for compressed / plain outputs and None where no file is open.
     With ``n_bins`` (a demultiplexing run, ``chunk.bc`` filled) the trimmed route is split by barcode: streams
-    3 .. 3 + n_bins - 1.  -> (blobs[stream][mate], counts per stream)."""
-    lease = [[gz[r][m] is False for m in range(2)] for r in range(3)]
-    views, counts = format_chunk(chunk, plan, res1, cap2, res2, copy=False, lease=lease, xflags=xflags, n_bins=n_bins)
+    3 .. 3 + n_bins - 1; with ``too_long_route`` stream 3 holds the pairs TooLong caught.
+    -> (blobs[stream][mate], counts per stream)."""
+    lease = [[gz[r][m] is False for m in range(2)] for r in range(4 if too_long_route else 3)]
+    views, counts = format_chunk(chunk, plan, res1, cap2, res2, copy=False, lease=lease, xflags=xflags, n_bins=n_bins,
+                                 too_long_route=too_long_route)
     blobs = [[None, None] for _ in views]
     for s, row in enumerate(views):
         for m, v in enumerate(row):

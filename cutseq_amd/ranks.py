@@ -298,6 +298,7 @@ def run_parent(argv: List[str], args, tp) -> Optional[dict]:
     world = int(args.ranks)
     paths = list(args.input_file)
     names_all = [n for names in (args.output_file, args.short_file, args.untrimmed_file,
+                                 getattr(args, "too_long_file", None) or [],
                                  [getattr(args, "info_file", None)]) for n in names if n]
     if "-" in paths or "-" in names_all:
         logging.warning(f"--ranks {world} ignored: standard input / output cannot be shared between ranks.")
@@ -357,6 +358,8 @@ def output_groups(args) -> dict:
     groups = {"output_file": args.output_file, "short_file": args.short_file, "untrimmed_file": args.untrimmed_file}
     for b, names in enumerate(getattr(args, "demux_files", None) or []):  # demultiplexing: a pair of files per barcode
         groups[f"demux_files:{b}"] = names
+    if getattr(args, "too_long_file", None):  # --too-long-output: parts like the too-short files'
+        groups["too_long_file"] = args.too_long_file
     if getattr(args, "info_file", None):  # every rank's table of its share; concatenated in rank order like the records
         groups["info_file"] = [args.info_file]
     if getattr(args, "demux_files", None):

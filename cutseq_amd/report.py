@@ -169,7 +169,7 @@ def _host_threads() -> int:
 
 
 def json_report(tp: TrimPlan, totals: dict, barcode, input1, input2, output1, output2, short1, short2,
-                untrimmed1, untrimmed2, info_file=None) -> dict:
+                untrimmed1, untrimmed2, info_file=None, too_long_files=None) -> dict:
     """Same header block as the reference's ``json_report`` (run.py:262-283) followed by the
     ``Statistics.as_json()`` sections; engine-specific counters live under ``"engine"``."""
     paired = tp.paired
@@ -239,6 +239,9 @@ def json_report(tp: TrimPlan, totals: dict, barcode, input1, input2, output1, ou
     }
     if info_file:  # (a run without --info-file keeps the block it always had)
         d["output"]["info_file"] = info_file
+    if too_long_files:  # (--too-long-output, added the same way; the counts above are what they are without it)
+        d["output"]["too_long1"] = too_long_files[0]
+        d["output"]["too_long2"] = too_long_files[1] if paired and len(too_long_files) > 1 else None
     return d
 
 

@@ -105,6 +105,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("-M", "--max-length", type=int, default=None, metavar="LEN",
                    help="Extension (cutadapt's option): discard reads longer than LEN after trimming. A pair is discarded "
                         "if either read is too long. The counterpart of -m.")
+    p.add_argument("--too-long-output", dest="too_long_file", type=str, nargs="+", metavar="FILE",
+                   help="Extension (cutadapt's option): write the reads -M/--max-length catches to FILE (one per input "
+                        "file) instead of discarding them: as trimmed, like the too-short files. Needs -M; not with "
+                        "--demux-barcodes.")
     p.add_argument("--max-ee", "--max-expected-errors", dest="max_ee", type=float, default=None, metavar="ERRORS",
                    help="Extension (cutadapt's option): discard reads whose expected number of errors, the sum of "
                         "10^(-Q/10) over the trimmed read's qualities, exceeds ERRORS. A pair is discarded if either "
@@ -215,6 +219,15 @@ def resolve_args(args):
                   "no error count to report.")
         if not switches.enabled("TEXT_PATH"):
             _fail("--info-file needs the text path: the table is written on the GPU (CUTSEQ_TEXT_PATH=0 is set).")
+    too_long_file = getattr(args, "too_long_file", None)
+    if too_long_file:
+        if max_length is None:
+            _fail("--too-long-output needs -M/--max-length: without it no read is too long.")
+        if args.demux_barcodes:
+            _fail("--too-long-output cannot be combined with --demux-barcodes: the output class it would take on the "
+                  "GPU is the barcodes' there.")
+        if inputs:  # (no default name from -O: the given names or none)
+            args.too_long_file = output_paths(too_long_file, inputs, None, "too-long")
     if not inputs:
         # the reference dies with an IndexError here (run.py:1079-1083); same exit class, clearer message
         _fail("Input file is required.")
@@ -414,6 +427,7 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
     # the open file (or None) per [stream][mate]
     outs = [[fastq.OutputFile(n) if n else None for n in names]
             for names in textio.output_name_groups(args, paired, tp.swap_outputs, n_bins)]
+    too_long_route = len(outs) == 4 and not n_bins  # --too-long-output: stream 3 holds what -M catches
     # which (route, mate) streams go to disk, and whether they are gzip
     gz = [[(fh.gz if fh is not None else None) for fh in (group + [None])[:2]] for group in outs]
 
@@ -441,11 +455,12 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
     def finish(chunk, r1, cap2, r2):
         """Pool job: records -> bytes on their way to disk; also this chunk's share of the report."""
         try:
-            blobs, counts = fastq.finish_chunk(chunk, tp, r1, cap2, r2, gz, n_bins=n_bins, xflags=chunk.xflags)
+            blobs, counts = fastq.finish_chunk(chunk, tp, r1, cap2, r2, gz, n_bins=n_bins, xflags=chunk.xflags,
+                                               too_long_route=too_long_route)
             part = report.new_totals()
             report.account_chunk(part, tp, chunk.len1, r1, chunk.len2 if paired else None, r2 if paired else None,
                                  xflags=chunk.xflags)
-            part["routes"] = counts
+            part["routes"] = counts[:3] if too_long_route else counts  # (its pairs are the totals' "too_long" already)
             return blobs, part
         finally:
             chunk.release()
@@ -542,7 +557,7 @@ def run_cutseq(args, argv=None):
             args.output_file[0], args.output_file[1] if paired else None,
             args.short_file[0], args.short_file[1] if paired else None,
             args.untrimmed_file[0], args.untrimmed_file[1] if paired else None,
-            info_file=getattr(args, "info_file", None))
+            info_file=getattr(args, "info_file", None), too_long_files=getattr(args, "too_long_file", None))
         report.write_json(args.json_file, rep)
     print(report.minimal_report(tp, totals), file=sys.stderr)
     return totals

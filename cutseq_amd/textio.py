@@ -599,8 +599,9 @@ class TextWorker(fanout.Worker):
     _tick = staticmethod(_tick)
 
     def __init__(self, tp, device: int, chunk_reads: int, compress: bool = False, bins: int = 0,
-                 fasta_routes: int = 0, info: int = 0):
+                 fasta_routes: int = 0, info: int = 0, too_long_route: bool = False):
         super().__init__(f"cutseq-gpu{device}")
+        self.too_long_route = too_long_route  # --too-long-output: the pairs -M catches are a fourth stream (route 3)
         self.info = info  # abi.CS_INFO_* bits: the batches also yield the --info-file table
         self.tp, self.device, self.chunk_reads, self.compress = tp, device, chunk_reads, compress
         self.fasta_routes = fasta_routes  # bit 2 * class + mate: that stream's records leave as FASTA
@@ -628,7 +629,8 @@ class TextWorker(fanout.Worker):
         self.capacity = max(self.capacity, int(text_bytes * 1.25) + (1 << 20))
         self.text = textpath.TextEngine(self.engine, slots=self.SLOTS, max_text_bytes=self.capacity,
                                         max_records=self.chunk_reads, stride=self.stride, compress=self.compress,
-                                        bins=self.bins, fasta_routes=self.fasta_routes, info=self.info)
+                                        bins=self.bins, fasta_routes=self.fasta_routes, info=self.info,
+                                        too_long_route=self.too_long_route)
 
     def submit(self, slot: int, item):
         b1, b2 = item
@@ -652,7 +654,7 @@ class TextWorker(fanout.Worker):
         if max(res.n_long) * 64 > b1.n and self.stride < abi.CS_MAX_STRIDE:
             self.want_stride = max(self.want_stride, min(abi.CS_MAX_STRIDE, (int(res.max_len) + 3) // 4 * 4))
         sizes = counts = None
-        if self.bins:
+        if self.bins or self.too_long_route:
             sizes, _, counts = self.text.routes(slot)
         discards = self.text.discards(slot) if self.tp.has_filters else None
         out = [fastq.PINNED.take(max(int(res.out_bytes[m]), 1)) for m in range(2 if b2 is not None else 1)]
@@ -718,7 +720,8 @@ def output_formats(groups, has_qualities: bool) -> int:
     ``OutputFiles.open_record_writer`` hands each name to dnaio on its own (cutseq/run.py:437-441, 449, 465, 754-758).
 
     ``groups``: the files by the stream they receive -- [trimmed, too short, untrimmed, barcode 0, barcode 1, ...],
-    each a list of names by mate (None / "": no such file), AFTER any swap of the mates' files: the format goes with
+    or [trimmed, too short, untrimmed, too long] for a run with ``--too-long-output`` (class 3 as well: such a run has
+    no barcodes) --, each a list of names by mate (None / "": no such file), AFTER any swap of the mates' files: the format goes with
     the file.  Bit ``2 * class + mate`` of the result is set when that stream leaves as FASTA; every barcode's files are
     class 3 and must agree per mate (their names come from one template).  Per file the rule of
     :func:`output_format`: a FASTA / FASTQ extension decides, any other name follows the input; a FASTQ file of an
@@ -753,14 +756,18 @@ def output_name_groups(args, paired: bool, swap_outputs: bool, n_bins: int) -> L
     """The output files' names by the stream they receive -- [trimmed, too short, untrimmed, barcode 0, barcode 1, ...],
     one entry per mate each (None: no such file).  Paired --auto-rc on a '-' library swaps the mates' trimmed files
     (cutseq/run.py:787-791), the barcodes' too; a demultiplexing run has no common trimmed file, and one handed over
-    without files for its barcodes gets one nameless group for their streams (dropped, and of class 3 all the same)."""
+    without files for its barcodes gets one nameless group for their streams (dropped, and of class 3 all the same).
+    ``--too-long-output`` (never in a demultiplexing run) adds a fourth group, not swapped: only the trimmed pair is."""
     mates = 2 if paired else 1
     groups = [list(args.output_file) if not n_bins else [], list(args.short_file or []), list(args.untrimmed_file or [])]
     if n_bins:
         groups += [list(names) for names in (getattr(args, "demux_files", None) or [[]])]
+    too_long = list(getattr(args, "too_long_file", None) or [])
+    if too_long and not n_bins:
+        groups.append(too_long)
     groups = [(g + [None, None])[:mates] for g in groups]
     if paired and swap_outputs:
-        groups = [g if q in (1, 2) else g[::-1] for q, g in enumerate(groups)]
+        groups = [g if q in (1, 2) or (q == 3 and not n_bins) else g[::-1] for q, g in enumerate(groups)]
     return groups
 
 
@@ -820,7 +827,8 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
     totals = report.new_totals()
     t_start = time.perf_counter()
     report.phase("readers and writers open")
-    workers = [TextWorker(tp, dev, chunk_reads, compress, n_bins, fasta_routes, info_flags) for dev in devices]
+    too_long_route = len(name_groups) == 4 and not n_bins  # --too-long-output: what -M catches is route 3
+    workers = [TextWorker(tp, dev, chunk_reads, compress, n_bins, fasta_routes, info_flags, too_long_route) for dev in devices]
     if n_bins:
         totals["routes"] += [0] * n_bins
     budget = threading.Semaphore(2 * len(workers) * TextWorker.SLOTS + 2)  # batches between reader and disk
@@ -853,8 +861,8 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         res = item.res
         totals["in_pairs"] += item.n
         progress.update(item.n)
-        if item.counts is not None:  # (demultiplexing: [0] stays 0, the barcodes' pairs are routes 3 ..)
-            for q in range(len(item.counts)):
+        if item.counts is not None:  # (demultiplexing: [0] stays 0, the barcodes' pairs are routes 3 ..; a too-long
+            for q in range(len(totals["routes"])):  # route is no route of the totals: "too_long" below counts its pairs)
                 totals["routes"][q] += int(item.counts[q])
         else:
             for q in range(3):

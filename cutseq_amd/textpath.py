@@ -63,8 +63,10 @@ class TextEngine:
 
     def __init__(self, engine: TrimEngine, slots: int = 3, max_text_bytes: int = 64 << 20, max_records: int = 1 << 18,
                  stride: int = 152, compress: bool = False, bins: int = 0, fasta: bool = False,
-                 fasta_routes: int = 0, info: int = 0):
-        """``info``: ``abi.CS_INFO_*`` bits -- the batch also yields cutadapt's ``--info-file`` table for read 1
+                 fasta_routes: int = 0, info: int = 0, too_long_route: bool = False):
+        """``too_long_route``: cutadapt's ``--too-long-output`` -- the pairs ``-M`` catches are written as route 3, a
+        fourth stream (:meth:`routes`), class 3 of ``fasta_routes``; the plan needs ``max_length`` and no ``bins``.
+        ``info``: ``abi.CS_INFO_*`` bits -- the batch also yields cutadapt's ``--info-file`` table for read 1
         (:meth:`info`, :meth:`fetch_info`).  ``compress``: every route's output leaves the device as one gzip member (``res.route_bytes`` then counts
         compressed bytes): what ``.gz`` output files take as they are.  ``bins``: the plan demultiplexes (table form)
         into that many barcodes; the trimmed records of barcode b are route 3 + b (:meth:`routes`).  ``fasta``: every
@@ -85,7 +87,8 @@ class TextEngine:
         p.n_bins = int(bins)
         p.info = int(info)
         self.info_flags = int(info)
-        self.n_routes = 3 + int(bins)
+        p.too_long_route = 1 if too_long_route else 0
+        self.n_routes = 3 + int(bins) + (1 if too_long_route else 0)
         p.max_tag = max_tag(plan)
         self._keep = []  # the literals must outlive the call
         for field, chain in (("suffix1", plan.r1), ("suffix2", plan.r2)):

@@ -412,13 +412,21 @@ typedef struct cs_text_params {
                                  754-758 -- or the output files are named .fasta / .fa                              */
   uint8_t fasta_routes;       /* per-stream form of fasta_out, for output files that name different formats: bit
                                  2 * class + mate (mate 0 / 1) set = that stream's records leave as FASTA.  class 0 =
-                                 trimmed, 1 = too short, 2 = untrimmed, 3 = the routes of all barcodes (n_bins > 0).  A
+                                 trimmed, 1 = too short, 2 = untrimmed, 3 = the routes of all barcodes (n_bins > 0) or the
+                                 too-long route (too_long_route; the two never meet).  A
                                  stream is FASTA when fasta_out is set or its bit is; 0 = fasta_out alone decides.  A
                                  bit of a stream the plan does not have (mate 2 of a single-end plan, class 3 without
-                                 bins) is CS_ERR_ARG                                                                 */
+                                 bins or a too-long route) is CS_ERR_ARG                                                                 */
   uint8_t info;               /* CS_INFO_* bits; 0 = no table (the kernels launched are then exactly those of a
                                  cs_text without the member).  CS_ERR_ARG on a plan with a CS_OP_DEMUX op            */
-  uint8_t _reserved[1];
+  uint8_t too_long_route;     /* cutadapt's --too-long-output: a pair TooLong (cs_plan_set_max_length) catches behind
+                                 TooShort is written, not discarded -- as trimmed, to route 3: four streams per mate,
+                                 back to back in route order (0 trimmed, 1 too short, 2 untrimmed, 3 too long), sizes
+                                 through cs_text_routes; fasta_routes class 3 and a gzip member of its own (compress)
+                                 are that stream's.  The other two discarding filters still discard.  0 (what the byte
+                                 held while it was reserved): TooLong discards, three streams, the kernels launched are
+                                 those of a cs_text without the member.  CS_ERR_ARG on a plan without
+                                 cs_plan_set_max_length, and together with n_bins (class 3 is the barcodes' there)   */
 } cs_text_params;
 
 typedef struct cs_text_result {
@@ -426,7 +434,9 @@ typedef struct cs_text_result {
   uint32_t error_record;      /* first offending record of the batch                                            */
   uint32_t max_len;           /* longest read of the batch                                                      */
   uint32_t n_records;
-  uint32_t route_count[3];    /* records (pairs) per route (n_bins > 0: [0] = all barcodes together; likewise below) */
+  uint32_t route_count[3];    /* records (pairs) per route (n_bins > 0: [0] = all barcodes together; likewise below).
+                                 too_long_route: these, route_bytes and text_bytes keep describing routes 0 .. 2 --
+                                 the fourth stream's sizes come from cs_text_routes -- while out_bytes sums all four */
   uint32_t n_too_many_n;      /* pairs discarded by TooManyN (cs_plan_set_max_n), in no route; cs_text_discards has
                                  this and the other two discarding filters' counts                                */
   uint64_t route_bytes[3][2]; /* [route][mate]                                                                  */
@@ -450,13 +460,15 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
                    uint32_t n_records);
 /* Blocks until the slot's batch is formatted on the device; sizes and errors in *res. */
 int cs_text_wait(cs_text *t, uint32_t slot, cs_text_result *res);
-/* Behind cs_text_wait: the sizes of every route stream, 3 + n_bins of them: bytes[route][mate] as cs_text_fetch
+/* Behind cs_text_wait: the sizes of every route stream, 3 + n_bins of them (4 with too_long_route): bytes[route][mate] as cs_text_fetch
  * delivers them (gzip members if compress), text_bytes[route][mate] uncompressed, count[route] records.  The streams of
  * a mate lie in route order in the fetched buffer.  Any of the three pointers may be NULL. */
 int cs_text_routes(cs_text *t, uint32_t slot, uint64_t *bytes, uint64_t *text_bytes, uint32_t *count);
 /* Behind cs_text_wait: the pairs (single-end: reads) of the slot's batch that the discarding filters took, by
  * precedence: pairs[0] TooLong, pairs[1] TooManyN (= cs_text_result.n_too_many_n), pairs[2] TooManyExpectedErrors.
- * A pair that several of them catch counts once, under the first in that order; one that TooShort catches in none. */
+ * A pair that several of them catch counts once, under the first in that order; one that TooShort catches in none.
+ * With cs_text_params.too_long_route the pairs TooLong caught are written, not discarded: pairs[0] keeps counting them
+ * (it equals count[3] of cs_text_routes), and stays where a report takes its too_long figure from. */
 int cs_text_discards(cs_text *t, uint32_t slot, uint32_t pairs[3]);
 /* Copies the output text (res->out_bytes[m] bytes per mate) into the caller's buffers and blocks until it is
  * there; the slot is free for the next cs_text_submit afterwards.  dst2 == NULL for single-end. */
