@@ -641,8 +641,10 @@ int cs_plan_create(const cs_op *ops_r1, int n1, const cs_op *ops_r2, int n2, con
         csdev::DevOp &f = p->host.ops[m][0];
         const bool free_ends = (f.op.align_flags & (CS_QUERY_START | CS_QUERY_STOP)) == (CS_QUERY_START | CS_QUERY_STOP);
         if (f.op.kind == CS_OP_ADAPTER && f.filter_mode == csdev::FILTER_MYERS32 && !f.op.reversed && free_ends &&
-            f.op.shortcut == CS_SHORTCUT_NONE && !f.exists_only && log_friendly(f.op.m, f.op.k))
+            f.op.shortcut == CS_SHORTCUT_NONE && !f.exists_only && log_friendly(f.op.m, f.op.k)) {
           f.solo_first = 1;
+          f.quiet_groups = (uint32_t)csdev::quiet_columns((int)f.op.align_flags, f.op.m, f.op.k, nullptr) / 8u;
+        }
       }
       if (!allow || cnt[m] < 2) continue;
       csdev::DevOp &a = p->host.ops[m][0];
@@ -673,6 +675,7 @@ int cs_plan_create(const cs_op *ops_r1, int n1, const cs_op *ops_r2, int n2, con
           }
         a.pair_tn[(j - 1) >> 3] |= (uint32_t)(best + 1) << (4 * ((j - 1) & 7));
       }
+      a.quiet_groups = (uint32_t)csdev::quiet_columns((int)b.op.align_flags, b.op.m, b.op.k, a.pair_tn) / 8u;
     }
   }
   *out = p;
@@ -708,6 +711,18 @@ int cs_plan_set_max_ee(cs_plan *plan, double errors) {
 int cs_plan_set_ee_reversed(cs_plan *plan, int reversed) {
   if (!plan) return fail(CS_ERR_ARG, "null plan");
   plan->host.ee_reversed = reversed ? 1u : 0u;
+  return CS_OK;
+}
+
+int cs_plan_walk_info(const cs_plan *plan, int mate, uint32_t info[6]) {
+  if (!plan || !info) return fail(CS_ERR_ARG, "null plan or info");
+  if (mate < 1 || mate > 2) return fail(CS_ERR_ARG, "mate %d: 1 or 2", mate);
+  memset(info, 0, 6 * sizeof info[0]);
+  if (plan->host.n_ops[mate - 1] < 1) return CS_OK;
+  const csdev::DevOp &a = plan->host.ops[mate - 1][0];
+  info[0] = a.pair_next ? 2u : a.solo_first ? 1u : 0u;
+  info[1] = a.quiet_groups;
+  for (int i = 0; i < 4; ++i) info[2 + i] = a.pair_tn[i];
   return CS_OK;
 }
 

@@ -122,7 +122,28 @@ struct DevOp {
   // cut_pack[i] = cut_len (16 bits, signed) | conditional << 16 | capture << 17 | force_min_len << 19 of its i-th cut
   uint32_t cut_run;
   uint32_t cut_pack[kCutRun];
+  // scan kernel, on the op that opens the chain (pair_next or solo_first): the walk's first quiet_groups groups of eight
+  // columns hold no candidate of the exact op (quiet_columns below) and no column in FRONT of their last one has
+  // T(j) >= 0; they run without scores, tests and log (myers_pair)
+  uint32_t quiet_groups;
 };
+
+// The leading walk's quiet columns: the largest multiple of eight Q such that the exact op (m rows, k errors) has no
+// candidate in a column <= Q -- row m costs at least m - j in column j unless the reference start is free, the columns
+// Aligner.locate visits apart (column_range: all of them, the op's query ends are free) -- and, where an existence-only
+// op walks along (tn: its T(j) + 1 of columns 1..32, DevOp::pair_tn; null: none), T(j) = -1 for every j < Q.
+__host__ __device__ inline int quiet_columns(int flags, int m, int k, const uint32_t *tn) {
+  if (flags & CS_REF_START) return 0;
+  int q = 0;
+  while (q + 8 < m - k && q + 8 <= 32) {
+    bool clear = true;
+    for (int j = q > 0 ? q : 1; j < q + 8 && tn; ++j)  // (column q closed the groups so far: now it lies in front of the last one)
+      clear = clear && ((tn[(j - 1) >> 3] >> (4 * ((j - 1) & 7))) & 15u) == 0u;
+    if (!clear) break;
+    q += 8;
+  }
+  return q;
+}
 
 struct DevPlan {
   cs_params params;
@@ -1373,10 +1394,23 @@ __device__ __forceinline__ Verdict myers_pair(const DevOp &da, const DevOp &db, 
     advance();
 #pragma unroll
     for (int u = 0; u < QD; ++u) refill(u, word_code<true>(wcur, u));
-    auto group = [&](auto early_tag, uint32_t tw) {
-      constexpr bool EARLY = decltype(early_tag)::value;
+    constexpr int STEADY = 0, EARLY_G = 1, QUIET = 2;
+    auto group = [&](auto body_tag, uint32_t tw) {
+      constexpr bool EARLY = decltype(body_tag)::value == EARLY_G;
       const uint32_t wnext = take();  // the bases of the NEXT group
       advance();
+      if constexpr (decltype(body_tag)::value == QUIET) {
+        // no column of the group can hold a candidate of either op (DevOp::quiet_groups): the bare recurrences
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+          myers_step_noscore<false>(st, qb[u % QD], 0u);
+          if constexpr (HAS_A) myers_step_noscore<false>(sa, qa[u % QD], 0u);
+          refill(u % QD, u + QD < NB ? word_code<true>(wcur, u + QD) : word_code<true>(wnext, u + QD - NB));
+        }
+        wcur = wnext;
+        j += NB;
+        return;
+      }
       int sc[NB];
 #pragma unroll
       for (int u = 0; u < NB; ++u) {
@@ -1412,14 +1446,29 @@ __device__ __forceinline__ Verdict myers_pair(const DevOp &da, const DevOp &db, 
     const int early_groups = (ma + ka + NB - 1) >> 3;
     // two loops, not one with a switch inside: the two group bodies leave the five state registers in different
     // places, and a common loop head pays ten register moves per group to reconcile them
-    if constexpr (HAS_A) {
-      int g = 0;  // (used inside the loop only: wave-uniform)
-      do {
-        group(std::true_type{}, g == 0 ? tn0 : g == 1 ? tn1 : g == 2 ? tn2 : tn3);
-        ++g;
-      } while (g < early_groups && j + NB - 1 <= n);
+    // the quiet groups; behind them both scores come from the vertical deltas -- exact values, not bounds -- and the
+    // last quiet column, the only one of them that T may admit, gets its 5' test
+    const int quiet_j = (int)da.quiet_groups * NB + 1;  // the first column behind them
+    if (quiet_j > 1) {
+      do group(std::integral_constant<int, QUIET>{}, 0u);
+      while (j < quiet_j && j + NB - 1 <= n);
+      st.score = (int)__builtin_popcount(st.Pv) - (int)(__builtin_popcount(st.Mv) + (uint32_t)sh) - k1;
+      if constexpr (HAS_A) {
+        sa.score = (int)__builtin_popcount(sa.Pv) - (int)(__builtin_popcount(sa.Mv) + fill_a);
+        const int tq = (int)(da.pair_tn[da.quiet_groups - 1u] >> 28);  // T + 1 of the last quiet column
+        flag |= sa.score - (j == quiet_j ? tq : 0);  // (a read that ends before: T = -1 where it stopped)
+      }
     }
-    while (j + NB - 1 <= n) group(std::false_type{}, 0u);
+    if constexpr (HAS_A) {
+      // (g counts from the plan's constant, not from where a lane's quiet groups stopped: a lane that stopped early has
+      // no whole group left, and a wave-uniform g keeps the group's T word and its nibbles on the scalar unit)
+      int g = (int)da.quiet_groups;
+      while (g < early_groups && j + NB - 1 <= n) {
+        group(std::integral_constant<int, EARLY_G>{}, g == 0 ? tn0 : g == 1 ? tn1 : g == 2 ? tn2 : tn3);
+        ++g;
+      }
+    }
+    while (j + NB - 1 <= n) group(std::integral_constant<int, STEADY>{}, 0u);
     __builtin_amdgcn_s_setprio(PRIO_REST);
     // the up to NB - 1 columns behind the last whole group, as one more group of the lanes that have them (their
     // columns sit where each lane's walk stopped): the steps of both ops with exact scores, the 5' test per column,
@@ -2376,6 +2425,14 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
   x += __builtin_amdgcn_update_dpp(0, x, 0x143 /* row_bcast:31 */, 0xc, 0xf, true);
   return (uint32_t)__builtin_amdgcn_readlane(x, 63);
 }
+// The lane's index in a block of one wave, computed where it is needed: two instructions on the execution-mask
+// counters (their start value hidden from the optimiser, or the result is hoisted and lives on).  The scan kernel
+// uses it instead of threadIdx.x, which would occupy a register from the first tile to the last.
+__device__ __forceinline__ uint32_t wave_lane_fresh() {
+  uint32_t zero = 0u;
+  asm volatile("" : "+v"(zero));
+  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero));
+}
 __device__ __forceinline__ uint32_t wave_count(bool p) { return (uint32_t)__popcll(__ballot(p)); }
 
 // One lane's atomicAdd on a wave-uniform address whose answer is looked at LATER (the tile and queue reservations).
@@ -2530,7 +2587,9 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
   const bool use_filter = ((pw0 >> 24) & 0xffu) != 0;
   const bool fold_case = (pw1 & 0xffu) == CS_CASE_FOLD;
   const bool tie_ins = ((pw1 >> 8) & 0xffu) == CS_TIE_INSERTION;
+#ifdef CS_PHASE_TIMERS
   const int lane = tid;
+#endif
 
   // LDS carve-up (dwords): private mask table + slack | tile | DP scratch | queue | match-mask tables | stats
   // (the scan kernel has neither DP scratch nor queue: col_dwords == 0, no items)
@@ -2624,8 +2683,9 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
   uint32_t pend_q = 0;      // lane 0: the queue position the counter answered
   auto flush_ring = [&]() {  // parked records -> queue
     const uint32_t qb = (uint32_t)__builtin_amdgcn_readfirstlane((int)pend_q);
-    if ((uint32_t)lane < pend_count) {
-      uint4 *rec = a.defer[mate] + (size_t)(qb + (uint32_t)lane) * 2u;
+    const uint32_t lane = wave_lane_fresh();
+    if (lane < pend_count) {
+      uint4 *rec = a.defer[mate] + (size_t)(qb + lane) * 2u;
       rec[0] = ring[lane * 2];
       rec[1] = ring[lane * 2 + 1];
     }
@@ -2638,7 +2698,8 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
   // derived from it are recomputed per tile -- a handful of adds and shifts -- instead of living in registers across
   // the tile loop.  Hoisted, four of them were spilled, and their reloads -- scratch loads, answered in order behind the
   // previous tile's result stores -- made the next tile's first instructions wait for those stores.
-  uint32_t lane_fresh = threadIdx.x;
+  // (scan kernel: not even threadIdx.x itself stays in a register across the loop, see wave_lane_fresh)
+  uint32_t lane_fresh = SCAN ? wave_lane_fresh() : threadIdx.x;
   asm volatile("" : "+v"(lane_fresh));
   const int tid = (int)lane_fresh, lane = tid;
   const bool top = !SCAN && tile_id >= tiles_a;  // a batch of the queue's top region
@@ -2699,8 +2760,10 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
       if (CODED) {
         const uint32_t pad2 = (a.lds_stride_dw * 2u - S) * 2u;  // pad in bytes
         // (FAST: the re-coding that trusts the bytes and checks them, see encode4_pairs_fast; -> the lanes' differences)
-        auto stage_coded = [&](auto fast_tag) -> uint32_t {
-        constexpr bool FAST = decltype(fast_tag)::value;
+        // (LINEAR: the coded tile is linear in the source -- no pad, 16-byte aligned rows of at least a quad -- see below)
+        const bool linear = pad2 == 0 && (((uintptr_t)src) & 15u) == 0 && S >= 4;  // wave-uniform
+        auto stage_coded = [&](auto fast_tag, auto linear_tag) -> uint32_t {
+        constexpr bool FAST = decltype(fast_tag)::value, LINEAR = decltype(linear_tag)::value;
         uint32_t bad = 0, done = 0;
         EncodeConsts ec;
         FastEncodeConsts fc;
@@ -2711,10 +2774,36 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
         auto enc4 = [&](uint32_t w) -> uint32_t {
           if constexpr (FAST) return encode4_nib_fast(w, bad, fc); else return encode4_nib_v(w, ec);
         };
-        if ((((uintptr_t)src) & 15u) == 0 && S >= 4) {  // a quad then touches at most two rows
+        constexpr int kBatch = 4;  // loads in flight per lane before the first one is consumed (three rounds per 150-base tile; five in flight are no faster any more and spill five registers more)
+        constexpr uint32_t kRound = (uint32_t)TILE * kBatch;
+        if constexpr (LINEAR) {
+          // quad q of the tile lands at byte 8 q of the coded tile whatever row it lies in: one 8-byte store per quad
+          // at a constant offset from the lane's slot of the round, no row / column to keep.  The loads roll as below.
+          const uint32_t quads = total >> 2, last_q = quads - 1u;
+          const uint4 *src4 = reinterpret_cast<const uint4 *>(src);
+          uint32_t dst = tile_b + ((uint32_t)tid << 3);
+          uint4 w[kBatch];
+#pragma unroll
+          for (int u = 0; u < kBatch; ++u) w[u] = src4[min((uint32_t)tid + (uint32_t)u * TILE, last_q)];
+          auto put = [&](const uint4 &v, uint32_t off) {
+            *(lds_u64 *)(uintptr_t)(dst + off) = (unsigned long long)enc8(v.x, v.y) | ((unsigned long long)enc8(v.z, v.w) << 32);
+          };
+          uint32_t qb = 0;  // (wave-uniform)
+          for (; qb + kRound < quads; qb += kRound) {
+#pragma unroll
+            for (int u = 0; u < kBatch; ++u) {
+              put(w[u], (uint32_t)u * TILE * 8u);
+              w[u] = src4[min(qb + kRound + (uint32_t)u * TILE + (uint32_t)tid, last_q)];
+            }
+            dst += kRound * 8u;
+          }
+#pragma unroll
+          for (int u = 0; u < kBatch; ++u)
+            if (qb + (uint32_t)u * TILE + (uint32_t)tid < quads) put(w[u], (uint32_t)u * TILE * 8u);
+          done = quads << 2;
+        } else if ((((uintptr_t)src) & 15u) == 0 && S >= 4) {  // a quad then touches at most two rows
           const uint32_t quads = total >> 2;
           const uint4 *src4 = reinterpret_cast<const uint4 *>(src);
-          constexpr int kBatch = 4;  // loads in flight per lane before the first one is consumed (three rounds per 150-base tile; five in flight are no faster any more and spill five registers more)
           // row / column of this lane's first dword by one division, then advanced by the constant
           // lane stride (TILE quads) with a wrap test
           // (no integer division per tile: (x + 0.5) / S in float is further from an integer than its rounding error
@@ -2728,22 +2817,18 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
           // loads and stores in straight-line code, the wait in front of a slot leaves the three younger loads in flight.
           // A load beyond the tile's last quad (the last round is partial as a rule) re-reads that quad and is dropped.
           const uint32_t last_q = quads - 1u;  // (quads >= 1: a tile has at least one row of at least four dwords)
-          constexpr uint32_t kRound = (uint32_t)TILE * kBatch;
+          (void)enc8;
           uint4 w[kBatch];
 #pragma unroll
           for (int u = 0; u < kBatch; ++u) w[u] = src4[min((uint32_t)tid + (uint32_t)u * TILE, last_q)];
-          auto put = [&](const uint4 &v) {
-            if (pad2 == 0) {  // wave-uniform: the coded tile is linear in the source, one 8-byte store per quad
-              *(lds_u64 *)(uintptr_t)dst = (unsigned long long)enc8(v.x, v.y) | ((unsigned long long)enc8(v.z, v.w) << 32);
-            } else {
-              const uint32_t n0 = enc4(v.x), n1 = enc4(v.y);
-              const uint32_t n2 = enc4(v.z), n3 = enc4(v.w);
-              // the quad may run over the end of its row: later slots move by one pad
-              lds_write_u16(dst, 0, n0);
-              lds_write_u16(dst + ((c + 1 >= S) ? pad2 : 0u), 2, n1);
-              lds_write_u16(dst + ((c + 2 >= S) ? pad2 : 0u), 4, n2);
-              lds_write_u16(dst + ((c + 3 >= S) ? pad2 : 0u), 6, n3);
-            }
+          auto put = [&](const uint4 &v) {  // (pad2 != 0 here: the linear tile has its own form above)
+            const uint32_t n0 = enc4(v.x), n1 = enc4(v.y);
+            const uint32_t n2 = enc4(v.z), n3 = enc4(v.w);
+            // the quad may run over the end of its row: later slots move by one pad
+            lds_write_u16(dst, 0, n0);
+            lds_write_u16(dst + ((c + 1 >= S) ? pad2 : 0u), 2, n1);
+            lds_write_u16(dst + ((c + 2 >= S) ? pad2 : 0u), 4, n2);
+            lds_write_u16(dst + ((c + 3 >= S) ? pad2 : 0u), 6, n3);
           };
           auto step = [&]() {
             c += step_c;
@@ -2775,17 +2860,20 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
         }
         return bad;
         };  // stage_coded
+        auto stage = [&](auto fast_tag) -> uint32_t {
+          return linear ? stage_coded(fast_tag, std::true_type{}) : stage_coded(fast_tag, std::false_type{});
+        };
         // a wave keeps the fast form until a tile holds a byte it cannot vouch for (wave-uniform, sticky)
         bool redo = !fast_ok;
         if (fast_ok) {
-          const uint32_t bad = stage_coded(std::true_type{});
+          const uint32_t bad = stage(std::true_type{});
           if (a.fast_recode != 2u && __ballot(bad != 0u)) {  // (2: tests only -- never fall back)
             redo = true;
             fast_ok = !fast_failed;  // one odd byte now and then costs its tile a second staging; two tiles in a row
           }                          // (zero padding, soft-masked reads): the wave stays with the exact form
           fast_failed = redo;
         }
-        if (redo) (void)stage_coded(std::false_type{});
+        if (redo) (void)stage(std::false_type{});
       } else {
         for (uint32_t dw = tid; dw < total; dw += TILE) {
           const uint32_t r = dw / S;
@@ -3770,7 +3858,7 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
   CS_T_MARK(pt, 6);
   }  // persistent tile / batch loop
   if (SCAN && pend_count) {  // what is still parked when the block runs out of tiles
-    if (!pend_asked && tid == 0) pend_q = atomicAdd(&a.defer_count[mate * kTileCounterStride], pend_count);
+    if (!pend_asked && wave_lane_fresh() == 0u) pend_q = atomicAdd(&a.defer_count[mate * kTileCounterStride], pend_count);
     flush_ring();
   }
 #ifdef CS_PHASE_TIMERS
@@ -3789,8 +3877,9 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
 
   // one global atomic per counter per block (the LDS accumulators are 32-bit: a block sees
   // far fewer than 2^32 bases)
-  if (tid < kStatWords && sacc[tid])
-    atomicAdd(&a.stats[(size_t)mate * kStatWords + tid], (unsigned long long)sacc[tid]);
+  const int tid_end = SCAN ? (int)wave_lane_fresh() : tid;
+  if (tid_end < kStatWords && sacc[tid_end])
+    atomicAdd(&a.stats[(size_t)mate * kStatWords + tid_end], (unsigned long long)sacc[tid_end]);
 }
 
 }  // namespace csdev

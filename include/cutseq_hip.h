@@ -298,6 +298,13 @@ int cs_plan_set_max_ee(cs_plan *plan, double errors);
  * is written.  The other two filters do not depend on the orientation.  Default 0. */
 int cs_plan_set_ee_reversed(cs_plan *plan, int reversed);
 
+/* What the scan kernel's leading walk was compiled to for a mate (1 or 2); for tests and tools, no caller needs it.
+ * info[0]: 0 no leading walk, 1 the forward op that opens the chain walks alone, 2 the existence-only 5' op and the 3'
+ * op behind it walk together; info[1]: leading groups of eight columns that can hold no candidate of either op and run
+ * without scores and tests; info[2..5]: the 5' op's T(j) + 1 of columns 1..32, four bits each (0: no candidate can end
+ * there). */
+int cs_plan_walk_info(const cs_plan *plan, int mate, uint32_t info[6]);
+
 /* One engine per GPU (one per process in the multi-GPU layout; replaces
  * make_runner(inpaths, cores=threads), run.py:436,753). Uploads the op tables, owns a
  * stream, the device statistics block and `n_slots` staging slots of `max_reads` reads

@@ -7,6 +7,7 @@ import csv
 import glob
 import json
 import os
+import re
 import sys
 from pathlib import Path
 
@@ -32,9 +33,11 @@ pairs = int(sys.argv[2]) if len(sys.argv) > 2 else pairs_of_the_passes()
 
 
 def kernel_of(name: str) -> str:
-    if "trim_kernel" not in name:
+    m = re.search(r"trim_kernel<([^>]*)>", name)
+    if not m:
         return ""
-    return "resolve" if name.rstrip(">(csdev::KArgs) ").endswith("1") or ", 1>" in name else "scan"
+    args = [a.strip() for a in m.group(1).split(",")]  # CODED, WIDE, MODE, FILT (older builds: no FILT)
+    return "resolve" if len(args) > 2 and args[2] == "1" else "scan"
 
 
 per = {"scan": {}, "resolve": {}}
