@@ -144,6 +144,7 @@ class cs_reads(C.Structure):
 CS_TEXT_OK, CS_TEXT_ERR_MALFORMED, CS_TEXT_ERR_TOO_LONG, CS_TEXT_ERR_IDS_DIFFER, CS_TEXT_ERR_LINE_COUNT = 0, 1, 2, 3, 4
 CS_TEXT_ERR_INFO_MISMATCH, CS_TEXT_ERR_INFO_OVERFLOW = 5, 6
 CS_INFO_ON, CS_INFO_GZIP, CS_INFO_NO_QUAL = 1, 2, 4  # cs_text_params.info
+CS_INTERLEAVE_IN, CS_INTERLEAVE_OUT, CS_INTERLEAVE_OUT_MATE2_FIRST = 1, 2, 4  # cs_text_create_interleaved
 
 
 class cs_text_params(C.Structure):

@@ -20,7 +20,7 @@ EXPORTS = (
     "cs_stats_fetch", "cs_last_kernel_ms", "cs_last_kernel_split_ms", "cs_kernel_time_totals", "cs_alloc_pinned", "cs_alloc_pinned_huge", "cs_free_pinned", "cs_alloc_device",
     "cs_free_device", "cs_copy_to_device", "cs_copy_to_host",
     "cs_text_create", "cs_text_destroy", "cs_text_submit", "cs_text_wait", "cs_text_routes", "cs_text_fetch",
-    "cs_text_info", "cs_text_fetch_info",
+    "cs_text_info", "cs_text_fetch_info", "cs_text_create_interleaved",
 )
 
 
@@ -117,6 +117,9 @@ def load() -> C.CDLL:
     u64 = C.c_uint64
     L.cs_text_create.restype = i32
     L.cs_text_create.argtypes = [vp, C.POINTER(abi.cs_text_params), u32, u64, u32, u32, C.POINTER(vp)]
+    if hasattr(L, "cs_text_create_interleaved"):  # (an older build loaded through CUTSEQ_HIP_LIB for an A/B has none)
+        L.cs_text_create_interleaved.restype = i32
+        L.cs_text_create_interleaved.argtypes = [vp, C.POINTER(abi.cs_text_params), u32, u32, u64, u32, u32, C.POINTER(vp)]
     L.cs_text_destroy.restype = None
     L.cs_text_destroy.argtypes = [vp]
     L.cs_text_submit.restype = i32

@@ -1497,6 +1497,7 @@ struct cs_text {
   uint32_t n_routes = 3;      // 3 + cs_text_params.n_bins; 4 with cs_text_params.too_long_route
   bool route_block = false;   // more than three routes: their sizes and counts live in the slots' RouteBlock
   uint8_t info = 0;           // CS_INFO_* (cs_text_params.info)
+  uint32_t interleave = 0;    // CS_INTERLEAVE_* (cs_text_create_interleaved): one text in / one stream per route out
   uint64_t info_cap = 0;      // bytes of a batch's info table at most
   uint32_t info_chunks = 0;   // ... and deflate chunks
   hipStream_t h2d = nullptr, d2h = nullptr;
@@ -1592,15 +1593,33 @@ void cs_text_destroy(cs_text *t) { free_text(t); }
 
 int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slots, uint64_t max_text_bytes,
                    uint32_t max_records, uint32_t stride, cs_text **out) {
+  return cs_text_create_interleaved(eng, params, 0u, n_slots, max_text_bytes, max_records, stride, out);
+}
+
+int cs_text_create_interleaved(cs_engine *eng, const cs_text_params *params, uint32_t interleave, uint32_t n_slots,
+                               uint64_t max_text_bytes, uint32_t max_records, uint32_t stride, cs_text **out) {
   if (!out) return fail(CS_ERR_ARG, "out is null");
   *out = nullptr;
   if (!eng || !params) return fail(CS_ERR_ARG, "null engine or params");
+  const bool woven_in = (interleave & CS_INTERLEAVE_IN) != 0, woven_out = (interleave & CS_INTERLEAVE_OUT) != 0;
+  if (interleave & ~(uint32_t)(CS_INTERLEAVE_IN | CS_INTERLEAVE_OUT | CS_INTERLEAVE_OUT_MATE2_FIRST))
+    return fail(CS_ERR_ARG, "interleave = 0x%x: CS_INTERLEAVE_IN, CS_INTERLEAVE_OUT [| CS_INTERLEAVE_OUT_MATE2_FIRST], or 0", interleave);
+  if (interleave && !eng->paired) return fail(CS_ERR_ARG, "interleave = 0x%x on a single-end plan: there are no mates to weave", interleave);
+  if ((interleave & CS_INTERLEAVE_OUT_MATE2_FIRST) && !woven_out)
+    return fail(CS_ERR_ARG, "CS_INTERLEAVE_OUT_MATE2_FIRST orders an interleaved output: it needs CS_INTERLEAVE_OUT");
+  if (interleave && params->n_bins) return fail(CS_ERR_ARG, "interleave: the kernels of a plan with n_bins are not extended");
+  if (woven_out && (((params->fasta_routes >> 1) ^ params->fasta_routes) & 0x55u))
+    return fail(CS_ERR_ARG, "CS_INTERLEAVE_OUT: fasta_routes = 0x%02x gives the mates of one class different formats, and one "
+                "stream has one", params->fasta_routes);
   if (!n_slots || !max_records || !max_text_bytes) return fail(CS_ERR_ARG, "slots, records and text bytes must be positive");
   if (stride == 0 || stride % 4 || stride > CS_MAX_STRIDE)
     return fail(CS_ERR_ARG, "stride %u must be a multiple of 4 in [4, %d]", stride, CS_MAX_STRIDE);
-  const uint64_t out_cap = max_text_bytes + (uint64_t)max_records * (params->max_tag + 8u) + 64u;
+  // an interleaved output holds both mates' records: every record of the one text (CS_INTERLEAVE_IN) or of the two
+  const uint64_t out_cap = (woven_out && !woven_in ? 2u : 1u) * max_text_bytes +
+                           (woven_out ? 2u : 1u) * (uint64_t)max_records * (params->max_tag + 8u) + 64u;
   if (max_text_bytes >= (1ull << 30) || out_cap >= (1ull << 30))
-    return fail(CS_ERR_ARG, "a batch is limited to 1 GiB of text per mate (%llu requested)", (unsigned long long)max_text_bytes);
+    return fail(CS_ERR_ARG, woven_out ? "a batch is limited to 1 GiB of interleaved output (%llu bytes of text per input requested)"
+                                      : "a batch is limited to 1 GiB of text per mate (%llu requested)", (unsigned long long)max_text_bytes);
   cs_text *t = new (std::nothrow) cs_text();
   if (!t) return fail(CS_ERR_NOMEM, "out of memory");
   t->eng = eng;
@@ -1609,6 +1628,7 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
   t->max_records = max_records;
   t->stride = stride;
   t->max_tag = params->max_tag;
+  t->interleave = interleave;
   memset(&t->tp, 0, sizeof t->tp);
   t->tp.paired = eng->paired ? 1 : 0;
   t->tp.has_umi = params->has_umi ? 1 : 0;
@@ -1742,7 +1762,9 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
     auto carve = [&](uint8_t *base) {
       Carver c{base};
       for (int m = 0; m < mates; ++m) {
-        c.take(s.d_nl[m], (size_t)max_records * 4 + 8);
+        // (an interleaved text: one index over both mates' lines, and no text or index of mate 2's own)
+        if (!woven_in) c.take(s.d_nl[m], (size_t)max_records * 4 + 8);
+        else if (m == 0) c.take(s.d_nl[m], (size_t)max_records * 8 + 8);
         c.take(s.d_rec[m], max_records);
         c.take(s.d_idr[m], max_records);
       }
@@ -1750,17 +1772,20 @@ int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slot
       for (int m = 0; m < mates; ++m) c.take(s.d_long_of[m], max_records);
       ones_bytes = c.at - zero_bytes;
       for (int m = 0; m < mates; ++m) {
-        c.take(s.d_text[m], max_text_bytes + 64);
+        if (!woven_in || m == 0) c.take(s.d_text[m], max_text_bytes + 64);
         c.take(s.d_seq[m], rows);
         c.take(s.d_qual[m], rows);
         c.take(s.d_len[m], max_records);
         c.take(s.d_res[m], max_records);
         c.take(s.d_dst[m], max_records);
-        c.take(s.d_out[m], out_cap);
+        // (an interleaved output: mate 1's buffer and deflate staging hold both mates, mate 2 has none)
+        if (!woven_out || m == 0) c.take(s.d_out[m], out_cap);
         c.take(s.d_lrec[m], max_records);
         c.take(s.d_lres[m], max_records);
-        if (t->compress) c.take(s.gz[m], t->max_chunks);
+        if (t->compress && (!woven_out || m == 0)) c.take(s.gz[m], t->max_chunks);
       }
+      if (woven_in) s.d_text[1] = s.d_text[0];
+      if (woven_out) s.d_out[1] = s.d_out[0];
       if (t->needs_cap2) c.take(s.d_cap2, max_records);
       c.take(s.d_blk, (size_t)2 * (t->seg_blocks + 1) + (size_t)2 * t->n_routes * (t->fmt_blocks + 1));
       c.take(s.d_totals, 2 + 2 * (size_t)t->n_routes);
@@ -1809,7 +1834,9 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
   if (!t || !text1) return fail(CS_ERR_ARG, "null text engine or text");
   if (slot >= t->slots.size()) return fail(CS_ERR_ARG, "slot %u out of range", slot);
   cs_engine *eng = t->eng;
-  if ((text2 != nullptr) != eng->paired) return fail(CS_ERR_ARG, "plan is %s-end", eng->paired ? "paired" : "single");
+  const bool woven_in = (t->interleave & CS_INTERLEAVE_IN) != 0, woven_out = (t->interleave & CS_INTERLEAVE_OUT) != 0;
+  if (woven_in && (text2 || bytes2)) return fail(CS_ERR_ARG, "CS_INTERLEAVE_IN: both mates come in text1 (text2 must be NULL, bytes2 0)");
+  if (!woven_in && (text2 != nullptr) != eng->paired) return fail(CS_ERR_ARG, "plan is %s-end", eng->paired ? "paired" : "single");
   if (bytes1 > t->max_text || bytes2 > t->max_text || n_records > t->max_records)
     return fail(CS_ERR_ARG, "batch of %u records, %llu / %llu bytes exceeds the slot (%u records, %llu bytes)", n_records,
                 (unsigned long long)bytes1, (unsigned long long)bytes2, t->max_records, (unsigned long long)t->max_text);
@@ -1817,14 +1844,15 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
   if (s.busy) return fail(CS_ERR_STATE, "slot %u still in flight: cs_text_wait + cs_text_fetch first", slot);
   HIP_TRY(hipSetDevice(eng->device));
   const int mates = eng->paired ? 2 : 1;
+  const int texts = woven_in ? 1 : mates;  // texts uploaded and indexed
   const void *src[2] = {text1, text2};
   const uint64_t bytes[2] = {bytes1, bytes2};
-  for (int m = 0; m < mates; ++m)
+  for (int m = 0; m < texts; ++m)
     if (n_records && !bytes[m]) return fail(CS_ERR_ARG, "mate %d: %u records in 0 bytes of text", m + 1, n_records);
   s.n = n_records;
   s.waited = false;
   hipStream_t st = eng->stream, rs = eng->resolve_stream;
-  for (int m = 0; m < mates; ++m)
+  for (int m = 0; m < texts; ++m)
     if (bytes[m]) HIP_TRY(hipMemcpyAsync(s.d_text[m], src[m], bytes[m], hipMemcpyHostToDevice, t->h2d));
   HIP_TRY(hipEventRecord(s.uploaded, t->h2d));
   HIP_TRY(hipStreamWaitEvent(st, s.uploaded, 0));
@@ -1832,17 +1860,23 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
   uint32_t *blk_nl[2] = {s.d_blk, s.d_blk + t->seg_blocks + 1};
   uint32_t *blk_fmt = s.d_blk + 2 * (t->seg_blocks + 1);
   if (n_records) {
-    for (int m = 0; m < mates; ++m) {
+    for (int m = 0; m < texts; ++m) {
       const uint32_t nb = (uint32_t)((bytes[m] + cstext::kSeg - 1) / cstext::kSeg);
       hipLaunchKernelGGL(cstext::text_count_nl, dim3(nb), dim3(cstext::kSegThreads), 0, st, s.d_text[m], (uint32_t)bytes[m],
                          blk_nl[m]);
       hipLaunchKernelGGL(cstext::text_scan_blocks, dim3(1), dim3(1024), 0, st, blk_nl[m], nb, 1u, s.d_totals + m);
       hipLaunchKernelGGL(cstext::text_write_nl, dim3(nb), dim3(cstext::kSegThreads), 0, st, s.d_text[m], (uint32_t)bytes[m],
-                         blk_nl[m], s.d_totals + m, 4u * n_records, s.d_nl[m], s.d_meta, m);
-      hipLaunchKernelGGL(cstext::text_parse_records, dim3((n_records + 255u) / 256u), dim3(256), 0, st, s.d_text[m],
-                         s.d_nl[m], n_records, t->stride, t->tp, m, s.d_rec[m], s.d_idr[m], s.d_len[m], s.d_lrec[m],
-                         s.d_long_of[m], s.d_meta);
+                         blk_nl[m], s.d_totals + m, (woven_in ? 8u : 4u) * n_records, s.d_nl[m], s.d_meta, m);
+      if (!woven_in)
+        hipLaunchKernelGGL(cstext::text_parse_records, dim3((n_records + 255u) / 256u), dim3(256), 0, st, s.d_text[m],
+                           s.d_nl[m], n_records, t->stride, t->tp, m, s.d_rec[m], s.d_idr[m], s.d_len[m], s.d_lrec[m],
+                           s.d_long_of[m], s.d_meta);
     }
+    if (woven_in)  // the one index, read once per mate: record r of mate m at lines 4 * (2r + m) ..
+      for (int m = 0; m < mates; ++m)
+        hipLaunchKernelGGL(cstext::text_parse_records_woven, dim3((n_records + 255u) / 256u), dim3(256), 0, st, s.d_text[0],
+                           s.d_nl[0], n_records, t->stride, t->tp, m, s.d_rec[m], s.d_idr[m], s.d_len[m], s.d_lrec[m],
+                           s.d_long_of[m], s.d_meta);
     if (mates == 2)
       hipLaunchKernelGGL(cstext::text_check_pairs, dim3((n_records + 255u) / 256u), dim3(256), 0, st, s.d_text[0], s.d_rec[0],
                          s.d_text[1], s.d_rec[1], n_records, s.d_meta);
@@ -1946,6 +1980,20 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
       hipLaunchKernelGGL(cstext::format_sizes_bins, dim3(fb), dim3(256), 0, rs, fa, t->tp);
       hipLaunchKernelGGL(cstext::text_scan_blocks, dim3(cols < 64u ? cols : 64u), dim3(1024), 0, rs, blk_fmt, fb, cols, fa.totals);
       hipLaunchKernelGGL(cstext::format_offsets_bins, dim3(fb), dim3(256), 0, rs, fa, t->tp);
+    } else if (woven_out) {  // one stream per route: a column each, both mates' records in it
+      const uint32_t lead = (t->interleave & CS_INTERLEAVE_OUT_MATE2_FIRST) ? 1u : 0u;
+      if (t->tp.too_long_route) {
+        fa.route_bytes = &s.d_routes->bytes[0][0];
+        fa.route_count = s.d_routes->count;
+        HIP_TRY(hipMemsetAsync(s.d_routes, 0, sizeof(RouteBlock), rs));
+        hipLaunchKernelGGL(cstext::format_sizes_woven<4>, dim3(fb), dim3(256), 0, rs, fa, t->tp);
+        hipLaunchKernelGGL(cstext::text_scan_blocks, dim3(1), dim3(1024), 0, rs, blk_fmt, fb, 4u, fa.totals);
+        hipLaunchKernelGGL(cstext::format_offsets_woven<4>, dim3(fb), dim3(256), 0, rs, fa, t->tp, lead);
+      } else {
+        hipLaunchKernelGGL(cstext::format_sizes_woven<3>, dim3(fb), dim3(256), 0, rs, fa, t->tp);
+        hipLaunchKernelGGL(cstext::text_scan_blocks, dim3(1), dim3(1024), 0, rs, blk_fmt, fb, 3u, fa.totals);
+        hipLaunchKernelGGL(cstext::format_offsets_woven<3>, dim3(fb), dim3(256), 0, rs, fa, t->tp, lead);
+      }
     } else if (t->tp.too_long_route) {  // four routes: the plain block scans over eight columns
       fa.route_bytes = &s.d_routes->bytes[0][0];
       fa.route_count = s.d_routes->count;
@@ -1979,7 +2027,7 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
       HIP_TRY(hipGetLastError());
     }
     if (t->compress) {
-      for (int m = 0; m < mates; ++m) {
+      for (int m = 0; m < (woven_out ? 1 : mates); ++m) {  // (interleaved: mate 1's streams hold both mates)
         uint32_t fasta_classes = 0;
         for (uint32_t c = 0; c < 4u; ++c) fasta_classes |= ((t->tp.fasta_routes >> (2u * c + m)) & 1u) << c;
         launch_deflate(rs, s.gz[m], s.d_out[m], t->route_block ? &s.d_routes->bytes[0][m] : &s.d_meta->route_bytes[0][m],

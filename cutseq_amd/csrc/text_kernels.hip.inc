@@ -20,6 +20,10 @@
 //                         sums, exclusive scan, block-local scans -- output order = input order.  <3>: the three routes;
 //                         <4>: cs_text_params.too_long_route, the pairs TooLong catches are a fourth route, not discarded
 //   format_copy           32 lanes per output record: '@' id ['_' UMI] '\n' seq[start:stop] "\n+\n" qual[start:stop] '\n'
+//   text_parse_records_woven / format_sizes_woven / format_offsets_woven   cutadapt's --interleaved (cs_text_create_interleaved):
+//                         both mates' records in ONE text, alternating, and / or ONE output stream per route, the
+//                         record of one mate followed by its partner's.  Kernels of their own: a cs_text without the
+//                         bits launches what it launched before
 //
 // Everything a kernel rejects (malformed record, read longer than the row stride, mate ids that differ) lands in
 // TextMeta.err as the smallest (record index, code) key; the host raises what the reference's reader would.
@@ -298,6 +302,82 @@ __global__ void __launch_bounds__(256) text_parse_records(const uint8_t *text, c
   long_of[r] = long_slot;
 }
 
+// The same for an interleaved text (cs_text_create_interleaved, CS_INTERLEAVE_IN): the one text holds both mates'
+// records, alternating, under one newline index -- record r of mate `mate` stands at lines 4 * (2r + mate) .. + 3.  One
+// launch per mate, like text_parse_records; everything else is that kernel's, line for line.  A kernel of its own and
+// not a shared body: text_parse_records has to stay the code it was (profiles/interleaved_ab.log), and it does not when
+// its body moves into a function the two are inlined from (two more SGPRs, another block order).
+__global__ void __launch_bounds__(256) text_parse_records_woven(const uint8_t *text, const uint32_t *nl, uint32_t n,
+                                                                uint32_t stride, TextParams tp, int mate, Rec *rec,
+                                                                uint32_t *idr, uint16_t *len, cslong::LongRec *lrec,
+                                                                uint32_t *long_of, TextMeta *meta) {
+  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+  if (r >= n) return;
+  // (no index to go by: the one text's bit, mate 1's, for both launches)
+  if (meta->no_index & 1u) {
+    const Rec none = {0, 0, 0, 0, 0};
+    rec[r] = none;
+    idr[r] = 0;
+    len[r] = 0;
+    long_of[r] = kNotLong;
+    return;
+  }
+  uint32_t start[4], end[4];
+#pragma unroll
+  for (int l = 0; l < 4; ++l) {
+    const uint32_t line = 4u * (2u * r + (uint32_t)mate) + (uint32_t)l;
+    start[l] = line == 0 ? 0u : nl[line - 1] + 1u;
+    end[l] = nl[line];
+    if (end[l] > start[l] && text[end[l] - 1] == '\r') --end[l];
+  }
+  Rec out = {0, 0, 0, 0, 0};
+  bool bad = end[0] <= start[0] || text[start[0]] != '@' || end[2] <= start[2] || text[start[2]] != '+';
+  const uint32_t sl = end[1] - start[1], ql = end[3] - start[3];
+  bad = bad || sl != ql || end[0] - start[0] - 1u > 65535u;
+  uint32_t long_slot = kNotLong;
+  if (bad) {
+    report(meta, r, ERR_MALFORMED);
+  } else {
+    atomicMax(&meta->max_len, sl);
+    if (sl > CS_MAX_READ) report(meta, r, ERR_TOO_LONG);
+    if (sl > stride || sl >= (uint32_t)CS_LEN_SKIP) {
+      long_slot = atomicAdd(&meta->n_long[mate], 1u);  // (at most n of them: the list has n entries)
+      cslong::LongRec lr;
+      lr.rec = r;
+      lr.seq_off = start[1];
+      lr.qual_off = start[3];
+      lr.len = sl;
+      lrec[long_slot] = lr;
+    }
+    out.seq_off = start[1];
+    out.qual_off = start[3];
+    out.hdr_off = start[0] + 1u;
+    uint32_t hl = end[0] - start[0] - 1u;
+    const uint8_t *name = text + out.hdr_off;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const uint32_t k = tp.suffix_len[mate][s];
+      if (k && hl >= k) {
+        bool same = true;
+        for (uint32_t i = 0; i < k; ++i) same = same && name[hl - k + i] == tp.suffix[mate][s][i];
+        if (same) hl -= k;
+      }
+    }
+    out.hdr_len = (uint16_t)hl;
+    out.len = long_slot == kNotLong ? (uint16_t)sl : (uint16_t)0;  // (a long read leaves an empty row)
+    uint32_t a = 0;
+    while (a < hl && is_space(name[a])) ++a;
+    uint32_t b = a;
+    while (b < hl && !is_space(name[b])) ++b;
+    uint32_t c = b;
+    while (c < hl && is_space(name[c])) ++c;
+    idr[r] = (b > a && c < hl) ? (a | ((b - a) << 16)) : (hl << 16);
+  }
+  rec[r] = out;
+  len[r] = long_slot == kNotLong ? out.len : (uint16_t)CS_LEN_SKIP;
+  long_of[r] = long_slot;
+}
+
 // dnaio.record_names_match: ids up to the first space / tab, one trailing 1 / 2 / 3 ignored in both
 __global__ void __launch_bounds__(256) text_check_pairs(const uint8_t *text1, const Rec *rec1, const uint8_t *text2,
                                                         const Rec *rec2, uint32_t n, TextMeta *meta) {
@@ -562,6 +642,89 @@ __global__ void __launch_bounds__(256) format_offsets(FormatArgs a, TextParams t
         if (kRoutes == 4u)
           for (uint32_t q = 0; q < kRoutes; ++q) a.route_bytes[q * 2u + m] = a.totals[q * 2u + m];
       }
+    }
+  }
+}
+
+// ---- the same two steps for interleaved output (cs_text_create_interleaved, CS_INTERLEAVE_OUT): a route's two mate
+// streams are ONE stream in mate 1's buffer, record of mate 1, record of mate 2, pair after pair.  One column per route
+// (blk / totals hold kRoutes of them), a pair contributes len[0] + len[1]; the first mate's record stands at the pair's
+// offset and the second's behind it.  dst[0] and dst[1] are offsets into the one buffer (FormatArgs.out[1] == out[0]),
+// so format_copy runs as it is.  `second_first` (CS_INTERLEAVE_OUT_MATE2_FIRST): mate 2's record leads.
+template <uint32_t kRoutes>
+__global__ void __launch_bounds__(256) format_sizes_woven(FormatArgs a, TextParams tp) {
+  __shared__ uint32_t sh[8];
+  if (a.meta->err != ~0ull) return;
+  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+  RecordShape s = {kRoutes, {0u, 0u}, 0u};
+  if (r < a.n) s = record_shape<kRoutes == 4u>(a, tp, r);
+#pragma unroll
+  for (uint32_t c = 0; c < kRoutes; ++c) {
+    uint32_t total;
+    (void)block_scan_256(s.route == c ? s.len[0] + s.len[1] : 0u, total, sh);
+    if (threadIdx.x == 0) a.blk[blockIdx.x * kRoutes + c] = total;
+  }
+}
+
+template <uint32_t kRoutes>
+__global__ void __launch_bounds__(256) format_offsets_woven(FormatArgs a, TextParams tp, uint32_t second_first) {
+  __shared__ uint32_t sh[8];
+  if (a.meta->err != ~0ull) return;
+  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+  RecordShape s = {kRoutes, {0u, 0u}, 0u};
+  if (r < a.n) s = record_shape<kRoutes == 4u>(a, tp, r);
+  // where a route's stream starts inside the buffer: behind the routes in front of it
+  unsigned long long base[kRoutes];
+  base[0] = 0;
+  for (uint32_t q = 1; q < kRoutes; ++q) base[q] = base[q - 1u] + a.totals[q - 1u];
+  uint32_t mine = 0;
+#pragma unroll
+  for (uint32_t c = 0; c < kRoutes; ++c) {
+    uint32_t total;
+    const uint32_t local = block_scan_256(s.route == c ? s.len[0] + s.len[1] : 0u, total, sh);
+    if (s.route == c) mine = (uint32_t)base[c] + a.blk[blockIdx.x * kRoutes + c] + local;
+  }
+  uint32_t counts[kRoutes];
+#pragma unroll
+  for (uint32_t q = 0; q < kRoutes; ++q) {
+    uint32_t total;
+    (void)block_scan_256(s.route == q ? 1u : 0u, total, sh);
+    counts[q] = total;
+  }
+  uint32_t discarded = 0;
+  if (tp.filters) (void)block_scan_256(r < a.n ? s.why : 0u, discarded, sh);
+  uint32_t kept_bp[2] = {0, 0};
+#pragma unroll
+  for (uint32_t m = 0; m < 2; ++m) {
+    uint32_t bp = 0;
+    if (r < a.n && s.route == 0u) {
+      const ReadView v = read_view(a, m, r);
+      bp = v.stop - v.start;
+    }
+    (void)block_scan_256(bp, kept_bp[m], sh);
+  }
+  if (r < a.n) {
+    const bool gone = s.route == kRouteDiscard;
+    const uint32_t lead = second_first ? 1u : 0u;
+    a.dst[lead][r] = gone ? kDiscarded : mine | (s.route << 30);
+    a.dst[lead ^ 1u][r] = gone ? kDiscarded : (mine + s.len[lead]) | (s.route << 30);
+  }
+  if (threadIdx.x == 0) {
+    for (uint32_t q = 0; q < 3; ++q)
+      if (counts[q]) atomicAdd(&a.meta->route_count[q], counts[q]);
+    if (kRoutes == 4u)
+      for (uint32_t q = 0; q < kRoutes; ++q)
+        if (counts[q]) atomicAdd(&a.route_count[q], counts[q]);
+    add_discards(a.meta, discarded);
+    for (uint32_t m = 0; m < 2; ++m)
+      if (kept_bp[m]) atomicAdd(&a.meta->written_bp[m], (unsigned long long)kept_bp[m]);
+    if (blockIdx.x == 0) {  // (mate 2's sizes stay the zeros text_init_meta and the route block's memset wrote)
+      unsigned long long all = 0;
+      for (uint32_t q = 0; q < kRoutes; ++q) all += a.totals[q];
+      a.meta->out_bytes[0] = all;
+      for (int q = 0; q < 3; ++q) a.meta->route_bytes[q][0] = a.totals[q];
+      if (kRoutes == 4u)
+        for (uint32_t q = 0; q < kRoutes; ++q) a.route_bytes[q * 2u] = a.totals[q];
     }
   }
 }

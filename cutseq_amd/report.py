@@ -169,7 +169,7 @@ def _host_threads() -> int:
 
 
 def json_report(tp: TrimPlan, totals: dict, barcode, input1, input2, output1, output2, short1, short2,
-                untrimmed1, untrimmed2, info_file=None, too_long_files=None) -> dict:
+                untrimmed1, untrimmed2, info_file=None, too_long_files=None, interleaved=False) -> dict:
     """Same header block as the reference's ``json_report`` (run.py:262-283) followed by the
     ``Statistics.as_json()`` sections; engine-specific counters live under ``"engine"``."""
     paired = tp.paired
@@ -201,7 +201,9 @@ def json_report(tp: TrimPlan, totals: dict, barcode, input1, input2, output1, ou
         "tag": "Cutadapt report",
         # the report layout is cutadapt 5's; the numbers come from this engine (local version label says so)
         "cutadapt_version": f"5.0+cutseq.amd.{__version__}",
-        "input": {"path1": input1, "path2": input2, "paired": True if input2 else False},
+        # ("interleaved": cutadapt's key -- path1 holds both mates, path2 is null and the run is paired all the same)
+        "input": {"path1": input1, "path2": input2, "paired": True if input2 or interleaved else False,
+                  "interleaved": bool(interleaved)},
         "output": {"output1": output1, "output2": output2, "short1": short1, "short2": short2,
                    "untrimmed1": untrimmed1, "untrimmed2": untrimmed2},
         "barcode": barcode.to_dict(),

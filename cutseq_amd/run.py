@@ -120,6 +120,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Extension (cutadapt's option; a TODO of the reference): write a tab-separated table of the "
                         "adapter matches of read 1 to FILE, one row per match, in input order; reads without a match "
                         "get one row with -1. A .gz / .bz2 / .xz / .zst name compresses the table.")
+    p.add_argument("--interleaved", action="store_true",
+                   help="Extension (cutadapt's option): paired reads in ONE file, mate 1 and mate 2 alternating. With one "
+                        "input file, that file holds interleaved pairs (the run is a paired run); the outputs are "
+                        "interleaved too unless -o names two files. With two input files, the outputs are interleaved "
+                        "(-o takes one name). An interleaved run takes one name each for -o, -s, -u and "
+                        "--too-long-output; '-' reads standard input / writes standard output. Not with "
+                        "--demux-barcodes.")
     p.add_argument("--rank-spec", type=str, help=argparse.SUPPRESS)  # a child of --ranks: its share of the run
     p.add_argument("--demux-barcodes", type=str, metavar="FILE",
                    help="Extension: demultiplex on the 5' inline barcode. FILE lists 'name<TAB>sequence' per line (all as "
@@ -164,14 +171,54 @@ def _fail(message: str):
     sys.exit(1)
 
 
-def output_paths(given, inputs, prefix, word):
-    """File names of one output class, one per input file."""
+def output_paths(given, inputs, prefix, word, interleaved=None):
+    """File names of one output class, one per input file.  ``interleaved`` (an ``--interleaved`` run): "out" -- the
+    class is ONE file of interleaved pairs, ``<stem>_<word>.fastq.gz`` --, or "split" -- one interleaved input file,
+    two output files; the stem comes from ``-O`` or from the first input file."""
+    if interleaved:
+        want = 1 if interleaved == "out" else 2
+        if given:
+            if len(given) != want:
+                _fail(f"Number of {word} output files ({len(given)}) must match the number this --interleaved run "
+                      f"writes per class: {want} ({'interleaved' if want == 1 else 'one per mate'}).")
+            return list(given)
+        stem = prefix if prefix is not None else remove_fq_suffix(inputs[0])
+        return [f"{stem}_{word}.fastq.gz"] if want == 1 else [f"{stem}_{word}_R{mate}.fastq.gz" for mate in (1, 2)]
     if given:
         if len(given) != len(inputs):
             _fail(f"Number of {word} output files ({len(given)}) must match number of input files ({len(inputs)}).")
         return list(given)
     stems = [prefix] * len(inputs) if prefix is not None else [remove_fq_suffix(name) for name in inputs]
     return [f"{stem}_{word}_R{mate}.fastq.gz" for mate, stem in enumerate(stems, 1)]
+
+
+def resolve_interleaved(args, inputs):
+    """``--interleaved`` -> args.interleaved_in / args.interleaved_out / args.paired, and the form of every output class
+    (None: not such a run, "out": one interleaved file, "split": interleaved input, two files).  One input file: it
+    holds the pairs, and the outputs are interleaved unless -o names two files.  Two input files: the outputs are
+    interleaved, and -o takes one name."""
+    args.interleaved_in = args.interleaved_out = False
+    args.paired = len(inputs) == 2
+    if not getattr(args, "interleaved", False) or not inputs:
+        return None
+    if args.demux_barcodes:
+        _fail("--interleaved cannot be combined with --demux-barcodes: the barcodes' kernels write one stream per mate.")
+    if not switches.enabled("TEXT_PATH"):
+        _fail("--interleaved needs the text path: the pairs are woven on the GPU (CUTSEQ_TEXT_PATH=0 is set).")
+    given = len(args.output_file) if args.output_file else 0
+    if len(inputs) == 1:
+        args.interleaved_in = True
+        args.interleaved_out = given != 2
+        if getattr(args, "ranks", 1) > 1 and not getattr(args, "rank_spec", None):
+            _fail("--interleaved input cannot be split between --ranks: a share that begins at a record boundary "
+                  "cannot know which mate it begins with (two input files with --interleaved output can).")
+    else:
+        if given == 2:
+            _fail("--interleaved with two input files and two -o files would have nothing to do: give -o one name "
+                  "(interleaved output) or drop --interleaved.")
+        args.interleaved_out = True
+    args.paired = True
+    return "out" if args.interleaved_out else "split"
 
 
 def resolve_scheme(args) -> str:
@@ -211,7 +258,8 @@ def resolve_args(args):
     if nextseq is not None and not abi.CS_Q_SUM_LOW <= nextseq + 33 <= abi.CS_Q_SUM_HIGH:
         # (unlike -q's, this cutoff is not clamped: a G's term is +1 whatever it is -- include/cutseq_hip.h, CS_OP_NEXTSEQ)
         _fail(f"--nextseq-trim: the cutoff must lie in [{abi.CS_Q_SUM_LOW - 33}, {abi.CS_Q_SUM_HIGH - 33}] (got {nextseq}).")
-    if getattr(args, "min_quality_r2", None) is not None and len(inputs) == 1:
+    form = resolve_interleaved(args, inputs)
+    if getattr(args, "min_quality_r2", None) is not None and len(inputs) == 1 and not args.interleaved_in:
         _fail("-Q sets the quality cutoff of the second read: it needs two input files.")
     if getattr(args, "info_file", None):
         if args.demux_barcodes:
@@ -227,7 +275,7 @@ def resolve_args(args):
             _fail("--too-long-output cannot be combined with --demux-barcodes: the output class it would take on the "
                   "GPU is the barcodes' there.")
         if inputs:  # (no default name from -O: the given names or none)
-            args.too_long_file = output_paths(too_long_file, inputs, None, "too-long")
+            args.too_long_file = output_paths(too_long_file, inputs, None, "too-long", form)
     if not inputs:
         # the reference dies with an IndexError here (run.py:1079-1083); same exit class, clearer message
         _fail("Input file is required.")
@@ -244,9 +292,9 @@ def resolve_args(args):
         args.ensure_inline_barcode and _SCHEME_HAS_INLINE.match(args.adapter_scheme) is not None)
     for attr, word in OUTPUT_CLASSES:
         if attr == "untrimmed_file" and not wants_untrimmed:
-            args.untrimmed_file = [None] * len(inputs)
+            args.untrimmed_file = [None] * ({"out": 1, "split": 2}.get(form) or len(inputs))
         else:
-            setattr(args, attr, output_paths(getattr(args, attr), inputs, args.output_prefix, word))
+            setattr(args, attr, output_paths(getattr(args, attr), inputs, args.output_prefix, word, form))
     if args.demux is not None:  # one pair of trimmed files per barcode instead of the common one
         args.demux_files = [output_paths(None, inputs, args.output_prefix, f"{name}_trimmed") for name in args.demux[0]]
     return args
@@ -282,11 +330,11 @@ def settings_from_args(args) -> CutadaptConfig:
 
 
 def compile_plan(args, barcode: BarcodeConfig, settings: CutadaptConfig) -> TrimPlan:
-    if len(args.input_file) == 1:
+    if not getattr(args, "paired", len(args.input_file) == 2):  # (--interleaved: one input file can hold pairs)
         return compile_single(barcode, settings, untrimmed_requested=args.untrimmed_file[0] is not None)
     return compile_paired(
         barcode, settings,
-        untrimmed_requested=args.untrimmed_file[0] is not None and args.untrimmed_file[1] is not None)
+        untrimmed_requested=all(name is not None for name in args.untrimmed_file))
 
 
 def dry_run_steps(tp: TrimPlan) -> List[str]:
@@ -551,13 +599,14 @@ def run_cutseq(args, argv=None):
         totals = run_pipeline(args, tp)
         _phase("pipeline done")
     if args.json_file:
-        paired = tp.paired
+        # (the mate-2 keys are null where one file holds both mates: interleaved input, interleaved output)
+        second = lambda names: names[1] if tp.paired and len(names) > 1 else None  # noqa: E731
         rep = report.json_report(
-            tp, totals, barcode, args.input_file[0], args.input_file[1] if paired else None,
-            args.output_file[0], args.output_file[1] if paired else None,
-            args.short_file[0], args.short_file[1] if paired else None,
-            args.untrimmed_file[0], args.untrimmed_file[1] if paired else None,
-            info_file=getattr(args, "info_file", None), too_long_files=getattr(args, "too_long_file", None))
+            tp, totals, barcode, args.input_file[0], second(args.input_file),
+            args.output_file[0], second(args.output_file), args.short_file[0], second(args.short_file),
+            args.untrimmed_file[0], second(args.untrimmed_file),
+            info_file=getattr(args, "info_file", None), too_long_files=getattr(args, "too_long_file", None),
+            interleaved=getattr(args, "interleaved_in", False))
         report.write_json(args.json_file, rep)
     print(report.minimal_report(tp, totals), file=sys.stderr)
     return totals
@@ -580,6 +629,8 @@ def _block_records(args, n_devices: int) -> int:
     if args.input_file[0].endswith(".gz"):
         size *= 4  # (a guess at the text behind it)
     records = size // 300  # (a short-read record is ~330 bytes)
+    if getattr(args, "interleaved_in", False):  # (a block counts pairs, and this file holds both mates)
+        records //= 2
     want = records // (24 * max(n_devices, 1))
     block = textio.CHUNK_READS
     while block > 16384 and block > want:

@@ -90,14 +90,20 @@ class TextReader(threading.Thread):
     then ``None``.  Exceptions travel through the queue."""
 
     def __init__(self, path: str, chunk_reads: int, start: int = 0, skip_lines: int = 0, max_records: Optional[int] = None,
-                 stop: Optional[int] = None):
-        """``start`` / ``skip_lines`` / ``max_records`` / ``stop``: one rank's share of the file in the multi-process form
+                 stop: Optional[int] = None, interleaved: bool = False):
+        """``interleaved``: the file holds pairs, mate 1 and mate 2 alternating (``--interleaved``).  ``chunk_reads`` still
+        counts records and must be even, so every block holds whole pairs; a block's ``n`` and ``first_record`` count
+        pairs.  A file that ends on an odd record is refused (:meth:`pair_count`).
+        ``start`` / ``skip_lines`` / ``max_records`` / ``stop``: one rank's share of the file in the multi-process form
         (``ranks.py``): begin at byte ``start`` (plain text) or at the gzip member that starts there, drop
         ``skip_lines`` lines, stop behind ``max_records`` records (None = to the end of the file) or in front of the
         gzip member that starts at compressed offset ``stop``."""
         super().__init__(daemon=True, name=f"cutseq-read-{os.path.basename(path)}")
         self.path, self.chunk_reads = path, chunk_reads
         self.start_at, self.skip_lines, self.max_records, self.stop_at = start, skip_lines, max_records, stop
+        self.interleaved = interleaved
+        if interleaved and (chunk_reads % 2 or start or skip_lines or max_records is not None or stop is not None):
+            raise ValueError(f"{path}: an interleaved input is read whole, in blocks of an even number of records")
         self.blocks: "queue.Queue" = queue.Queue(maxsize=3)
         self._halt = False
         # What the file holds decides how it is read (dnaio / xopen go by content too, cutseq/run.py:434-441, 751-758):
@@ -144,6 +150,21 @@ class TextReader(threading.Thread):
             except queue.Empty:
                 pass
             self.join(timeout=0.05)
+
+    @staticmethod
+    def pair_count(records: int, path: str) -> int:
+        """Pairs in a block of ``records`` records of an interleaved input; only the last block can be odd."""
+        if records % 2:
+            raise fastq.FastqFormatError(
+                f"{path}: the interleaved input is incomplete: it ends after an odd number of records, the last record "
+                "has no partner.")
+        return records // 2
+
+    def _block(self, buf: np.ndarray, nbytes: int, records: int, done: int) -> TextBlock:
+        """The block of ``records`` records behind the ``done`` records handed out so far."""
+        if self.interleaved:
+            return TextBlock(buf, nbytes, self.pair_count(records, self.path), done // 2)
+        return TextBlock(buf, nbytes, records, done)
 
     # -- sources: append text behind buf[:fill] -> (buf, fill, [(offset, nbytes, newlines)], eof) ------------------
     @staticmethod
@@ -311,7 +332,7 @@ class TextReader(threading.Thread):
                     nxt = fastq.PINNED.take(max(buf.size, int(self.chunk_reads * est * 1.25) + 2 * _BLOCK))
                     carry = fill - cut
                     C.memmove(nxt.ctypes.data, buf.ctypes.data + cut, carry)
-                    block = TextBlock(buf, cut, need // 4, done)
+                    block = self._block(buf, cut, need // 4, done)
                     done += need // 4
                     if left is not None:
                         left -= need // 4
@@ -357,7 +378,7 @@ class TextReader(threading.Thread):
                     tail_lines = last + 2
                 else:
                     raise fastq.FastqFormatError(f"{self.path}: truncated FASTQ record at end of file")
-                block = TextBlock(buf, end, tail_lines // 4, done)
+                block = self._block(buf, end, tail_lines // 4, done)
                 buf = None
                 if self._put(block):
                     self._put(None)
@@ -599,8 +620,11 @@ class TextWorker(fanout.Worker):
     _tick = staticmethod(_tick)
 
     def __init__(self, tp, device: int, chunk_reads: int, compress: bool = False, bins: int = 0,
-                 fasta_routes: int = 0, info: int = 0, too_long_route: bool = False):
+                 fasta_routes: int = 0, info: int = 0, too_long_route: bool = False, interleave_in: bool = False,
+                 interleave_out: bool = False, mate2_first: bool = False):
         super().__init__(f"cutseq-gpu{device}")
+        # --interleaved: an item is (block of both mates, None); the routes come back as one stream each
+        self.interleave_in, self.interleave_out, self.mate2_first = interleave_in, interleave_out, mate2_first
         self.too_long_route = too_long_route  # --too-long-output: the pairs -M catches are a fourth stream (route 3)
         self.info = info  # abi.CS_INFO_* bits: the batches also yield the --info-file table
         self.tp, self.device, self.chunk_reads, self.compress = tp, device, chunk_reads, compress
@@ -630,7 +654,8 @@ class TextWorker(fanout.Worker):
         self.text = textpath.TextEngine(self.engine, slots=self.SLOTS, max_text_bytes=self.capacity,
                                         max_records=self.chunk_reads, stride=self.stride, compress=self.compress,
                                         bins=self.bins, fasta_routes=self.fasta_routes, info=self.info,
-                                        too_long_route=self.too_long_route)
+                                        too_long_route=self.too_long_route, interleave_in=self.interleave_in,
+                                        interleave_out=self.interleave_out, mate2_first=self.mate2_first)
 
     def submit(self, slot: int, item):
         b1, b2 = item
@@ -657,14 +682,15 @@ class TextWorker(fanout.Worker):
         if self.bins or self.too_long_route:
             sizes, _, counts = self.text.routes(slot)
         discards = self.text.discards(slot) if self.tp.has_filters else None
-        out = [fastq.PINNED.take(max(int(res.out_bytes[m]), 1)) for m in range(2 if b2 is not None else 1)]
+        mates_out = 1 if self.interleave_out else (2 if b2 is not None or self.interleave_in else 1)
+        out = [fastq.PINNED.take(max(int(res.out_bytes[m]), 1)) for m in range(mates_out)]
         info_buf, info_bytes = None, 0
         if self.info:
             info_bytes = self.text.info(slot)[0]
             info_buf = fastq.PINNED.take(max(info_bytes, 1))
             self.text.fetch_info(slot, info_buf)
         t0 = _tick("take", t0)
-        self.text.fetch(slot, out[0], out[1] if b2 is not None else None)
+        self.text.fetch(slot, out[0], out[1] if mates_out == 2 else None)
         _tick("fetch", t0)
         b1.release()
         if b2 is not None:
@@ -757,8 +783,11 @@ def output_name_groups(args, paired: bool, swap_outputs: bool, n_bins: int) -> L
     one entry per mate each (None: no such file).  Paired --auto-rc on a '-' library swaps the mates' trimmed files
     (cutseq/run.py:787-791), the barcodes' too; a demultiplexing run has no common trimmed file, and one handed over
     without files for its barcodes gets one nameless group for their streams (dropped, and of class 3 all the same).
-    ``--too-long-output`` (never in a demultiplexing run) adds a fourth group, not swapped: only the trimmed pair is."""
-    mates = 2 if paired else 1
+    ``--too-long-output`` (never in a demultiplexing run) adds a fourth group, not swapped: only the trimmed pair is.
+    An interleaved output (``args.interleaved_out``) has one name per class and nothing to swap: the device writes mate
+    2's record first instead (``mate2_first``)."""
+    interleaved = bool(getattr(args, "interleaved_out", False))
+    mates = 2 if paired and not interleaved else 1
     groups = [list(args.output_file) if not n_bins else [], list(args.short_file or []), list(args.untrimmed_file or [])]
     if n_bins:
         groups += [list(names) for names in (getattr(args, "demux_files", None) or [[]])]
@@ -766,7 +795,7 @@ def output_name_groups(args, paired: bool, swap_outputs: bool, n_bins: int) -> L
     if too_long and not n_bins:
         groups.append(too_long)
     groups = [(g + [None, None])[:mates] for g in groups]
-    if paired and swap_outputs:
+    if paired and swap_outputs and not interleaved:
         groups = [g if q in (1, 2) or (q == 3 and not n_bins) else g[::-1] for q, g in enumerate(groups)]
     return groups
 
@@ -777,12 +806,20 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
     global _DISCARD
     _DISCARD = switches.enabled("DISCARD_OUTPUT")  # diagnostic: the writers drop their bytes
     paired = tp.paired
+    # --interleaved: one reader whose blocks hold both mates (2 * chunk_reads records: chunk_reads pairs) and / or one
+    # writer per output class, whose stream the device has woven
+    woven_in, woven_out = bool(getattr(args, "interleaved_in", False)), bool(getattr(args, "interleaved_out", False))
+    if woven_in and shares is not None:
+        raise ValueError("an interleaved input cannot be split between ranks")
     share = shares or [{}, {}]
-    r1 = TextReader(args.input_file[0], chunk_reads, **share[0])  # (a missing input file raises here, before anything else exists)
+    if woven_in:
+        r1 = TextReader(args.input_file[0], 2 * chunk_reads, interleaved=True)
+    else:
+        r1 = TextReader(args.input_file[0], chunk_reads, **share[0])  # (a missing input file raises here, before anything else exists)
     r2 = None
     opened: List[StreamWriter] = []
     try:
-        r2 = TextReader(args.input_file[1], chunk_reads, **share[1]) if paired else None
+        r2 = TextReader(args.input_file[1], chunk_reads, **share[1]) if paired and not woven_in else None
         report.phase("readers started")
 
         # demultiplexing (table form): the trimmed pairs of barcode b are route 3 + b, one pair of files each
@@ -799,7 +836,8 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
             raise fastq.FastqFormatError("--max-ee needs qualities: the input is FASTA")
         if r1.fasta and tp.has_nextseq:  # (the qualities the FASTA re-shaper invents would not stop the Gs from going)
             raise fastq.FastqFormatError(f"--nextseq-trim needs qualities: {args.input_file[0]} is a FASTA file.")
-        fasta_routes = output_formats(name_groups, has_qualities=not r1.fasta)
+        # (an interleaved class is one file, hence one format: both mates' bits follow its name)
+        fasta_routes = output_formats([g * 2 for g in name_groups] if woven_out else name_groups, has_qualities=not r1.fasta)
 
         def writer(name, precompressed):
             opened.append(StreamWriter(name, precompressed=precompressed))
@@ -828,7 +866,9 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
     t_start = time.perf_counter()
     report.phase("readers and writers open")
     too_long_route = len(name_groups) == 4 and not n_bins  # --too-long-output: what -M catches is route 3
-    workers = [TextWorker(tp, dev, chunk_reads, compress, n_bins, fasta_routes, info_flags, too_long_route) for dev in devices]
+    workers = [TextWorker(tp, dev, chunk_reads, compress, n_bins, fasta_routes, info_flags, too_long_route,
+                          interleave_in=woven_in, interleave_out=woven_out, mate2_first=woven_out and tp.swap_outputs)
+               for dev in devices]
     if n_bins:
         totals["routes"] += [0] * n_bins
     budget = threading.Semaphore(2 * len(workers) * TextWorker.SLOTS + 2)  # batches between reader and disk
@@ -874,7 +914,7 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
                 totals[key] += pairs
         sizes = item.sizes if item.sizes is not None else res.route_bytes
         jobs = []
-        for m in range(2 if paired else 1):
+        for m in range(2 if paired and not woven_out else 1):
             at = 0
             for route in range(len(outs)):
                 nbytes = int(sizes[route][m])

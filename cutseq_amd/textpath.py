@@ -63,8 +63,13 @@ class TextEngine:
 
     def __init__(self, engine: TrimEngine, slots: int = 3, max_text_bytes: int = 64 << 20, max_records: int = 1 << 18,
                  stride: int = 152, compress: bool = False, bins: int = 0, fasta: bool = False,
-                 fasta_routes: int = 0, info: int = 0, too_long_route: bool = False):
-        """``too_long_route``: cutadapt's ``--too-long-output`` -- the pairs ``-M`` catches are written as route 3, a
+                 fasta_routes: int = 0, info: int = 0, too_long_route: bool = False,
+                 interleave_in: bool = False, interleave_out: bool = False, mate2_first: bool = False):
+        """``interleave_in`` / ``interleave_out`` / ``mate2_first``: cutadapt's ``--interleaved`` on a paired plan
+        (``cs_text_create_interleaved``) -- :meth:`submit` takes ONE text of ``2 * n_records`` records, mate 1 and mate 2
+        alternating; every route's two streams leave as one in mate 1's buffer, mate 1's record first (``mate2_first``:
+        mate 2's), and the sizes of mate 2's streams are 0.  Not with ``bins``.
+        ``too_long_route``: cutadapt's ``--too-long-output`` -- the pairs ``-M`` catches are written as route 3, a
         fourth stream (:meth:`routes`), class 3 of ``fasta_routes``; the plan needs ``max_length`` and no ``bins``.
         ``info``: ``abi.CS_INFO_*`` bits -- the batch also yields cutadapt's ``--info-file`` table for read 1
         (:meth:`info`, :meth:`fetch_info`).  ``compress``: every route's output leaves the device as one gzip member (``res.route_bytes`` then counts
@@ -98,8 +103,15 @@ class TextEngine:
             for i, lit in enumerate(lits):
                 arr[i] = lit
         self._h = C.c_void_p()
-        capi.check(self.L.cs_text_create(engine._eng_h, C.byref(p), slots, max_text_bytes, max_records, stride,
-                                         C.byref(self._h)))
+        self.interleave_in, self.interleave_out = bool(interleave_in), bool(interleave_out)
+        self.interleave = ((abi.CS_INTERLEAVE_IN if interleave_in else 0) | (abi.CS_INTERLEAVE_OUT if interleave_out else 0)
+                           | (abi.CS_INTERLEAVE_OUT_MATE2_FIRST if mate2_first else 0))
+        if self.interleave:
+            capi.check(self.L.cs_text_create_interleaved(engine._eng_h, C.byref(p), self.interleave, slots, max_text_bytes,
+                                                         max_records, stride, C.byref(self._h)))
+        else:
+            capi.check(self.L.cs_text_create(engine._eng_h, C.byref(p), slots, max_text_bytes, max_records, stride,
+                                             C.byref(self._h)))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -113,8 +125,9 @@ class TextEngine:
         self.close()
 
     def submit(self, slot: int, text1, bytes1: int, text2=None, bytes2: int = 0, n_records: int = 0) -> None:
-        """Asynchronous.  ``text1`` / ``text2``: buffers (or addresses) holding ``n_records`` complete records each;
-        they must stay untouched until :meth:`wait` returns."""
+        """Asynchronous.  ``text1`` / ``text2``: buffers (or addresses) holding ``n_records`` complete records each
+        (``interleave_in``: ``text1`` alone, ``2 * n_records`` records); they must stay untouched until :meth:`wait`
+        returns."""
         capi.check(self.L.cs_text_submit(self._h, slot, _address(text1), bytes1, _address(text2) or None, bytes2, n_records))
 
     def wait(self, slot: int, first_record: int = 0, names=("mate 1", "mate 2")) -> abi.cs_text_result:
@@ -180,16 +193,18 @@ class TextEngine:
         self.submit(slot, text1, len(text1), text2, len(text2) if text2 is not None else 0, n_records)
         res = self.wait(slot)
         got, _, count = self.routes(slot)
+        paired = text2 is not None or self.interleave_in
         out = [np.empty(max(int(res.out_bytes[m]), 1), dtype=np.uint8) for m in range(2)]
-        self.fetch(slot, out[0], out[1] if text2 is not None else None)
+        self.fetch(slot, out[0], out[1] if paired and not self.interleave_out else None)
         if self.n_routes > 3:
-            return split_routes(got, out, text2 is not None), [int(c) for c in count]
-        return split_routes(res, out, text2 is not None), [int(c) for c in res.route_count]
+            return split_routes(got, out, paired), [int(c) for c in count]
+        return split_routes(res, out, paired), [int(c) for c in res.route_count]
 
 
 def split_routes(res, out, paired: bool):
     """-> streams[route][mate] (bytes) from the per-mate buffers :meth:`TextEngine.fetch` filled.  ``res``: the
-    ``cs_text_result`` of the batch, or the bytes[route, mate] array of :meth:`TextEngine.routes`."""
+    ``cs_text_result`` of the batch, or the bytes[route, mate] array of :meth:`TextEngine.routes`.  An interleaved
+    output (``interleave_out``) has sizes of 0 for mate 2: every route comes back as ``[woven stream, b""]``."""
     sizes = res.route_bytes if isinstance(res, abi.cs_text_result) else res
     streams = [[b"", b""] for _ in range(len(sizes))]
     for m in range(2 if paired else 1):

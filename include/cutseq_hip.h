@@ -460,6 +460,30 @@ typedef struct cs_text cs_text;
  * `stride` bytes (multiple of 4, <= CS_MAX_STRIDE).  Uses the engine's plan, streams and statistics block. */
 int cs_text_create(cs_engine *eng, const cs_text_params *params, uint32_t n_slots, uint64_t max_text_bytes,
                    uint32_t max_records, uint32_t stride, cs_text **out);
+/* cutadapt's --interleaved: the mates of a paired plan in ONE text and / or ONE stream per route.  cs_text_create is
+ * this function with interleave = 0 (and launches exactly the kernels it launched before this one existed).
+ *
+ * CS_INTERLEAVE_IN: cs_text_submit takes one text of 2 * n_records records -- mate 1 of pair 0, mate 2 of pair 0, mate 1
+ * of pair 1, ... --, text2 must be NULL and bytes2 0; max_text_bytes bounds that one text.  n_records, max_records,
+ * error_record and every count keep meaning pairs: a malformed record of either mate of pair r reports record r, mates
+ * whose ids differ CS_TEXT_ERR_IDS_DIFFER at r, a text without 8 * n_records lines CS_TEXT_ERR_LINE_COUNT
+ * (cs_text_result.n_lines[0] has the lines found, n_lines[1] is 0).
+ *
+ * CS_INTERLEAVE_OUT: each route's two mate streams are one stream in mate 1's buffer -- the record of mate 1, then the
+ * record of mate 2, pair after pair in input order; with CS_INTERLEAVE_OUT_MATE2_FIRST mate 2's record leads (what
+ * paired --auto-rc on a '-' library asks for, where two files would swap names).  route_bytes[q][1], text_bytes[q][1],
+ * out_bytes[1] and the [q][1] entries of cs_text_routes are 0, the [q][0] entries describe the woven stream, and
+ * cs_text_fetch takes dst2 == NULL.  With compress each route is one gzip member holding both mates.  route_count,
+ * written_bp[2], cs_text_discards and the info table are what they are without the bit.
+ *
+ * CS_ERR_ARG: any bit on a single-end plan; an unknown bit; MATE2_FIRST without OUT; params->n_bins != 0 (the kernels of
+ * demultiplexing plans are not extended); with OUT, fasta_routes bits of one class that differ between the mates (one
+ * stream has one format), and a woven buffer of 1 GiB or more (the bound cs_text_create applies per mate applies to the
+ * sum: output offsets keep 30 bits). */
+enum { CS_INTERLEAVE_IN = 1, CS_INTERLEAVE_OUT = 2, CS_INTERLEAVE_OUT_MATE2_FIRST = 4 };
+int cs_text_create_interleaved(cs_engine *eng, const cs_text_params *params, uint32_t interleave,
+                               uint32_t n_slots, uint64_t max_text_bytes, uint32_t max_records,
+                               uint32_t stride, cs_text **out);
 void cs_text_destroy(cs_text *t);
 /* Asynchronous: upload (text1 / text2: host memory, pinned for true overlap; they must stay untouched until
  * cs_text_wait returns), record index, trimming kernels, output formatting.  text2 == NULL for single-end. */
