@@ -289,7 +289,7 @@ def _append_parts(final: str, parts: List[str]) -> None:
 
 
 def _host_threads(args) -> int:
-    return int(args.threads) if getattr(args, "threads", None) else fastq.pool_size()
+    return int(args.threads) if args.threads else fastq.pool_size()
 
 
 def run_parent(argv: List[str], args, tp) -> Optional[dict]:
@@ -297,10 +297,7 @@ def run_parent(argv: List[str], args, tp) -> Optional[dict]:
     to one process."""
     world = int(args.ranks)
     paths = list(args.input_file)
-    names_all = [n for names in (args.output_file, args.short_file, args.untrimmed_file,
-                                 getattr(args, "too_long_file", None) or [],
-                                 [getattr(args, "info_file", None)]) for n in names if n]
-    if "-" in paths or "-" in names_all:
+    if "-" in paths or "-" in args.outputs.names():
         logging.warning(f"--ranks {world} ignored: standard input / output cannot be shared between ranks.")
         return None
     for path in paths:
@@ -309,7 +306,7 @@ def run_parent(argv: List[str], args, tp) -> Optional[dict]:
             logging.warning(f"--ranks {world} ignored: {path} is not a plain or gzip FASTQ file.")
             return None
     t0 = time.perf_counter()
-    if getattr(args, "threads", None):
+    if args.threads:
         try:
             fastq.set_threads(args.threads)  # (the counting pass below honours -t too)
         except RuntimeError:
@@ -353,18 +350,9 @@ def part_name(name, r):
 
 
 def output_groups(args) -> dict:
-    """{key of a rank's spec: the output files under it}: every rank writes a part of each (``part_name``) and the
-    parts are concatenated in rank order."""
-    groups = {"output_file": args.output_file, "short_file": args.short_file, "untrimmed_file": args.untrimmed_file}
-    for b, names in enumerate(getattr(args, "demux_files", None) or []):  # demultiplexing: a pair of files per barcode
-        groups[f"demux_files:{b}"] = names
-    if getattr(args, "too_long_file", None):  # --too-long-output: parts like the too-short files'
-        groups["too_long_file"] = args.too_long_file
-    if getattr(args, "info_file", None):  # every rank's table of its share; concatenated in rank order like the records
-        groups["info_file"] = [args.info_file]
-    if getattr(args, "demux_files", None):
-        groups["output_file"] = [None] * len(args.output_file)  # (nothing is written under the common trimmed names)
-    return groups
+    """{key of a rank's spec: the output files under it} (``OutputLayout.rank_groups``): every rank writes a part of each
+    (``part_name``) and the parts are concatenated in rank order."""
+    return args.outputs.rank_groups()
 
 
 def _run_ranks(argv: List[str], args, world: int, shares, t0: float, how: str) -> dict:
@@ -412,7 +400,7 @@ def _run_ranks(argv: List[str], args, world: int, shares, t0: float, how: str) -
             report.merge_totals(totals, part)
             stats += part["stats"]
             devs += part["devices"]
-        bin_names = list(args.demux[0]) if getattr(args, "demux", None) else None
+        bin_names = list(args.demux[0]) if args.demux else None
         totals.update(stats=stats, devices=devs, bin_names=bin_names, seconds=time.perf_counter() - t0, ranks=world,
                       ranks_split=how, threads_per_rank=per_rank)
         progress = report.Progress()

@@ -20,9 +20,10 @@ import time
 from collections import deque
 from typing import List, Optional
 
-from . import __version__, abi, fanout, report, switches
+from . import __version__, abi, fanout, outputs, report, switches
 from .abi import ReadTooLong
-from .common import BUILDIN_ADAPTERS, BarcodeConfig, print_builtin_adapters, remove_fq_suffix
+from .common import BUILDIN_ADAPTERS, BarcodeConfig, print_builtin_adapters
+from .outputs import OUTPUT_CLASSES, _fail  # noqa: F401 -- (OUTPUT_CLASSES: under the name it had here)
 from .plan import CutadaptConfig, TrimPlan, compile_paired, compile_single
 from .report import phase as _phase
 
@@ -155,70 +156,29 @@ class _QualityCutoffs(argparse.Action):
         setattr(namespace, front, cutoffs[0] if len(cutoffs) == 2 else 0)
 
 
-# Output naming (user-visible contract of the reference CLI, run.py:1058-1107): for every output class the
-# files are, in this order of precedence, the ones given on the command line (one per input file), the
-# -O prefix, or the input name without its FASTQ suffix, followed by "_<class>_R<mate>.fastq.gz".
-OUTPUT_CLASSES = (  # (argparse attribute, word in the file name)
-    ("output_file", "trimmed"),
-    ("short_file", "short"),
-    ("untrimmed_file", "untrimmed"),
-)
 _SCHEME_HAS_INLINE = re.compile(r".*\([ATGCatgc]+\).*")
 
 
-def _fail(message: str):
-    logging.error(message)
-    sys.exit(1)
-
-
-def output_paths(given, inputs, prefix, word, interleaved=None):
-    """File names of one output class, one per input file.  ``interleaved`` (an ``--interleaved`` run): "out" -- the
-    class is ONE file of interleaved pairs, ``<stem>_<word>.fastq.gz`` --, or "split" -- one interleaved input file,
-    two output files; the stem comes from ``-O`` or from the first input file."""
-    if interleaved:
-        want = 1 if interleaved == "out" else 2
-        if given:
-            if len(given) != want:
-                _fail(f"Number of {word} output files ({len(given)}) must match the number this --interleaved run "
-                      f"writes per class: {want} ({'interleaved' if want == 1 else 'one per mate'}).")
-            return list(given)
-        stem = prefix if prefix is not None else remove_fq_suffix(inputs[0])
-        return [f"{stem}_{word}.fastq.gz"] if want == 1 else [f"{stem}_{word}_R{mate}.fastq.gz" for mate in (1, 2)]
-    if given:
-        if len(given) != len(inputs):
-            _fail(f"Number of {word} output files ({len(given)}) must match number of input files ({len(inputs)}).")
-        return list(given)
-    stems = [prefix] * len(inputs) if prefix is not None else [remove_fq_suffix(name) for name in inputs]
-    return [f"{stem}_{word}_R{mate}.fastq.gz" for mate, stem in enumerate(stems, 1)]
-
-
 def resolve_interleaved(args, inputs):
-    """``--interleaved`` -> args.interleaved_in / args.interleaved_out / args.paired, and the form of every output class
-    (None: not such a run, "out": one interleaved file, "split": interleaved input, two files).  One input file: it
-    holds the pairs, and the outputs are interleaved unless -o names two files.  Two input files: the outputs are
-    interleaved, and -o takes one name."""
-    args.interleaved_in = args.interleaved_out = False
-    args.paired = len(inputs) == 2
-    if not getattr(args, "interleaved", False) or not inputs:
-        return None
+    """``--interleaved`` -> (the input is interleaved, the outputs are).  One input file: it holds the pairs, and the
+    outputs are interleaved unless -o names two files.  Two input files: the outputs are interleaved, and -o takes one
+    name."""
+    if not args.interleaved or not inputs:
+        return False, False
     if args.demux_barcodes:
         _fail("--interleaved cannot be combined with --demux-barcodes: the barcodes' kernels write one stream per mate.")
     if not switches.enabled("TEXT_PATH"):
         _fail("--interleaved needs the text path: the pairs are woven on the GPU (CUTSEQ_TEXT_PATH=0 is set).")
     given = len(args.output_file) if args.output_file else 0
     if len(inputs) == 1:
-        args.interleaved_in = True
-        args.interleaved_out = given != 2
-        if getattr(args, "ranks", 1) > 1 and not getattr(args, "rank_spec", None):
+        if args.ranks > 1 and not args.rank_spec:
             _fail("--interleaved input cannot be split between --ranks: a share that begins at a record boundary "
                   "cannot know which mate it begins with (two input files with --interleaved output can).")
-    else:
-        if given == 2:
-            _fail("--interleaved with two input files and two -o files would have nothing to do: give -o one name "
-                  "(interleaved output) or drop --interleaved.")
-        args.interleaved_out = True
-    args.paired = True
-    return "out" if args.interleaved_out else "split"
+        return True, given != 2
+    if given == 2:
+        _fail("--interleaved with two input files and two -o files would have nothing to do: give -o one name "
+              "(interleaved output) or drop --interleaved.")
+    return False, True
 
 
 def resolve_scheme(args) -> str:
@@ -246,36 +206,31 @@ def resolve_args(args):
     if len(inputs) > 2:
         _fail("Input file can not be more than two.")
     args.adapter_scheme = resolve_scheme(args)
-    max_n = getattr(args, "max_n", None)
-    if max_n is not None and not max_n >= 0:  # (NaN fails the comparison too)
-        _fail(f"--max-n: the count must not be negative (got {max_n}).")
-    max_length, max_ee = getattr(args, "max_length", None), getattr(args, "max_ee", None)
-    if max_length is not None and max_length < 0:
-        _fail(f"-M/--max-length: the length must not be negative (got {max_length}).")
-    if max_ee is not None and not max_ee >= 0:  # (NaN fails the comparison too)
-        _fail(f"--max-ee: the number of expected errors must not be negative (got {max_ee}).")
-    nextseq = getattr(args, "nextseq_trim", None)
+    if args.max_n is not None and not args.max_n >= 0:  # (NaN fails the comparison too)
+        _fail(f"--max-n: the count must not be negative (got {args.max_n}).")
+    if args.max_length is not None and args.max_length < 0:
+        _fail(f"-M/--max-length: the length must not be negative (got {args.max_length}).")
+    if args.max_ee is not None and not args.max_ee >= 0:  # (NaN fails the comparison too)
+        _fail(f"--max-ee: the number of expected errors must not be negative (got {args.max_ee}).")
+    nextseq = args.nextseq_trim
     if nextseq is not None and not abi.CS_Q_SUM_LOW <= nextseq + 33 <= abi.CS_Q_SUM_HIGH:
         # (unlike -q's, this cutoff is not clamped: a G's term is +1 whatever it is -- include/cutseq_hip.h, CS_OP_NEXTSEQ)
         _fail(f"--nextseq-trim: the cutoff must lie in [{abi.CS_Q_SUM_LOW - 33}, {abi.CS_Q_SUM_HIGH - 33}] (got {nextseq}).")
-    form = resolve_interleaved(args, inputs)
-    if getattr(args, "min_quality_r2", None) is not None and len(inputs) == 1 and not args.interleaved_in:
+    interleaved_in, interleaved_out = resolve_interleaved(args, inputs)
+    if args.min_quality_r2 is not None and len(inputs) == 1 and not interleaved_in:
         _fail("-Q sets the quality cutoff of the second read: it needs two input files.")
-    if getattr(args, "info_file", None):
+    if args.info_file:
         if args.demux_barcodes:
             _fail("--info-file cannot be combined with --demux-barcodes: the table form of the demultiplexing op has "
                   "no error count to report.")
         if not switches.enabled("TEXT_PATH"):
             _fail("--info-file needs the text path: the table is written on the GPU (CUTSEQ_TEXT_PATH=0 is set).")
-    too_long_file = getattr(args, "too_long_file", None)
-    if too_long_file:
-        if max_length is None:
+    if args.too_long_file:
+        if args.max_length is None:
             _fail("--too-long-output needs -M/--max-length: without it no read is too long.")
         if args.demux_barcodes:
             _fail("--too-long-output cannot be combined with --demux-barcodes: the output class it would take on the "
                   "GPU is the barcodes' there.")
-        if inputs:  # (no default name from -O: the given names or none)
-            args.too_long_file = output_paths(too_long_file, inputs, None, "too-long", form)
     if not inputs:
         # the reference dies with an IndexError here (run.py:1079-1083); same exit class, clearer message
         _fail("Input file is required.")
@@ -290,13 +245,12 @@ def resolve_args(args):
             _fail(str(exc))
     wants_untrimmed = bool(args.untrimmed_file) or args.demux is not None or (
         args.ensure_inline_barcode and _SCHEME_HAS_INLINE.match(args.adapter_scheme) is not None)
-    for attr, word in OUTPUT_CLASSES:
-        if attr == "untrimmed_file" and not wants_untrimmed:
-            args.untrimmed_file = [None] * ({"out": 1, "split": 2}.get(form) or len(inputs))
-        else:
-            setattr(args, attr, output_paths(getattr(args, attr), inputs, args.output_prefix, word, form))
-    if args.demux is not None:  # one pair of trimmed files per barcode instead of the common one
-        args.demux_files = [output_paths(None, inputs, args.output_prefix, f"{name}_trimmed") for name in args.demux[0]]
+    layout = args.outputs = outputs.resolve(args, interleaved_in, interleaved_out, wants_untrimmed)
+    # (what the options resolved to, for callers that look: nothing in this package reads them from here on)
+    args.paired, args.interleaved_in, args.interleaved_out = layout.paired, interleaved_in, interleaved_out
+    for cls in layout.classes:
+        if not cls.barcode:
+            setattr(args, cls.key, list(cls.names))
     return args
 
 
@@ -310,31 +264,28 @@ def settings_from_args(args) -> CutadaptConfig:
     st.threads = args.threads if args.threads is not None else 0
     st.min_length = args.min_length
     st.min_quality = args.min_quality
-    st.min_quality_front = getattr(args, "min_quality_front", 0)
-    st.trim_n = getattr(args, "trim_n", False)
-    st.nextseq_trim = getattr(args, "nextseq_trim", None)
-    st.min_quality_r2 = getattr(args, "min_quality_r2", None)
-    st.min_quality_front_r2 = getattr(args, "min_quality_front_r2", None)
+    st.min_quality_front = args.min_quality_front
+    st.trim_n = args.trim_n
+    st.nextseq_trim = args.nextseq_trim
+    st.min_quality_r2 = args.min_quality_r2
+    st.min_quality_front_r2 = args.min_quality_front_r2
     st.dry_run = args.dry_run
     st.auto_rc = args.auto_rc
     st.json_file = args.json_file
     st.force_trim_min_length = args.force_trim_min_length
     st.force_anywhere = args.force_anywhere
     st.select_rule = abi.CS_SELECT_LEFTMOST if args.cutadapt_selection == "4" else abi.CS_SELECT_SCORE
-    st.max_n = getattr(args, "max_n", None)
-    st.max_length = getattr(args, "max_length", None)
-    st.max_ee = getattr(args, "max_ee", None)
-    if getattr(args, "demux", None) is not None:
+    st.max_n = args.max_n
+    st.max_length = args.max_length
+    st.max_ee = args.max_ee
+    if args.demux is not None:
         st.demux_barcodes = list(args.demux[1])
     return st
 
 
 def compile_plan(args, barcode: BarcodeConfig, settings: CutadaptConfig) -> TrimPlan:
-    if not getattr(args, "paired", len(args.input_file) == 2):  # (--interleaved: one input file can hold pairs)
-        return compile_single(barcode, settings, untrimmed_requested=args.untrimmed_file[0] is not None)
-    return compile_paired(
-        barcode, settings,
-        untrimmed_requested=all(name is not None for name in args.untrimmed_file))
+    compile_for = compile_paired if args.outputs.paired else compile_single  # (--interleaved: one input file can hold pairs)
+    return compile_for(barcode, settings, untrimmed_requested=args.outputs.untrimmed_requested)
 
 
 def dry_run_steps(tp: TrimPlan) -> List[str]:
@@ -442,7 +393,7 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
     _phase("devices counted")
     if n_dev <= 0:
         raise capi.HipUnavailable("no HIP device visible; cutseq_amd has no CPU trimming path")
-    if getattr(args, "threads", None) is not None:
+    if args.threads is not None:
         if args.threads < 1:
             _fail("-t/--threads must be at least 1.")
         try:
@@ -473,9 +424,8 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
     paired = tp.paired
     n_bins = len(tp.demux.barcodes) if tp.demux is not None else 0
     # the open file (or None) per [stream][mate]
-    outs = [[fastq.OutputFile(n) if n else None for n in names]
-            for names in textio.output_name_groups(args, paired, tp.swap_outputs, n_bins)]
-    too_long_route = len(outs) == 4 and not n_bins  # --too-long-output: stream 3 holds what -M catches
+    outs = [[fastq.OutputFile(n) if n else None for n in names] for names in args.outputs.name_groups(tp.swap_outputs)]
+    too_long_route = args.outputs.too_long_route  # --too-long-output: stream 3 holds what -M catches
     # which (route, mate) streams go to disk, and whether they are gzip
     gz = [[(fh.gz if fh is not None else None) for fh in (group + [None])[:2]] for group in outs]
 
@@ -566,16 +516,10 @@ def run_cutseq(args, argv=None):
                 if name != "-" and codec.sniff_input(name)[1] in (b">", b"#"):
                     _fail(f"{option} needs qualities: {name} is a FASTA file.")
     totals = None
-    if getattr(args, "rank_spec", None):  # a child of --ranks: its share, its part files, its totals; the parent reports
+    if args.rank_spec:  # a child of --ranks: its share, its part files, its totals; the parent reports
         from . import ranks
         spec = ranks.load_spec(args.rank_spec)
-        for key, names in spec["outputs"].items():
-            if key.startswith("demux_files:"):
-                args.demux_files[int(key.split(":")[1])] = names
-            elif key == "info_file":
-                args.info_file = names[0]
-            else:
-                setattr(args, key, names)
+        args.outputs = args.outputs.with_rank_names(spec["outputs"])
         try:
             totals = run_pipeline(args, tp, shares=spec["inputs"])
         except (ValueError, OSError) as exc:
@@ -588,7 +532,7 @@ def run_cutseq(args, argv=None):
             raise
         ranks.dump_totals(spec, totals)
         return totals
-    if getattr(args, "ranks", 1) > 1:
+    if args.ranks > 1:
         if not switches.enabled("TEXT_PATH"):
             logging.warning("--ranks ignored: it needs the text path.")
         else:
@@ -599,15 +543,8 @@ def run_cutseq(args, argv=None):
         totals = run_pipeline(args, tp)
         _phase("pipeline done")
     if args.json_file:
-        # (the mate-2 keys are null where one file holds both mates: interleaved input, interleaved output)
-        second = lambda names: names[1] if tp.paired and len(names) > 1 else None  # noqa: E731
-        rep = report.json_report(
-            tp, totals, barcode, args.input_file[0], second(args.input_file),
-            args.output_file[0], second(args.output_file), args.short_file[0], second(args.short_file),
-            args.untrimmed_file[0], second(args.untrimmed_file),
-            info_file=getattr(args, "info_file", None), too_long_files=getattr(args, "too_long_file", None),
-            interleaved=getattr(args, "interleaved_in", False))
-        report.write_json(args.json_file, rep)
+        names, extra = args.outputs.report_names(args.input_file)
+        report.write_json(args.json_file, report.json_report(tp, totals, barcode, *names, **extra))
     print(report.minimal_report(tp, totals), file=sys.stderr)
     return totals
 
@@ -629,7 +566,7 @@ def _block_records(args, n_devices: int) -> int:
     if args.input_file[0].endswith(".gz"):
         size *= 4  # (a guess at the text behind it)
     records = size // 300  # (a short-read record is ~330 bytes)
-    if getattr(args, "interleaved_in", False):  # (a block counts pairs, and this file holds both mates)
+    if args.outputs.interleaved_in:  # (a block counts pairs, and this file holds both mates)
         records //= 2
     want = records // (24 * max(n_devices, 1))
     block = textio.CHUNK_READS

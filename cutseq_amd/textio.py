@@ -21,6 +21,7 @@ behind ``CUTSEQ_TEXT_PATH=0``, held to the same outputs by the tests' switch mat
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import mmap
 import os
 import queue
@@ -32,6 +33,7 @@ import numpy as np
 
 from . import abi, codec, fanout, fastq, report, switches, textpath
 from .abi import ReadTooLong
+from .outputs import TextOptions
 
 CHUNK_READS = 1 << 18
 _BLOCK = 8 << 20          # bytes per pread / per inflate hand-over
@@ -619,17 +621,10 @@ class TextWorker(fanout.Worker):
     SLOTS = 3
     _tick = staticmethod(_tick)
 
-    def __init__(self, tp, device: int, chunk_reads: int, compress: bool = False, bins: int = 0,
-                 fasta_routes: int = 0, info: int = 0, too_long_route: bool = False, interleave_in: bool = False,
-                 interleave_out: bool = False, mate2_first: bool = False):
+    def __init__(self, tp, device: int, chunk_reads: int, options: TextOptions):
         super().__init__(f"cutseq-gpu{device}")
-        # --interleaved: an item is (block of both mates, None); the routes come back as one stream each
-        self.interleave_in, self.interleave_out, self.mate2_first = interleave_in, interleave_out, mate2_first
-        self.too_long_route = too_long_route  # --too-long-output: the pairs -M catches are a fourth stream (route 3)
-        self.info = info  # abi.CS_INFO_* bits: the batches also yield the --info-file table
-        self.tp, self.device, self.chunk_reads, self.compress = tp, device, chunk_reads, compress
-        self.fasta_routes = fasta_routes  # bit 2 * class + mate: that stream's records leave as FASTA
-        self.bins = bins  # demultiplexing: one route per barcode behind the three ordinary ones
+        self.tp, self.device, self.chunk_reads, self.options = tp, device, chunk_reads, options
+        self.mates_out = 2 if tp.paired and not options.interleave_out else 1  # (a woven route comes back as one stream)
         self.text = None
         self.stride, self.capacity, self.want_stride = 152, 0, 152
 
@@ -652,10 +647,7 @@ class TextWorker(fanout.Worker):
         self.stride = stride
         self.capacity = max(self.capacity, int(text_bytes * 1.25) + (1 << 20))
         self.text = textpath.TextEngine(self.engine, slots=self.SLOTS, max_text_bytes=self.capacity,
-                                        max_records=self.chunk_reads, stride=self.stride, compress=self.compress,
-                                        bins=self.bins, fasta_routes=self.fasta_routes, info=self.info,
-                                        too_long_route=self.too_long_route, interleave_in=self.interleave_in,
-                                        interleave_out=self.interleave_out, mate2_first=self.mate2_first)
+                                        max_records=self.chunk_reads, stride=self.stride, **dataclasses.asdict(self.options))
 
     def submit(self, slot: int, item):
         b1, b2 = item
@@ -679,18 +671,17 @@ class TextWorker(fanout.Worker):
         if max(res.n_long) * 64 > b1.n and self.stride < abi.CS_MAX_STRIDE:
             self.want_stride = max(self.want_stride, min(abi.CS_MAX_STRIDE, (int(res.max_len) + 3) // 4 * 4))
         sizes = counts = None
-        if self.bins or self.too_long_route:
+        if self.options.bins or self.options.too_long_route:
             sizes, _, counts = self.text.routes(slot)
         discards = self.text.discards(slot) if self.tp.has_filters else None
-        mates_out = 1 if self.interleave_out else (2 if b2 is not None or self.interleave_in else 1)
-        out = [fastq.PINNED.take(max(int(res.out_bytes[m]), 1)) for m in range(mates_out)]
+        out = [fastq.PINNED.take(max(int(res.out_bytes[m]), 1)) for m in range(self.mates_out)]
         info_buf, info_bytes = None, 0
-        if self.info:
+        if self.options.info:
             info_bytes = self.text.info(slot)[0]
             info_buf = fastq.PINNED.take(max(info_bytes, 1))
             self.text.fetch_info(slot, info_buf)
         t0 = _tick("take", t0)
-        self.text.fetch(slot, out[0], out[1] if mates_out == 2 else None)
+        self.text.fetch(slot, out[0], out[1] if self.mates_out == 2 else None)
         _tick("fetch", t0)
         b1.release()
         if b2 is not None:
@@ -779,25 +770,30 @@ def output_formats(groups, has_qualities: bool) -> int:
 
 
 def output_name_groups(args, paired: bool, swap_outputs: bool, n_bins: int) -> List[list]:
-    """The output files' names by the stream they receive -- [trimmed, too short, untrimmed, barcode 0, barcode 1, ...],
-    one entry per mate each (None: no such file).  Paired --auto-rc on a '-' library swaps the mates' trimmed files
-    (cutseq/run.py:787-791), the barcodes' too; a demultiplexing run has no common trimmed file, and one handed over
-    without files for its barcodes gets one nameless group for their streams (dropped, and of class 3 all the same).
-    ``--too-long-output`` (never in a demultiplexing run) adds a fourth group, not swapped: only the trimmed pair is.
-    An interleaved output (``args.interleaved_out``) has one name per class and nothing to swap: the device writes mate
-    2's record first instead (``mate2_first``)."""
-    interleaved = bool(getattr(args, "interleaved_out", False))
-    mates = 2 if paired and not interleaved else 1
-    groups = [list(args.output_file) if not n_bins else [], list(args.short_file or []), list(args.untrimmed_file or [])]
-    if n_bins:
-        groups += [list(names) for names in (getattr(args, "demux_files", None) or [[]])]
-    too_long = list(getattr(args, "too_long_file", None) or [])
-    if too_long and not n_bins:
-        groups.append(too_long)
-    groups = [(g + [None, None])[:mates] for g in groups]
-    if paired and swap_outputs and not interleaved:
-        groups = [g if q in (1, 2) or (q == 3 and not n_bins) else g[::-1] for q, g in enumerate(groups)]
-    return groups
+    """``args.outputs.name_groups(swap_outputs)`` under its name of old (``paired`` and ``n_bins`` are the layout's own)."""
+    return args.outputs.name_groups(swap_outputs)
+
+
+def text_options(layout, tp, fasta: bool, gpu_deflate: bool) -> TextOptions:
+    """What the text engines of a run are told: from the output layout, the plan, the input's format (``fasta``: it has
+    no qualities) and the CUTSEQ_GPU_DEFLATE switch.
+    ``compress``: every output a ".gz" file -- the device compresses (deflate_kernels.hip.inc) and the writers pass the
+    members through; otherwise text comes back and ".gz" outputs are deflated in the host pool.  ``info``: the
+    --info-file table is one more stream per batch; its container goes by the file's name like a record output's, and a
+    ".gz" table leaves the device as gzip members under the same switch."""
+    groups = layout.name_groups(tp.swap_outputs)
+    names = layout.names(info=False)
+    info = 0
+    if layout.info_file:
+        info_gz = gpu_deflate and layout.info_file != "-" and codec.container_of_name(layout.info_file) == "gzip"
+        info = abi.CS_INFO_ON | (abi.CS_INFO_GZIP if info_gz else 0) | (abi.CS_INFO_NO_QUAL if fasta else 0)
+    return TextOptions(
+        compress=gpu_deflate and bool(names) and all(n != "-" and codec.container_of_name(n) == "gzip" for n in names),
+        bins=len(tp.demux.barcodes) if tp.demux is not None else 0,  # (table form: the pairs of barcode b are route 3 + b)
+        # (an interleaved class is one file, hence one format: both mates' bits follow its name)
+        fasta_routes=output_formats([g * 2 for g in groups] if layout.interleaved_out else groups, has_qualities=not fasta),
+        info=info, too_long_route=layout.too_long_route, interleave_in=layout.interleaved_in,
+        interleave_out=layout.interleaved_out, mate2_first=layout.interleaved_out and tp.swap_outputs)
 
 
 def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
@@ -806,9 +802,10 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
     global _DISCARD
     _DISCARD = switches.enabled("DISCARD_OUTPUT")  # diagnostic: the writers drop their bytes
     paired = tp.paired
+    layout = args.outputs
     # --interleaved: one reader whose blocks hold both mates (2 * chunk_reads records: chunk_reads pairs) and / or one
     # writer per output class, whose stream the device has woven
-    woven_in, woven_out = bool(getattr(args, "interleaved_in", False)), bool(getattr(args, "interleaved_out", False))
+    woven_in, woven_out = layout.interleaved_in, layout.interleaved_out
     if woven_in and shares is not None:
         raise ValueError("an interleaved input cannot be split between ranks")
     share = shares or [{}, {}]
@@ -822,36 +819,20 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         r2 = TextReader(args.input_file[1], chunk_reads, **share[1]) if paired and not woven_in else None
         report.phase("readers started")
 
-        # demultiplexing (table form): the trimmed pairs of barcode b are route 3 + b, one pair of files each
-        n_bins = len(tp.demux.barcodes) if tp.demux is not None else 0
-        name_groups = output_name_groups(args, paired, tp.swap_outputs, n_bins)
-        # every output a ".gz" file: the device compresses (deflate_kernels.hip.inc) and the writers pass the members
-        # through; otherwise text comes back and ".gz" outputs are deflated in the host pool (CUTSEQ_GPU_DEFLATE=0 too)
-        names_all = [n for group in name_groups for n in group if n]
-        gpu_deflate = switches.enabled("GPU_DEFLATE")
-        compress = gpu_deflate and bool(names_all) and all(n != "-" and codec.container_of_name(n) == "gzip" for n in names_all)
         if r2 is not None and r1.fasta != r2.fasta:
             raise fastq.FastqFormatError("the two input files are in different formats (one FASTA, one FASTQ)")
         if r1.fasta and tp.max_ee is not None:
             raise fastq.FastqFormatError("--max-ee needs qualities: the input is FASTA")
         if r1.fasta and tp.has_nextseq:  # (the qualities the FASTA re-shaper invents would not stop the Gs from going)
             raise fastq.FastqFormatError(f"--nextseq-trim needs qualities: {args.input_file[0]} is a FASTA file.")
-        # (an interleaved class is one file, hence one format: both mates' bits follow its name)
-        fasta_routes = output_formats([g * 2 for g in name_groups] if woven_out else name_groups, has_qualities=not r1.fasta)
+        options = text_options(layout, tp, r1.fasta, switches.enabled("GPU_DEFLATE"))
 
         def writer(name, precompressed):
             opened.append(StreamWriter(name, precompressed=precompressed))
             return opened[-1]
 
-        outs = [[writer(n, compress) if n else None for n in names] for names in name_groups]
-        # --info-file: one more stream per batch.  The container goes by the file's name like a record output's; a
-        # ".gz" table leaves the device as gzip members (CUTSEQ_GPU_DEFLATE=0: deflated in the host pool instead).
-        info_name = getattr(args, "info_file", None)
-        info_flags, info_out = 0, None
-        if info_name:
-            info_gz = gpu_deflate and info_name != "-" and codec.container_of_name(info_name) == "gzip"
-            info_flags = abi.CS_INFO_ON | (abi.CS_INFO_GZIP if info_gz else 0) | (abi.CS_INFO_NO_QUAL if r1.fasta else 0)
-            info_out = writer(info_name, info_gz)
+        outs = [[writer(n, options.compress) if n else None for n in names] for names in layout.name_groups(tp.swap_outputs)]
+        info_out = writer(layout.info_file, bool(options.info & abi.CS_INFO_GZIP)) if layout.info_file else None
     except BaseException:
         r1.close()
         if r2 is not None:
@@ -865,12 +846,8 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
     totals = report.new_totals()
     t_start = time.perf_counter()
     report.phase("readers and writers open")
-    too_long_route = len(name_groups) == 4 and not n_bins  # --too-long-output: what -M catches is route 3
-    workers = [TextWorker(tp, dev, chunk_reads, compress, n_bins, fasta_routes, info_flags, too_long_route,
-                          interleave_in=woven_in, interleave_out=woven_out, mate2_first=woven_out and tp.swap_outputs)
-               for dev in devices]
-    if n_bins:
-        totals["routes"] += [0] * n_bins
+    workers = [TextWorker(tp, dev, chunk_reads, options) for dev in devices]
+    totals["routes"] += [0] * options.bins
     budget = threading.Semaphore(2 * len(workers) * TextWorker.SLOTS + 2)  # batches between reader and disk
     progress = report.Progress()
 
@@ -947,7 +924,7 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         totals["out_bp"][m] = sum(int(pair[m]["out_bp"]) for pair in stats)
     totals["seconds"] = time.perf_counter() - t_start
     progress.close()
-    totals["bin_names"] = list(args.demux[0]) if n_bins else None
+    totals["bin_names"] = list(args.demux[0]) if options.bins else None
     totals["stats"] = stats
     totals["devices"] = devices
     totals["path"] = "text"

@@ -425,7 +425,9 @@ def test_cli_demultiplexing_fasta_bins_fastq_short_files(tmp_path, monkeypatch):
         def resolve(args):
             args = real(args)
             if fasta_bins:
-                args.demux_files = [[p.replace(".fastq.gz", ".fa.gz") for p in pair] for pair in args.demux_files]
+                args.outputs = args.outputs.with_rank_names({
+                    key: [p.replace(".fastq.gz", ".fa.gz") for p in pair]
+                    for key, pair in args.outputs.rank_groups().items() if key.startswith("demux_files:")})
             return args
 
         monkeypatch.setattr(cli, "resolve_args", resolve)

@@ -10,6 +10,7 @@ import pytest
 
 from cutseq_amd import abi, capi, fastq, plan as planmod, report, run, textio
 from cutseq_amd.common import BUILDIN_ADAPTERS
+from cutseq_amd.outputs import OutputLayout
 
 import interleave_rule
 
@@ -152,15 +153,13 @@ def test_dry_run_prints_the_paired_steps(capsys, caplog):
 # ---- the output files' groups and formats, the report ----------------------------------------------------------
 
 def test_one_name_per_class_and_no_swap():
-    args = SimpleNamespace(output_file=["t.fq"], short_file=["s.fa"], untrimmed_file=[None], too_long_file=["l.fq.gz"],
-                           interleaved_out=True)
+    args = SimpleNamespace(outputs=OutputLayout.of(["t.fq"], ["s.fa"], [None], ["l.fq.gz"], paired=True, interleaved_out=True))
     for swap in (False, True):  # (paired --auto-rc on a '-' library: the device leads with mate 2 instead)
         assert textio.output_name_groups(args, True, swap, 0) == [["t.fq"], ["s.fa"], [None], ["l.fq.gz"]]
     groups = textio.output_name_groups(args, True, False, 0)
     # one file, one format: both mates' bits of the class
     assert textio.output_formats([g * 2 for g in groups], has_qualities=True) == 0b1100
-    args.interleaved_out = False
-    args.output_file, args.short_file, args.untrimmed_file, args.too_long_file = ["a", "b"], ["c", "d"], [None, None], None
+    args.outputs = OutputLayout.of(["a", "b"], ["c", "d"], [None, None], None, paired=True)
     assert textio.output_name_groups(args, True, True, 0) == [["b", "a"], ["c", "d"], [None, None]]
 
 

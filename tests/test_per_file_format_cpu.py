@@ -11,6 +11,7 @@ from pathlib import Path
 import pytest
 
 from cutseq_amd import abi, fastq, ranks, textio
+from cutseq_amd.outputs import OutputLayout
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -125,8 +126,8 @@ def test_run_text_pipeline_swaps_before_it_asks(monkeypatch, tmp_path):
 
     for swap in (False, True):
         Plan.swap_outputs = swap
-        args = argparse.Namespace(input_file=ins, output_file=["t1.fq", "t2.fa"], short_file=["s1.fa", "s2.fq"],
-                                  untrimmed_file=[None, None])
+        args = argparse.Namespace(input_file=ins, outputs=OutputLayout.of(["t1.fq", "t2.fa"], ["s1.fa", "s2.fq"], [None, None],
+                                                                          paired=True))
         with pytest.raises(Stop):
             textio.run_text_pipeline(args, Plan, [0], 1000)
         assert seen["q"] is True
@@ -138,8 +139,8 @@ def test_run_text_pipeline_swaps_before_it_asks(monkeypatch, tmp_path):
         barcodes = ["ACGT", "TGCA"]
 
     Plan.demux, Plan.swap_outputs = Demux, False
-    args = argparse.Namespace(input_file=ins, output_file=[None, None], short_file=["s1.fa", "s2.fa"],
-                              untrimmed_file=[None, None])
+    args = argparse.Namespace(input_file=ins, outputs=OutputLayout.of([None, None], ["s1.fa", "s2.fa"], [None, None],
+                                                                      barcodes={"": [None, None]}, paired=True))
     with pytest.raises(Stop):
         textio.run_text_pipeline(args, Plan, [0], 1000)
     assert seen["groups"] == [[None, None], ["s1.fa", "s2.fa"], [None, None], [None, None]]

@@ -13,6 +13,7 @@ import pytest
 
 from cutseq_amd import abi, capi, fastq, plan as planmod, ranks, report, run, textio
 from cutseq_amd.common import BUILDIN_ADAPTERS
+from cutseq_amd.outputs import OutputLayout
 
 import filters_rule
 import toolong_rule
@@ -87,7 +88,8 @@ def _names(paired=True, **kw):
     base = dict(output_file=["t1.fq", "t2.fq"][:mates], short_file=["s1.fq", "s2.fq"][:mates],
                 untrimmed_file=[None, None][:mates], too_long_file=None)
     base.update(kw)
-    return SimpleNamespace(**base)
+    layout = OutputLayout.of(base["output_file"], base["short_file"], base["untrimmed_file"], base["too_long_file"], paired=paired)
+    return SimpleNamespace(outputs=layout)
 
 
 def test_output_name_groups_gain_a_fourth_group_that_is_never_swapped():
