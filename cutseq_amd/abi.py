@@ -14,7 +14,7 @@ CS_MAX_STRIDE = 1536
 CS_LEN_SKIP = 0xFFFF
 CS_MAX_READ = 1 << 24
 
-CS_OP_ADAPTER, CS_OP_CUT, CS_OP_QTRIM, CS_OP_DEMUX, CS_OP_NTRIM, CS_OP_NEXTSEQ = 1, 2, 3, 4, 5, 6
+CS_OP_ADAPTER, CS_OP_CUT, CS_OP_QTRIM, CS_OP_DEMUX, CS_OP_NTRIM, CS_OP_NEXTSEQ, CS_OP_SHORTEN = 1, 2, 3, 4, 5, 6, 7
 # cutoff + base of a quality-trimming op: CS_OP_QTRIM is clamped to this range, CS_OP_NEXTSEQ refused outside it
 CS_Q_SUM_LOW, CS_Q_SUM_HIGH = -1, 256
 CS_DEMUX_NONE = 0xFF
@@ -55,7 +55,14 @@ CS_OK = 0
 CS_ERR_ARG, CS_ERR_HIP, CS_ERR_NO_GPU, CS_ERR_NOMEM, CS_ERR_STATE = -1, -2, -3, -4, -5
 
 
+class _cs_op_seq(C.Union):
+    """cs_op's anonymous union: an adapter's bases, or CS_OP_SHORTEN's length in their first four bytes."""
+
+    _fields_ = [("seq", C.c_uint8 * CS_MAX_ADAPTER), ("length", C.c_int32)]
+
+
 class cs_op(C.Structure):
+    _anonymous_ = ("_seq",)
     _fields_ = [
         ("kind", C.c_uint8),
         ("align_flags", C.c_uint8),
@@ -75,7 +82,7 @@ class cs_op(C.Structure):
         ("cut_len", C.c_int16),
         ("force_min_len", C.c_uint16),
         ("q_cutoff", C.c_int16),
-        ("seq", C.c_uint8 * CS_MAX_ADAPTER),
+        ("_seq", _cs_op_seq),
         ("thr", C.c_uint8 * (CS_MAX_ADAPTER + 1)),
         ("_pad", C.c_uint8 * 1),
         ("q_cutoff_front", C.c_int16),
@@ -183,6 +190,7 @@ class cs_text_result(C.Structure):
 
 assert C.sizeof(cs_text_params) == 48 and C.sizeof(cs_text_result) == 176
 assert C.sizeof(cs_op) == 284 and cs_op.q_cutoff_front.offset == 282, C.sizeof(cs_op)
+assert cs_op.seq.offset == 24 and cs_op.length.offset == 24 and cs_op.thr.offset == 152
 assert C.sizeof(cs_result) == 8
 assert C.sizeof(cs_cap2) == 4
 assert C.sizeof(cs_params) == 32

@@ -136,6 +136,7 @@ struct cs_engine {
   uint32_t filters = 0;  // CS_X_* bits of the plan's filters (cs_plan_set_max_length / _max_n / _max_ee)
   bool ends = false;     // some CS_OP_QTRIM op has a front cutoff, or the plan has a CS_OP_NTRIM op (FILT_ENDS kernels)
   bool nextseq = false;  // the plan has a CS_OP_NEXTSEQ op: `ends` is set too (the ENDS walks), tile kernels FILT_NEXTSEQ
+  bool shorten = false;  // the plan has a CS_OP_SHORTEN op: `ends` is set too (the ENDS walks), tile kernels FILT_SHORTEN
   int n_cus = 256;
   uint32_t n_table_ops = 1;
   uint32_t col_dwords = 0;   // per-wave DP scratch the plan needs (resolve kernel)
@@ -171,6 +172,7 @@ void sync_fields(csdev::DevOp &d) {
   f.match_flag = o.match_flag, f.required = o.required, f.conditional = o.conditional, f.capture = o.capture;
   f.homopolymer = o.homopolymer, f.q_base = o.q_base, f.stat_slot = o.stat_slot, f.m = o.m, f.k = o.k;
   f.min_overlap = o.min_overlap, f.force_min_len = o.force_min_len, f.cut_len = o.cut_len, f.q_cutoff = o.q_cutoff;
+  f.length = o.kind == CS_OP_SHORTEN ? o.length : 0;  // (the field shares its bytes with an adapter's bases)
 }
 
 int build_dev_op(const cs_op &in, csdev::DevOp &out, int index, int mate) {
@@ -254,6 +256,11 @@ int build_dev_op(const cs_op &in, csdev::DevOp &out, int index, int mate) {
     }
     case CS_OP_NTRIM:
       break;
+    case CS_OP_SHORTEN:
+      // Every int32 is a length (include/cutseq_hip.h).  Nothing to refuse, and no test here that negates the field: the
+      // kernels form |length| as 0u - (uint32_t)length, which is 2^31 for INT32_MIN, and take the minimum with n unsigned.
+      static_assert(sizeof(op.length) == 4 && offsetof(cs_op, length) == offsetof(cs_op, seq), "cs_op: length overlays seq");
+      break;
     case CS_OP_NEXTSEQ: {
       // No clamp here: a 'G' adds +1 whatever the cutoff, so the terms never all have one sign and a clamped cutoff
       // changes results (include/cutseq_hip.h).  Inside the range CS_OP_QTRIM is clamped to, every term is within
@@ -294,6 +301,7 @@ const void *kernel_variant(const cs_engine *eng) {
 }
 template <int MODE>
 const void *kernel_of(const cs_engine *eng) {  // plans with filters take the kernels that decide them
+  if (eng->shorten) return kernel_variant<MODE, csdev::FILT_SHORTEN>(eng);  // (every read-end op's code plus CS_OP_SHORTEN)
   if (eng->nextseq) return kernel_variant<MODE, csdev::FILT_NEXTSEQ>(eng);  // (the read-end ops' code plus CS_OP_NEXTSEQ)
   if (eng->ends) return kernel_variant<MODE, csdev::FILT_ENDS>(eng);  // (... and whatever filters the plan has)
   if (!eng->filters) return kernel_variant<MODE, csdev::FILT_NONE>(eng);
@@ -1011,9 +1019,11 @@ int cs_engine_create(const cs_plan *plan, int device, uint32_t n_slots, uint32_t
     for (int i = 0; i < plan->host.n_ops[mt]; ++i) {
       const csdev::DevOp &d = plan->host.ops[mt][i];
       if (d.op.kind == CS_OP_DEMUX) eng->demux_mate = mt;
-      if (d.op.kind == CS_OP_NTRIM || d.op.kind == CS_OP_NEXTSEQ || (d.op.kind == CS_OP_QTRIM && d.op.q_cutoff_front != 0))
+      if (d.op.kind == CS_OP_NTRIM || d.op.kind == CS_OP_NEXTSEQ || d.op.kind == CS_OP_SHORTEN ||
+          (d.op.kind == CS_OP_QTRIM && d.op.q_cutoff_front != 0))
         eng->ends = true;
       if (d.op.kind == CS_OP_NEXTSEQ) eng->nextseq = true;
+      if (d.op.kind == CS_OP_SHORTEN) eng->shorten = true;
       if (d.op.kind == CS_OP_DEMUX && d.filter_mode) {
         // the resolve kernel runs the barcodes' own ops, one column per lane
         has_long_demux = true;
@@ -1900,7 +1910,7 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
       la.plan_slot = (uint32_t)eng->plan_slot;
       la.mate = m;
       la.gate = &s.d_meta->err;
-      if (eng->ends)  // (a front cutoff or a CS_OP_NTRIM op: the walk that knows them, with every filter)
+      if (eng->ends)  // (a front cutoff, a CS_OP_NTRIM, _NEXTSEQ or _SHORTEN op: the walk that knows them, with every filter)
         hipLaunchKernelGGL((cslong::long_kernel<true, true>), dim3(256), dim3(64), 0, st, la);
       else if (eng->filters & (CS_X_TOO_LONG | CS_X_TOO_MANY_EE))
         hipLaunchKernelGGL(cslong::long_kernel<true>, dim3(256), dim3(64), 0, st, la);

@@ -257,7 +257,7 @@ struct Walk {  // a read on its way through the chain
 //   cut(op, off, c)            a cutter took c bases at off
 //   quality_trimmed(k)         the quality trimmer took k bases
 //   demux(d, v, seq, w)        a CS_OP_DEMUX op, the caller's to apply (Events::kDemux; compiled out where false)
-// ENDS: the instantiation for plans with a front cutoff, a CS_OP_NTRIM or a CS_OP_NEXTSEQ op (cs_engine::ends), the only
+// ENDS: the instantiation for plans with a front cutoff, a CS_OP_NTRIM, CS_OP_NEXTSEQ or CS_OP_SHORTEN op (cs_engine::ends), the only
 // one that holds their code; every other plan runs the walk it ran before they came.
 template <int kMaxM, bool ENDS, class Events>
 __device__ __forceinline__ Walk walk_chain(const DevPlan *plan, int mate, const Env &v, const uint8_t *seq, const uint8_t *qual,
@@ -325,6 +325,16 @@ __device__ __forceinline__ Walk walk_chain(const DevPlan *plan, int mate, const 
         if (stop < n) w.flags |= CS_F_QTRIMMED;
         ev.quality_trimmed(n - stop);
         w.e = w.s + stop;
+      }
+    } else if (op.kind == CS_OP_SHORTEN) {  // cutadapt's Shortener: min(n, |length|) bases stay, first or (< 0) last ones
+      if constexpr (ENDS) {
+        // 32 bits against 32 bits: intervals here exceed 16 bits, and |INT32_MIN| exists as an unsigned value only
+        const int32_t length = op.length;
+        const int keep = (int)min((uint32_t)n, length < 0 ? 0u - (uint32_t)length : (uint32_t)length);
+        if (length >= 0)
+          w.e = w.s + keep;
+        else
+          w.s = w.e - keep;
       }
     } else if (op.kind == CS_OP_NTRIM) {  // cutadapt's NEndTrimmer: the runs of 'N' (upper case only) at both ends
       if constexpr (ENDS) {

@@ -27,7 +27,8 @@
 //   CUT / conditional CUT: interval arithmetic on [s, e);  DEMUX: table look-up on the first m + k bases
 //   QTRIM: BWA running sum on packed (sum, position) keys; with a front cutoff (FILT_ENDS kernels only) a second,
 //          forward walk from the 5' end.  NTRIM (FILT_ENDS kernels only): the runs of 'N' at both ends of [s, e)
-//   NEXTSEQ (FILT_NEXTSEQ kernels only): QTRIM's 3' walk with the read's bases beside its qualities, a 'G' adds 1
+//   SHORTEN (FILT_SHORTEN kernels only): min(n, |length|) bases stay, from the 5' end or, length < 0, from the 3' end
+//   NEXTSEQ (FILT_NEXTSEQ kernels and above only): QTRIM's 3' walk with the read's bases beside its qualities, a 'G' adds 1
 //
 // No block-wide barrier is needed after staging.  Result: 8 bytes per read.  Integer work: no MFMA.
 
@@ -88,6 +89,7 @@ struct DevFields {
   uint32_t kind, align_flags, reversed, remove, shortcut, match_flag, required, conditional, capture, homopolymer,
       q_base, stat_slot, m, k, min_overlap, force_min_len;
   int32_t cut_len, q_cutoff;
+  int32_t length;  // CS_OP_SHORTEN (0 for every other kind); takes the four bytes DevOp padded in front of peq
 };
 
 struct DevOp {
@@ -2562,8 +2564,12 @@ enum { MODE_SCAN = 0, MODE_RESOLVE = 1 };
 // plans that hold one (cutadapt -q FRONT,BACK and --trim-n): their code exists in these instantiations alone; 4: FILT 3's
 // code plus CS_OP_NEXTSEQ (cutadapt --nextseq-trim), for the plans that hold that op.  It has a value of its own because
 // inside FILT 3 its walk cost the -q 20,20 --trim-n plan 1.1 % of its throughput, three times the spread of the parent's
-// own runs (profiles/nextseq_ab.log).
-enum { FILT_NONE = 0, FILT_MAXN = 1, FILT_ALL = 2, FILT_ENDS = 3, FILT_NEXTSEQ = 4 };
+// own runs (profiles/nextseq_ab.log); 5: FILT 4's code plus CS_OP_SHORTEN (cutadapt -l / -L), for the plans that hold that
+// op.  A value of its own although the op is four integer instructions: inside FILT 3 it changed the spill counts of 10
+// of the 16 FILT 3 / FILT 4 kernels (the coded wide scan kernel: 9 -> 11 spilled VGPRs; profiles/length_ab.log), and
+// the same kind of change cost the -q 20,20 --trim-n plan 1.1 % when CS_OP_NEXTSEQ was tried there.  Here every kernel a
+// plan without the op runs is the parent's, figure for figure.
+enum { FILT_NONE = 0, FILT_MAXN = 1, FILT_ALL = 2, FILT_ENDS = 3, FILT_NEXTSEQ = 4, FILT_SHORTEN = 5 };
 template <bool CODED, bool WIDE, int MODE, int FILT>
 __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) trim_kernel(KArgs a) {
   if (a.gate && *a.gate != ~0ull) return;  // (wave-uniform: one wave per block)
@@ -3547,7 +3553,7 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
       }
       CS_T_MARK(pt, 5);
     } else if (kind == CS_OP_NEXTSEQ) {
-      if constexpr (FILT == FILT_NEXTSEQ) {
+      if constexpr (FILT >= FILT_NEXTSEQ) {
         // cutadapt's NextseqQualityTrimmer (--nextseq-trim): the 3' walk of the CS_OP_QTRIM branch above with one more
         // input, the read's base at each position -- a 'G' adds 1 whatever its quality byte says.  The same top-dword
         // exact step, the same wave walk (four live reads, 16 lanes each), the same (sum, position) key; wherever a
@@ -3662,6 +3668,20 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
           if (stop < n) fm |= CS_F_QTRIMMED;
           qc += (uint32_t)(n - stop);
           e = s + stop;
+        }
+      }
+    } else if (kind == CS_OP_SHORTEN) {
+      if constexpr (FILT >= FILT_SHORTEN) {
+        // cutadapt's Shortener (-l / -L): min(n, |length|) bases stay, the first ones or, length < 0, the last ones.
+        // Lane-local; the length is wave-uniform (a scalar dword of the op).  |length| is formed unsigned -- 2^31 for
+        // INT32_MIN, which no int holds -- and n, never negative, is compared with it as such.  No flag, no counter.
+        const int length = op.length;
+        const int keep = (int)min((uint32_t)n, length < 0 ? 0u - (uint32_t)length : (uint32_t)length);
+        if (on) {
+          if (length >= 0)
+            e = s + keep;
+          else
+            s = e - keep;
         }
       }
     } else if (kind == CS_OP_NTRIM) {

@@ -3,7 +3,8 @@
 Counterpart of the modifier-list assembly in the reference's ``pipeline_single``
 (cutseq/run.py:326-426) and ``pipeline_paired`` (cutseq/run.py:533-731).  Where the
 reference instantiates cutadapt ``Modifier`` objects, this module emits plain
-descriptors (:class:`AdapterOp`, :class:`CutOp`, :class:`NextSeqTrimOp`, :class:`QTrimOp`, :class:`NTrimOp`) in the same order;
+descriptors (:class:`AdapterOp`, :class:`CutOp`, :class:`NextSeqTrimOp`, :class:`QTrimOp`,
+:class:`ShortenOp`, :class:`NTrimOp`) in the same order;
 ``TrimPlan.pack()`` turns them into the ``cs_op`` POD table of ``include/cutseq_hip.h``.
 Header work (SuffixRemover, Renamer) stays on the host and is described by
 ``MateChain.name_suffixes`` / ``TrimPlan.has_umi``.
@@ -61,6 +62,10 @@ class CutadaptConfig:
         self.nextseq_trim = None
         self.min_quality_r2 = None
         self.min_quality_front_r2 = None
+        # cutadapt -l / --length LENGTH: a Shortener behind the quality trimmer of every mate, in front of --trim-n's
+        # op (None = off); -L LENGTH: mate 2's own length (None = it follows -l; -L alone shortens mate 2 only)
+        self.length = None
+        self.length_r2 = None
 
 
 @dataclass
@@ -156,6 +161,17 @@ class NextSeqTrimOp:
 
 
 @dataclass
+class ShortenOp:
+    """cutadapt's ``Shortener(length)`` (``-l`` / ``-L``): ``read[:length]``, or ``read[length:]`` for a negative length
+    (CS_OP_SHORTEN)."""
+
+    length: int
+
+    def __repr__(self):
+        return f"Shortener(length={self.length})"
+
+
+@dataclass
 class NTrimOp:
     """cutadapt's ``NEndTrimmer()`` (``--trim-n``): the runs of upper-case ``N`` at both ends of the read go."""
 
@@ -215,7 +231,7 @@ class DemuxOp:
                 f"max_error_rate={self.max_error_rate}))")
 
 
-Op = Union[AdapterOp, CutOp, QTrimOp, DemuxOp, NTrimOp, NextSeqTrimOp]
+Op = Union[AdapterOp, CutOp, QTrimOp, DemuxOp, NTrimOp, NextSeqTrimOp, ShortenOp]
 
 
 def info_adapter_names(ops: Sequence["Op"]) -> dict:
@@ -360,6 +376,11 @@ def pack_ops(ops: Sequence[Op], limit: int = abi.CS_MAX_OPS):
             c.q_base = op.base
         elif isinstance(op, NTrimOp):
             c.kind = abi.CS_OP_NTRIM
+        elif isinstance(op, ShortenOp):  # (every int32 is a length: nothing is clamped, nothing refused below)
+            c.kind = abi.CS_OP_SHORTEN
+            if not -2 ** 31 <= op.length < 2 ** 31:
+                raise ValueError("shorten length out of range")
+            c.length = op.length
         elif isinstance(op, NextSeqTrimOp):  # (no clamp: cs_plan_create refuses what the kernels' sums cannot hold)
             c.kind = abi.CS_OP_NEXTSEQ
             c.q_cutoff = max(-0x8000, min(int(op.cutoff), 0x7FFF))
@@ -481,6 +502,8 @@ def compile_single(barcode: BarcodeConfig, settings: CutadaptConfig, untrimmed_r
     if getattr(settings, "nextseq_trim", None) is not None:
         ops.append(NextSeqTrimOp(settings.nextseq_trim))
     ops.append(QTrimOp(settings.min_quality, cutoff_front=getattr(settings, "min_quality_front", 0)))
+    if getattr(settings, "length", None) is not None:  # (cutadapt's order: Shortener, then NEndTrimmer)
+        ops.append(ShortenOp(settings.length))
     if getattr(settings, "trim_n", False):  # (cutadapt puts --trim-n behind the adapter work; here: behind step 8)
         ops.append(NTrimOp())
     # step 9
@@ -574,6 +597,11 @@ def compile_paired(barcode: BarcodeConfig, settings: CutadaptConfig, untrimmed_r
         o2.append(QTrimOp(settings.min_quality_r2, cutoff_front=getattr(settings, "min_quality_front_r2", None) or 0))
     else:
         o2.append(QTrimOp(settings.min_quality, cutoff_front=front))
+    length, length_r2 = getattr(settings, "length", None), getattr(settings, "length_r2", None)
+    if length is not None:
+        o1.append(ShortenOp(length))
+    if length_r2 is not None or length is not None:  # -L: mate 2's own length; without it mate 2 follows -l
+        o2.append(ShortenOp(length_r2 if length_r2 is not None else length))
     if getattr(settings, "trim_n", False):
         o1.append(NTrimOp())
         o2.append(NTrimOp())

@@ -12,6 +12,7 @@ ordered write-back).  ``-t/--threads`` bounds the host thread pool that parses, 
 from __future__ import annotations
 
 import argparse
+import itertools
 import logging
 import os
 import re
@@ -65,6 +66,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "of -q's: the same walk with this cutoff, in which a G counts as a base of quality CUTOFF - 1 "
                         "whatever its quality value says (the dark cycles of two-colour instruments read as high-quality "
                         "G). Needs an input with qualities.")
+    p.add_argument("-l", "--length", type=int, default=None, metavar="LENGTH",
+                   help="Extension (cutadapt's option): shorten reads to LENGTH bases, behind adapter and quality "
+                        "trimming and in front of --trim-n and the filters. A positive value keeps the first LENGTH "
+                        "bases, a negative one the last. Applies to both reads of a pair unless -L is given.")
+    p.add_argument("-L", dest="length_r2", type=int, default=None, metavar="LENGTH",
+                   help="Extension (cutadapt's option): shorten the second read of a pair to LENGTH, in the form -l "
+                        "takes. (Default: the second read follows -l)")
     p.add_argument("-m", "--min-length", type=int, default=20,
                    help="Minimum length of reads to keep after trimming. (Default: 20)")
     p.add_argument("--with-rname-suffix", action="store_true",
@@ -219,6 +227,11 @@ def resolve_args(args):
     interleaved_in, interleaved_out = resolve_interleaved(args, inputs)
     if args.min_quality_r2 is not None and len(inputs) == 1 and not interleaved_in:
         _fail("-Q sets the quality cutoff of the second read: it needs two input files.")
+    if args.length_r2 is not None and len(inputs) == 1 and not interleaved_in:
+        _fail("-L shortens the second read: it needs two input files, or one with --interleaved.")
+    for option, value in (("-l/--length", args.length), ("-L", args.length_r2)):
+        if value is not None and not -2 ** 31 <= value < 2 ** 31:
+            _fail(f"{option}: the length must fit 32 bits (got {value}).")
     if args.info_file:
         if args.demux_barcodes:
             _fail("--info-file cannot be combined with --demux-barcodes: the table form of the demultiplexing op has "
@@ -269,6 +282,8 @@ def settings_from_args(args) -> CutadaptConfig:
     st.nextseq_trim = args.nextseq_trim
     st.min_quality_r2 = args.min_quality_r2
     st.min_quality_front_r2 = args.min_quality_front_r2
+    st.length = args.length
+    st.length_r2 = args.length_r2
     st.dry_run = args.dry_run
     st.auto_rc = args.auto_rc
     st.json_file = args.json_file
@@ -294,7 +309,8 @@ def dry_run_steps(tp: TrimPlan) -> List[str]:
     poly-A, quality trimming (and the single-end reverse complement).  The text of a step is this build's own
     (cutadapt's ``repr``s are not available here); the ORDER is the reference's."""
     if tp.paired:
-        steps = [f"({a}, {b})" for a, b in zip(tp.r1.describe(), tp.r2.describe())]
+        # (-L without -l: mate 2's chain ends one step behind mate 1's, which has None there)
+        steps = [f"({a}, {b})" for a, b in itertools.zip_longest(tp.r1.describe(), tp.r2.describe(), fillvalue="None")]
         renamer = f"PairedEndRenamer({'{id}_{r1.cut_prefix}{r2.cut_prefix}' if tp.has_umi else '{id}'!r})"
     else:
         steps = list(tp.r1.describe())

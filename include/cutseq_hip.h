@@ -50,7 +50,9 @@ typedef enum cs_status {
 
 /* ---- op table: what cutseq/run.py:305-433 (single) and :493-731 (paired) compile -- */
 
-enum { CS_OP_ADAPTER = 1, CS_OP_CUT = 2, CS_OP_QTRIM = 3, CS_OP_DEMUX = 4, CS_OP_NTRIM = 5, CS_OP_NEXTSEQ = 6 };
+enum {
+  CS_OP_ADAPTER = 1, CS_OP_CUT = 2, CS_OP_QTRIM = 3, CS_OP_DEMUX = 4, CS_OP_NTRIM = 5, CS_OP_NEXTSEQ = 6, CS_OP_SHORTEN = 7
+};
 
 /* CS_OP_QTRIM -- cutadapt's QualityTrimmer(cutoff_front, cutoff_back, base), quality_trim_index on the interval [s, e)
  * the op sees (n = e - s, qualities q[0..n)):
@@ -83,7 +85,18 @@ enum { CS_OP_ADAPTER = 1, CS_OP_CUT = 2, CS_OP_QTRIM = 3, CS_OP_DEMUX = 4, CS_OP
  * -34 (stop 0).  cs_plan_create refuses an op with q_cutoff + q_base outside [-1, 256] (CS_ERR_ARG); inside, every term
  * is within the bound CS_OP_QTRIM's sums are built for.  A plan with the op runs the read-end instantiations of the
  * long-read and info kernels and tile kernels that hold the read-end modifiers' code and this op's; every other plan
- * the kernels it ran before (cutadapt's order: this op in front of the chain's CS_OP_QTRIM). */
+ * the kernels it ran before (cutadapt's order: this op in front of the chain's CS_OP_QTRIM).
+ *
+ * CS_OP_SHORTEN -- cutadapt's Shortener(length) (-l / --length, -L for read 2); one field, `length` (int32), on the
+ * interval [s, e) the op sees (n = e - s):
+ *     length >= 0:  e = s + min(n, length)        read[:length]; length 0 leaves [s, s)
+ *     length <  0:  s = e - min(n, |length|)      read[length:]: the last |length| bases stay
+ * Every int32 is a valid length, INT32_MIN included: |length| is formed as an unsigned 32-bit value and compared with n
+ * as such, never negated as an int.  No counter and no flag of its own (cutadapt has none): out_bp, TooShort, the
+ * filters and the info table's final read see the result; qualtrim_bp and CS_F_QTRIMMED do not change.  cutadapt's order:
+ * behind the chain's CS_OP_QTRIM, in front of its CS_OP_NTRIM.  A plan with the op runs the read-end instantiations of the
+ * long-read and info kernels and tile kernels of its own, which hold all the read-end ops' code and this op's; every
+ * other plan the kernels it ran before. */
 
 /* CS_OP_DEMUX -- extension, not a reference capability (BASELINE.json config 5): ONE pass
  * decides which of up to 255 equally long inline barcodes starts the read, where the reference would
@@ -178,7 +191,10 @@ typedef struct cs_op {
   int16_t cut_len;       /* CUT: >0 from the 5' end, <0 from the 3' end               */
   uint16_t force_min_len;/* CUT (conditional): force_trim_min_length                  */
   int16_t q_cutoff;      /* QTRIM: cutoff_back (3' end); cutoff_front: q_cutoff_front below */
-  uint8_t seq[CS_MAX_ADAPTER];     /* ADAPTER: upper-cased bases                      */
+  union {                          /* (offset 24: the int32 shares the first bytes of a field only adapters use) */
+    uint8_t seq[CS_MAX_ADAPTER];   /* ADAPTER: upper-cased bases                      */
+    int32_t length;                /* SHORTEN: >= 0 keep the first `length` bases, < 0 the last |length| */
+  };
   uint8_t thr[CS_MAX_ADAPTER + 1]; /* ADAPTER: thr[L] = floor(L * max_error_rate) in IEEE double */
   uint8_t _pad[1];
   int16_t q_cutoff_front; /* QTRIM: cutoff_front (5' end); 0 = the reference's op, no front walk (carved out of the

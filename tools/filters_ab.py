@@ -17,6 +17,12 @@ quality trimmer of both mates.  --only LEG[,LEG]: these legs alone (an A/B of tw
 CUTSEQ_HIP_LIB choosing the library).
 
   python tools/filters_ab.py --nextseq [--cutoff 20]
+
+--shorten: the cost of -l LENGTH: the plan without it against the plan with a ShortenOp behind the quality trimmer of
+both mates.  Without --length the median final length of a sample of the same reads (both mates, the plan without the
+op) is taken and printed.
+
+  python tools/filters_ab.py --shorten [--length N] [--sample 1000000]
 """
 from __future__ import annotations
 
@@ -52,7 +58,24 @@ def plan_for(filters):
         if filters.get("nextseq") is not None:  # immediately in front of the chain's quality trimmer
             at = next(i for i, o in enumerate(chain.ops) if isinstance(o, planmod.QTrimOp))
             chain.ops = chain.ops[:at] + [planmod.NextSeqTrimOp(filters["nextseq"])] + chain.ops[at:]
+        if filters.get("shorten") is not None:  # directly behind the chain's quality trimmer, in front of an N trimmer
+            at = next(i for i, o in enumerate(chain.ops) if isinstance(o, planmod.QTrimOp))
+            chain.ops = chain.ops[:at + 1] + [planmod.ShortenOp(filters["shorten"])] + chain.ops[at + 1:]
     return tp
+
+
+def median_final_length(d, n, stride):
+    """Of the first n pairs: the median length of what the plan without the op leaves (both mates together)."""
+    import numpy as np
+    dev = torch.device("cuda:0")
+    outs = [torch.empty((n, 8), dtype=torch.uint8, device=dev) for _ in range(2)]
+    rr = [abi.cs_reads(d[f"seq{m}"].data_ptr(), d[f"qual{m}"].data_ptr(), d[f"len{m}"].data_ptr(), outs[m - 1].data_ptr(),
+                       None, None, None) for m in (1, 2)]
+    with TrimEngine(plan_for({}), device=0, slots=0) as eng:
+        eng.trim_device(rr[0], rr[1], n, stride)
+        torch.cuda.synchronize(dev)
+    res = [o.cpu().numpy().view(abi.RESULT_DTYPE).reshape(-1) for o in outs]
+    return int(np.median(np.concatenate([r["stop"].astype(np.int64) - r["start"].astype(np.int64) for r in res])))
 
 
 def front_walk_share(d, n, stride, front, base=33):
@@ -133,9 +156,11 @@ def main():
     ap.add_argument("--xflags", action="store_true", help="also write cs_reads.xflags (the text path does)")
     ap.add_argument("--ends", action="store_true", help="the legs of -q FRONT,20 and --trim-n instead of the filters'")
     ap.add_argument("--front", type=int, default=20, help="--ends: the 5' cutoff")
-    ap.add_argument("--sample", type=int, default=1_000_000, help="--ends: pairs the front-walk share is counted on")
+    ap.add_argument("--sample", type=int, default=1_000_000, help="--ends / --shorten: pairs the front-walk share / the median length is counted on")
     ap.add_argument("--nextseq", action="store_true", help="the legs of --nextseq-trim instead of the filters'")
     ap.add_argument("--cutoff", type=int, default=20, help="--nextseq: the cutoff")
+    ap.add_argument("--shorten", action="store_true", help="the legs of -l LENGTH instead of the filters'")
+    ap.add_argument("--length", type=int, default=None, help="--shorten: the length (default: the median final length)")
     ap.add_argument("--only", type=str, default=None, help="run these legs alone (comma-separated)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -157,6 +182,12 @@ def main():
                           "sample_pairs": min(n, args.sample)}), flush=True)
     if args.nextseq:
         legs = (("off", {}), ("nextseq", {"nextseq": args.cutoff}))
+    if args.shorten:
+        length = args.length
+        if length is None:
+            length = median_final_length(d, min(n, args.sample), stride)
+            print(json.dumps({"median_final_length": length, "sample_pairs": min(n, args.sample)}), flush=True)
+        legs = (("off", {}), ("shorten", {"shorten": length}))
     if args.only:
         legs = tuple(leg_ for leg_ in legs if leg_[0] in args.only.split(","))
     res = {key: [] for key, _ in legs}

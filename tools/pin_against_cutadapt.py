@@ -179,6 +179,11 @@ def build_chain(barcode, settings, paired: bool, untrimmed_requested: bool = Fal
     q2 = _get(settings, "min_quality_r2", None)  # (-Q: read 2's own cutoffs, both of them)
     second = (qf, q) if q2 is None else (_get(settings, "min_quality_front_r2", None) or 0, q2)
     each(M.QualityTrimmer(cutoff_front=qf, cutoff_back=q), M.QualityTrimmer(cutoff_front=second[0], cutoff_back=second[1]))
+    ln, ln2 = _get(settings, "length", None), _get(settings, "length_r2", None)
+    if ln is not None:  # -l / -L: cutadapt's order, Shortener behind the quality trimmers and in front of NEndTrimmer
+        each(M.Shortener(ln), M.Shortener(ln if ln2 is None else ln2))
+    elif ln2 is not None:
+        raise NotImplementedError("-L without -l: the mates' modifier lists differ in length")
     if _get(settings, "trim_n", False):  # --trim-n: behind the quality trimmer, as cutseq_amd.plan compiles it
         each(M.NEndTrimmer(), M.NEndTrimmer())
     # step 9
@@ -314,7 +319,8 @@ def collect_cases(n_synth: int = 2000):
     # read 2's own cutoffs, --nextseq-trim and -Q -- recalled rules)
     for flags in ({}, {"trim_polyA": True}, {"min_quality_front": 15, "min_quality": 10},
                   {"min_quality_front": 20, "trim_n": True}, {"nextseq_trim": 20},
-                  {"nextseq_trim": 10, "min_quality": 25, "min_quality_r2": 5, "min_quality_front_r2": 3, "trim_n": True}):
+                  {"nextseq_trim": 10, "min_quality": 25, "min_quality_r2": 5, "min_quality_front_r2": 3, "trim_n": True},
+                  {"length": 30, "length_r2": -25, "trim_n": True}):  # (Shortener, -l / -L: recalled too)
         cases.append(chain_case(f"fixture10k/TAKARAV3/{sorted(flags)}", BUILDIN_ADAPTERS["TAKARAV3"], flags, True,
                                 {"fixture": "fixture10k"}, rec1, rec2))
     for idx, (name, flags, paired) in enumerate(CHAIN_CASES):
