@@ -152,6 +152,15 @@ CS_TEXT_OK, CS_TEXT_ERR_MALFORMED, CS_TEXT_ERR_TOO_LONG, CS_TEXT_ERR_IDS_DIFFER,
 CS_TEXT_ERR_INFO_MISMATCH, CS_TEXT_ERR_INFO_OVERFLOW = 5, 6
 CS_INFO_ON, CS_INFO_GZIP, CS_INFO_NO_QUAL = 1, 2, 4  # cs_text_params.info
 CS_INTERLEAVE_IN, CS_INTERLEAVE_OUT, CS_INTERLEAVE_OUT_MATE2_FIRST = 1, 2, 4  # cs_text_create_interleaved
+# cs_text_set_rename: segment kinds, the "written mate's own" capture, the table's limits
+(CS_RENAME_LITERAL, CS_RENAME_HEADER, CS_RENAME_ID, CS_RENAME_COMMENT, CS_RENAME_CAPTURE, CS_RENAME_CAPTURE2,
+ CS_RENAME_MATE) = range(7)
+CS_RENAME_OWN = 2
+CS_RENAME_MAX_SEGMENTS, CS_RENAME_MAX_LITERAL, CS_RENAME_MAX_HEADER = 16, 255, 4
+
+
+class cs_rename_seg(C.Structure):
+    _fields_ = [("kind", C.c_uint8), ("mate", C.c_uint8), ("lit_off", C.c_uint8), ("lit_len", C.c_uint8)]
 
 
 class cs_text_params(C.Structure):
@@ -188,7 +197,7 @@ class cs_text_result(C.Structure):
     ]
 
 
-assert C.sizeof(cs_text_params) == 48 and C.sizeof(cs_text_result) == 176
+assert C.sizeof(cs_text_params) == 48 and C.sizeof(cs_text_result) == 176 and C.sizeof(cs_rename_seg) == 4
 assert C.sizeof(cs_op) == 284 and cs_op.q_cutoff_front.offset == 282, C.sizeof(cs_op)
 assert cs_op.seq.offset == 24 and cs_op.length.offset == 24 and cs_op.thr.offset == 152
 assert C.sizeof(cs_result) == 8

@@ -20,7 +20,7 @@ EXPORTS = (
     "cs_stats_fetch", "cs_last_kernel_ms", "cs_last_kernel_split_ms", "cs_kernel_time_totals", "cs_alloc_pinned", "cs_alloc_pinned_huge", "cs_free_pinned", "cs_alloc_device",
     "cs_free_device", "cs_copy_to_device", "cs_copy_to_host",
     "cs_text_create", "cs_text_destroy", "cs_text_submit", "cs_text_wait", "cs_text_routes", "cs_text_fetch",
-    "cs_text_info", "cs_text_fetch_info", "cs_text_create_interleaved",
+    "cs_text_info", "cs_text_fetch_info", "cs_text_create_interleaved", "cs_text_set_rename",
 )
 
 
@@ -120,6 +120,9 @@ def load() -> C.CDLL:
     if hasattr(L, "cs_text_create_interleaved"):  # (an older build loaded through CUTSEQ_HIP_LIB for an A/B has none)
         L.cs_text_create_interleaved.restype = i32
         L.cs_text_create_interleaved.argtypes = [vp, C.POINTER(abi.cs_text_params), u32, u32, u64, u32, u32, C.POINTER(vp)]
+    if hasattr(L, "cs_text_set_rename"):  # (likewise)
+        L.cs_text_set_rename.restype = i32
+        L.cs_text_set_rename.argtypes = [vp, C.POINTER(abi.cs_rename_seg), u32, C.c_char_p, u32]
     L.cs_text_destroy.restype = None
     L.cs_text_destroy.argtypes = [vp]
     L.cs_text_submit.restype = i32

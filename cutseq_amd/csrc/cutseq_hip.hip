@@ -1510,6 +1510,9 @@ struct cs_text {
   uint32_t interleave = 0;    // CS_INTERLEAVE_* (cs_text_create_interleaved): one text in / one stream per route out
   uint64_t info_cap = 0;      // bytes of a batch's info table at most
   uint32_t info_chunks = 0;   // ... and deflate chunks
+  bool renamed = false;       // cs_text_set_rename: the names come from `rename`, the format kernels take it
+  bool submitted = false;     // a batch has been submitted: the buffers keep their sizes from here on
+  cstext::RenameTable rename;
   hipStream_t h2d = nullptr, d2h = nullptr;
   std::vector<TextSlot> slots;
 };
@@ -1578,6 +1581,114 @@ struct Carver {
   }
 };
 
+// What a record name can add to a batch's output beyond the batch's own text: `per_record` bytes for every record --
+// the default name's '_' and captures (cs_text_params.max_tag), or a template's literals, captures and mate digits -- and
+// the whole text once more for every header-derived segment of a template (the default name's id is part of the text).
+struct NameBound {
+  uint64_t per_record = 0, header_copies = 0;
+};
+
+NameBound name_bound(uint32_t max_tag, const cstext::RenameTable *rn) {
+  NameBound b;
+  b.per_record = max_tag;
+  if (!rn) return b;
+  b.per_record = 0;
+  for (uint32_t i = 0; i < rn->n; ++i) {
+    const cs_rename_seg &sg = rn->seg[i];
+    if (sg.kind == CS_RENAME_LITERAL) b.per_record += sg.lit_len;
+    else if (sg.kind == CS_RENAME_CAPTURE || sg.kind == CS_RENAME_CAPTURE2) b.per_record += std::min(max_tag, 255u);  // (one capture <= all of them, and <= cap_len's 8 bits)
+    else if (sg.kind == CS_RENAME_MATE) b.per_record += 1u;
+    else ++b.header_copies;
+  }
+  return b;
+}
+
+// bytes of a mate's output buffer.  An interleaved output holds both mates' records: every record of the one text
+// (CS_INTERLEAVE_IN) or of the two
+uint64_t output_bound(uint32_t interleave, uint64_t max_text_bytes, uint32_t max_records, const NameBound &nb) {
+  const bool woven_in = (interleave & CS_INTERLEAVE_IN) != 0, woven_out = (interleave & CS_INTERLEAVE_OUT) != 0;
+  return (woven_out && !woven_in ? 2u : 1u) * (1u + nb.header_copies) * max_text_bytes +
+         (woven_out ? 2u : 1u) * (uint64_t)max_records * (nb.per_record + 8u) + 64u;
+}
+
+// Bytes of a batch's info table.  Every row shows its read once as bases and once as qualities next to the name, and a
+// record has at most one row per adapter op of mate 1's chain (one if there is none): rows <= the record's own text plus
+// what the name adds and 11 tabs, the line end, "errors rstart rstop name" in decimal (3 + 8 + 8 + 2 digits at most).
+uint64_t info_bound(const cs_engine *eng, uint64_t max_text_bytes, uint32_t max_records, const NameBound &nb) {
+  const uint64_t rows = eng->info_adapters ? eng->info_adapters : 1u;
+  return rows * ((1u + nb.header_copies) * max_text_bytes + (uint64_t)max_records * (nb.per_record + 40u)) + 64u;
+}
+
+// ONE device allocation per slot, carved up (a hundred separate hipMalloc calls cost a short run more than its
+// kernels): `carve` names every array once, and runs twice -- to measure, then over the allocation.
+// Its ORDER is a rule.  First the arrays that are zeroed: a batch that is rejected half-way leaves some of them
+// unwritten, and whatever a later kernel of that batch still reads through them must stay inside the allocations.
+// Then the "not a long read" markers, set to all ones for the same reason.  Then everything else.
+hipError_t alloc_slot_arena(cs_text *t, TextSlot &s) {
+  const cs_engine *eng = t->eng;
+  const bool woven_in = (t->interleave & CS_INTERLEAVE_IN) != 0, woven_out = (t->interleave & CS_INTERLEAVE_OUT) != 0;
+  const int mates = eng->paired ? 2 : 1;
+  const uint32_t max_records = t->max_records;
+  const size_t rows = (size_t)max_records * t->stride;
+  size_t zero_bytes = 0, ones_bytes = 0;
+  auto carve = [&](uint8_t *base) {
+    Carver c{base};
+    for (int m = 0; m < mates; ++m) {
+      // (an interleaved text: one index over both mates' lines, and no text or index of mate 2's own)
+      if (!woven_in) c.take(s.d_nl[m], (size_t)max_records * 4 + 8);
+      else if (m == 0) c.take(s.d_nl[m], (size_t)max_records * 8 + 8);
+      c.take(s.d_rec[m], max_records);
+      c.take(s.d_idr[m], max_records);
+    }
+    zero_bytes = c.at;
+    for (int m = 0; m < mates; ++m) c.take(s.d_long_of[m], max_records);
+    ones_bytes = c.at - zero_bytes;
+    for (int m = 0; m < mates; ++m) {
+      if (!woven_in || m == 0) c.take(s.d_text[m], t->max_text + 64);
+      c.take(s.d_seq[m], rows);
+      c.take(s.d_qual[m], rows);
+      c.take(s.d_len[m], max_records);
+      c.take(s.d_res[m], max_records);
+      c.take(s.d_dst[m], max_records);
+      // (an interleaved output: mate 1's buffer and deflate staging hold both mates, mate 2 has none)
+      if (!woven_out || m == 0) c.take(s.d_out[m], t->out_cap);
+      c.take(s.d_lrec[m], max_records);
+      c.take(s.d_lres[m], max_records);
+      if (t->compress && (!woven_out || m == 0)) c.take(s.gz[m], t->max_chunks);
+    }
+    if (woven_in) s.d_text[1] = s.d_text[0];
+    if (woven_out) s.d_out[1] = s.d_out[0];
+    if (t->needs_cap2) c.take(s.d_cap2, max_records);
+    c.take(s.d_blk, (size_t)2 * (t->seg_blocks + 1) + (size_t)2 * t->n_routes * (t->fmt_blocks + 1));
+    c.take(s.d_totals, 2 + 2 * (size_t)t->n_routes);
+    c.take(s.d_meta, 1);
+    if (t->tp.n_bins) c.take(s.d_bc, max_records);
+    if (t->route_block) c.take(s.d_routes, 1);
+    if (t->tp.filters)
+      for (int m = 0; m < mates; ++m) c.take(s.d_xf[m], max_records);
+    if (t->info) {
+      c.take(s.d_imatch, (size_t)max_records * (eng->info_adapters ? eng->info_adapters : 1u));
+      c.take(s.d_irec, max_records);
+      c.take(s.d_idst, max_records);
+      c.take(s.d_iblk, (size_t)t->fmt_blocks + 1);
+      c.take(s.d_itotal, 1);
+      c.take(s.d_info, t->info_cap);
+      c.take(s.d_imeta, 1);
+      if (t->info & CS_INFO_GZIP) c.take(s.info_gz, t->info_chunks);
+    }
+    return c.at;
+  };
+  hipError_t e = hipMalloc(&s.d_arena, carve(nullptr));
+  if (e != hipSuccess) {
+    s.d_arena = nullptr;
+    return e;
+  }
+  carve(s.d_arena);
+  e = hipMemsetAsync(s.d_arena, 0, zero_bytes, t->h2d);
+  if (e == hipSuccess) e = hipMemsetAsync(s.d_arena + zero_bytes, 0xff, ones_bytes, t->h2d);
+  return e;
+}
+
 void free_text(cs_text *t) {
   if (!t) return;
   if (t->eng) (void)hipSetDevice(t->eng->device);
@@ -1611,7 +1722,7 @@ int cs_text_create_interleaved(cs_engine *eng, const cs_text_params *params, uin
   if (!out) return fail(CS_ERR_ARG, "out is null");
   *out = nullptr;
   if (!eng || !params) return fail(CS_ERR_ARG, "null engine or params");
-  const bool woven_in = (interleave & CS_INTERLEAVE_IN) != 0, woven_out = (interleave & CS_INTERLEAVE_OUT) != 0;
+  const bool woven_out = (interleave & CS_INTERLEAVE_OUT) != 0;
   if (interleave & ~(uint32_t)(CS_INTERLEAVE_IN | CS_INTERLEAVE_OUT | CS_INTERLEAVE_OUT_MATE2_FIRST))
     return fail(CS_ERR_ARG, "interleave = 0x%x: CS_INTERLEAVE_IN, CS_INTERLEAVE_OUT [| CS_INTERLEAVE_OUT_MATE2_FIRST], or 0", interleave);
   if (interleave && !eng->paired) return fail(CS_ERR_ARG, "interleave = 0x%x on a single-end plan: there are no mates to weave", interleave);
@@ -1624,9 +1735,7 @@ int cs_text_create_interleaved(cs_engine *eng, const cs_text_params *params, uin
   if (!n_slots || !max_records || !max_text_bytes) return fail(CS_ERR_ARG, "slots, records and text bytes must be positive");
   if (stride == 0 || stride % 4 || stride > CS_MAX_STRIDE)
     return fail(CS_ERR_ARG, "stride %u must be a multiple of 4 in [4, %d]", stride, CS_MAX_STRIDE);
-  // an interleaved output holds both mates' records: every record of the one text (CS_INTERLEAVE_IN) or of the two
-  const uint64_t out_cap = (woven_out && !woven_in ? 2u : 1u) * max_text_bytes +
-                           (woven_out ? 2u : 1u) * (uint64_t)max_records * (params->max_tag + 8u) + 64u;
+  const uint64_t out_cap = output_bound(interleave, max_text_bytes, max_records, name_bound(params->max_tag, nullptr));
   if (max_text_bytes >= (1ull << 30) || out_cap >= (1ull << 30))
     return fail(CS_ERR_ARG, woven_out ? "a batch is limited to 1 GiB of interleaved output (%llu bytes of text per input requested)"
                                       : "a batch is limited to 1 GiB of text per mate (%llu requested)", (unsigned long long)max_text_bytes);
@@ -1709,12 +1818,8 @@ int cs_text_create_interleaved(cs_engine *eng, const cs_text_params *params, uin
       delete t;
       return fail(CS_ERR_ARG, "info: a plan with a demultiplexing op has no info table (its table form has no error count)");
     }
-    // Every row shows its read once as bases and once as qualities next to the name, and a record has at most one row
-    // per adapter op of mate 1's chain (one if there is none): rows <= the record's own text plus the UMI tag and
-    // 11 tabs, the line end, "errors rstart rstop name" in decimal (3 + 8 + 8 + 2 digits at most).
-    const uint64_t rows = eng->info_adapters ? eng->info_adapters : 1u;
     t->info = params->info;
-    t->info_cap = rows * (max_text_bytes + (uint64_t)max_records * (params->max_tag + 40u)) + 64u;
+    t->info_cap = info_bound(eng, max_text_bytes, max_records, name_bound(params->max_tag, nullptr));
     if (t->info_cap >= (1ull << 32)) {
       delete t;
       return fail(CS_ERR_ARG, "info: the table of a batch could reach %llu bytes (4 GiB at most): smaller blocks, please",
@@ -1760,66 +1865,8 @@ int cs_text_create_interleaved(cs_engine *eng, const cs_text_params *params, uin
   TXT_TRY(hipStreamCreateWithFlags(&t->h2d, hipStreamNonBlocking));
   TXT_TRY(hipStreamCreateWithFlags(&t->d2h, hipStreamNonBlocking));
   t->slots.resize(n_slots);
-  const int mates = eng->paired ? 2 : 1;
-  const size_t rows = (size_t)max_records * stride;
   for (TextSlot &s : t->slots) {
-    // ONE device allocation per slot, carved up (a hundred separate hipMalloc calls cost a short run more than its
-    // kernels): `carve` names every array once, and runs twice -- to measure, then over the allocation.
-    // Its ORDER is a rule.  First the arrays that are zeroed: a batch that is rejected half-way leaves some of them
-    // unwritten, and whatever a later kernel of that batch still reads through them must stay inside the allocations.
-    // Then the "not a long read" markers, set to all ones for the same reason.  Then everything else.
-    size_t zero_bytes = 0, ones_bytes = 0;
-    auto carve = [&](uint8_t *base) {
-      Carver c{base};
-      for (int m = 0; m < mates; ++m) {
-        // (an interleaved text: one index over both mates' lines, and no text or index of mate 2's own)
-        if (!woven_in) c.take(s.d_nl[m], (size_t)max_records * 4 + 8);
-        else if (m == 0) c.take(s.d_nl[m], (size_t)max_records * 8 + 8);
-        c.take(s.d_rec[m], max_records);
-        c.take(s.d_idr[m], max_records);
-      }
-      zero_bytes = c.at;
-      for (int m = 0; m < mates; ++m) c.take(s.d_long_of[m], max_records);
-      ones_bytes = c.at - zero_bytes;
-      for (int m = 0; m < mates; ++m) {
-        if (!woven_in || m == 0) c.take(s.d_text[m], max_text_bytes + 64);
-        c.take(s.d_seq[m], rows);
-        c.take(s.d_qual[m], rows);
-        c.take(s.d_len[m], max_records);
-        c.take(s.d_res[m], max_records);
-        c.take(s.d_dst[m], max_records);
-        // (an interleaved output: mate 1's buffer and deflate staging hold both mates, mate 2 has none)
-        if (!woven_out || m == 0) c.take(s.d_out[m], out_cap);
-        c.take(s.d_lrec[m], max_records);
-        c.take(s.d_lres[m], max_records);
-        if (t->compress && (!woven_out || m == 0)) c.take(s.gz[m], t->max_chunks);
-      }
-      if (woven_in) s.d_text[1] = s.d_text[0];
-      if (woven_out) s.d_out[1] = s.d_out[0];
-      if (t->needs_cap2) c.take(s.d_cap2, max_records);
-      c.take(s.d_blk, (size_t)2 * (t->seg_blocks + 1) + (size_t)2 * t->n_routes * (t->fmt_blocks + 1));
-      c.take(s.d_totals, 2 + 2 * (size_t)t->n_routes);
-      c.take(s.d_meta, 1);
-      if (t->tp.n_bins) c.take(s.d_bc, max_records);
-      if (t->route_block) c.take(s.d_routes, 1);
-      if (t->tp.filters)
-        for (int m = 0; m < mates; ++m) c.take(s.d_xf[m], max_records);
-      if (t->info) {
-        c.take(s.d_imatch, (size_t)max_records * (eng->info_adapters ? eng->info_adapters : 1u));
-        c.take(s.d_irec, max_records);
-        c.take(s.d_idst, max_records);
-        c.take(s.d_iblk, (size_t)t->fmt_blocks + 1);
-        c.take(s.d_itotal, 1);
-        c.take(s.d_info, t->info_cap);
-        c.take(s.d_imeta, 1);
-        if (t->info & CS_INFO_GZIP) c.take(s.info_gz, t->info_chunks);
-      }
-      return c.at;
-    };
-    TXT_TRY(hipMalloc(&s.d_arena, carve(nullptr)));
-    carve(s.d_arena);
-    TXT_TRY(hipMemsetAsync(s.d_arena, 0, zero_bytes, t->h2d));
-    TXT_TRY(hipMemsetAsync(s.d_arena + zero_bytes, 0xff, ones_bytes, t->h2d));
+    TXT_TRY(alloc_slot_arena(t, s));
     if (t->route_block) TXT_TRY(hipHostMalloc(&s.h_routes, sizeof(RouteBlock), hipHostMallocPortable));
     if (t->info) {
       TXT_TRY(hipHostMalloc(&s.h_imeta, sizeof(csinfo::InfoMeta), hipHostMallocPortable));
@@ -1839,6 +1886,63 @@ int cs_text_create_interleaved(cs_engine *eng, const cs_text_params *params, uin
   return CS_OK;
 }
 
+int cs_text_set_rename(cs_text *t, const cs_rename_seg *segments, uint32_t n, const char *literals, uint32_t n_bytes) {
+  if (!t || (n && !segments) || (n_bytes && !literals)) return fail(CS_ERR_ARG, "null text engine, segments or literals");
+  if (t->submitted) return fail(CS_ERR_ARG, "cs_text_set_rename comes before the first cs_text_submit: the buffers are sized for the names");
+  if (t->tp.n_bins) return fail(CS_ERR_ARG, "rename: the kernels of a plan with n_bins are not extended");
+  if (n > cstext::kRenameSegs) return fail(CS_ERR_ARG, "rename: %u segments (%u at most)", n, cstext::kRenameSegs);
+  if (n_bytes > cstext::kRenameLiteral) return fail(CS_ERR_ARG, "rename: %u literal bytes (%u at most)", n_bytes, cstext::kRenameLiteral);
+  cstext::RenameTable rn;
+  memset(&rn, 0, sizeof rn);
+  rn.n = n;
+  uint32_t literal = 0, headers = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const cs_rename_seg sg = segments[i];
+    if (sg.kind > CS_RENAME_MATE) return fail(CS_ERR_ARG, "rename: segment %u has kind %u", i, sg.kind);
+    if (sg.kind == CS_RENAME_LITERAL) {
+      if ((uint32_t)sg.lit_off + sg.lit_len > n_bytes) return fail(CS_ERR_ARG, "rename: segment %u reaches beyond the %u literal bytes", i, n_bytes);
+      literal += sg.lit_len;
+    }
+    if (sg.kind == CS_RENAME_HEADER || sg.kind == CS_RENAME_ID || sg.kind == CS_RENAME_COMMENT) ++headers;
+    if (sg.kind == CS_RENAME_CAPTURE || sg.kind == CS_RENAME_CAPTURE2) {
+      if (sg.mate > CS_RENAME_OWN || (sg.mate == 1 && !t->eng->paired))
+        return fail(CS_ERR_ARG, "rename: segment %u names the capture of mate %u of a %s-end plan", i, sg.mate + 1u, t->eng->paired ? "paired" : "single");
+      if (sg.kind == CS_RENAME_CAPTURE2 && t->eng->paired)
+        return fail(CS_ERR_ARG, "rename: segment %u names a second capture, and the chains of a paired plan hold one each", i);
+    }
+    rn.seg[i] = sg;
+  }
+  if (literal > cstext::kRenameLiteral) return fail(CS_ERR_ARG, "rename: the literal segments sum to %u bytes (%u at most)", literal, cstext::kRenameLiteral);
+  if (headers > CS_RENAME_MAX_HEADER)
+    return fail(CS_ERR_ARG, "rename: %u segments copy from the header (%d at most: each can double a batch's output)", headers, CS_RENAME_MAX_HEADER);
+  if (n_bytes) memcpy(rn.lit, literals, n_bytes);
+  const NameBound nb = name_bound(t->max_tag, &rn);
+  const uint64_t out_cap = output_bound(t->interleave, t->max_text, t->max_records, nb);
+  const uint64_t info_cap = t->info ? info_bound(t->eng, t->max_text, t->max_records, nb) : 0;
+  if (out_cap >= (1ull << 30))
+    return fail(CS_ERR_ARG, "rename: a mate's output of a batch could reach %llu bytes with this template (1 GiB at most): smaller blocks, please",
+                (unsigned long long)out_cap);
+  if (info_cap >= (1ull << 32))
+    return fail(CS_ERR_ARG, "rename: the info table of a batch could reach %llu bytes with this template (4 GiB at most): smaller blocks, please",
+                (unsigned long long)info_cap);
+  HIP_TRY(hipSetDevice(t->eng->device));
+  t->rename = rn;
+  t->renamed = true;
+  t->out_cap = out_cap;
+  t->max_chunks = (uint32_t)((out_cap + csdefl::kChunk - 1) / csdefl::kChunk) + t->n_routes;
+  if (t->info) {
+    t->info_cap = info_cap;
+    t->info_chunks = (uint32_t)((info_cap + csdefl::kChunk - 1) / csdefl::kChunk) + 1u;
+  }
+  for (TextSlot &s : t->slots) {  // the same arrays over again, the output buffers at their new sizes
+    HIP_TRY(hipFree(s.d_arena));
+    s.d_arena = nullptr;
+    HIP_TRY(alloc_slot_arena(t, s));
+  }
+  HIP_TRY(hipStreamSynchronize(t->h2d));  // (the memsets, as in cs_text_create)
+  return CS_OK;
+}
+
 int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1, const void *text2, uint64_t bytes2,
                    uint32_t n_records) {
   if (!t || !text1) return fail(CS_ERR_ARG, "null text engine or text");
@@ -1852,6 +1956,7 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
                 (unsigned long long)bytes1, (unsigned long long)bytes2, t->max_records, (unsigned long long)t->max_text);
   TextSlot &s = t->slots[slot];
   if (s.busy) return fail(CS_ERR_STATE, "slot %u still in flight: cs_text_wait + cs_text_fetch first", slot);
+  if (!s.d_arena) return fail(CS_ERR_STATE, "slot %u has no buffers: cs_text_set_rename failed to allocate them", slot);
   HIP_TRY(hipSetDevice(eng->device));
   const int mates = eng->paired ? 2 : 1;
   const int texts = woven_in ? 1 : mates;  // texts uploaded and indexed
@@ -1861,6 +1966,7 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
     if (n_records && !bytes[m]) return fail(CS_ERR_ARG, "mate %d: %u records in 0 bytes of text", m + 1, n_records);
   s.n = n_records;
   s.waited = false;
+  t->submitted = true;
   hipStream_t st = eng->stream, rs = eng->resolve_stream;
   for (int m = 0; m < texts; ++m)
     if (bytes[m]) HIP_TRY(hipMemcpyAsync(s.d_text[m], src[m], bytes[m], hipMemcpyHostToDevice, t->h2d));
@@ -1953,6 +2059,13 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
     fa.totals = s.d_totals + 2;
     fa.meta = s.d_meta;
     const uint32_t fb = (n_records + 255u) / 256u;
+    // a kernel that writes or measures names: with a template (cs_text_set_rename) the instantiation that takes the
+    // table behind its other arguments, without one the kernel it always was
+#define LAUNCH_NAMED(kernel, grid, block, ...)                                              \
+  do {                                                                                      \
+    if (t->renamed) hipLaunchKernelGGL(kernel, grid, block, 0, rs, __VA_ARGS__, t->rename); \
+    else hipLaunchKernelGGL(kernel, grid, block, 0, rs, __VA_ARGS__);                       \
+  } while (0)
     csinfo::InfoArgs ia;
     memset(&ia, 0, sizeof ia);
     if (t->info) {
@@ -1973,13 +2086,13 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
       HIP_TRY(hipMemsetAsync(s.d_imeta, 0, sizeof(csinfo::InfoMeta), rs));
       const dim3 rec_grid((n_records + 63u) / 64u);
       if (eng->ends && eng->info_max_m <= 48u)
-        hipLaunchKernelGGL((csinfo::info_record<48, true>), rec_grid, dim3(64), 0, rs, fa, t->tp, ia);
+        LAUNCH_NAMED((csinfo::info_record<48, true>), rec_grid, dim3(64), fa, t->tp, ia);
       else if (eng->ends)
-        hipLaunchKernelGGL((csinfo::info_record<CS_MAX_ADAPTER, true>), rec_grid, dim3(64), 0, rs, fa, t->tp, ia);
+        LAUNCH_NAMED((csinfo::info_record<CS_MAX_ADAPTER, true>), rec_grid, dim3(64), fa, t->tp, ia);
       else if (eng->info_max_m <= 48u)
-        hipLaunchKernelGGL(csinfo::info_record<48>, rec_grid, dim3(64), 0, rs, fa, t->tp, ia);
+        LAUNCH_NAMED(csinfo::info_record<48>, rec_grid, dim3(64), fa, t->tp, ia);
       else
-        hipLaunchKernelGGL(csinfo::info_record<CS_MAX_ADAPTER>, rec_grid, dim3(64), 0, rs, fa, t->tp, ia);
+        LAUNCH_NAMED(csinfo::info_record<CS_MAX_ADAPTER>, rec_grid, dim3(64), fa, t->tp, ia);
     }
     if (t->tp.n_bins) {  // one route per barcode: LDS sums per route instead of a block scan per route
       fa.bc = s.d_bc;
@@ -1996,46 +2109,47 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
         fa.route_bytes = &s.d_routes->bytes[0][0];
         fa.route_count = s.d_routes->count;
         HIP_TRY(hipMemsetAsync(s.d_routes, 0, sizeof(RouteBlock), rs));
-        hipLaunchKernelGGL(cstext::format_sizes_woven<4>, dim3(fb), dim3(256), 0, rs, fa, t->tp);
+        LAUNCH_NAMED(cstext::format_sizes_woven<4>, dim3(fb), dim3(256), fa, t->tp);
         hipLaunchKernelGGL(cstext::text_scan_blocks, dim3(1), dim3(1024), 0, rs, blk_fmt, fb, 4u, fa.totals);
-        hipLaunchKernelGGL(cstext::format_offsets_woven<4>, dim3(fb), dim3(256), 0, rs, fa, t->tp, lead);
+        LAUNCH_NAMED(cstext::format_offsets_woven<4>, dim3(fb), dim3(256), fa, t->tp, lead);
       } else {
-        hipLaunchKernelGGL(cstext::format_sizes_woven<3>, dim3(fb), dim3(256), 0, rs, fa, t->tp);
+        LAUNCH_NAMED(cstext::format_sizes_woven<3>, dim3(fb), dim3(256), fa, t->tp);
         hipLaunchKernelGGL(cstext::text_scan_blocks, dim3(1), dim3(1024), 0, rs, blk_fmt, fb, 3u, fa.totals);
-        hipLaunchKernelGGL(cstext::format_offsets_woven<3>, dim3(fb), dim3(256), 0, rs, fa, t->tp, lead);
+        LAUNCH_NAMED(cstext::format_offsets_woven<3>, dim3(fb), dim3(256), fa, t->tp, lead);
       }
     } else if (t->tp.too_long_route) {  // four routes: the plain block scans over eight columns
       fa.route_bytes = &s.d_routes->bytes[0][0];
       fa.route_count = s.d_routes->count;
       HIP_TRY(hipMemsetAsync(s.d_routes, 0, sizeof(RouteBlock), rs));
-      hipLaunchKernelGGL(cstext::format_sizes<4>, dim3(fb), dim3(256), 0, rs, fa, t->tp);
+      LAUNCH_NAMED(cstext::format_sizes<4>, dim3(fb), dim3(256), fa, t->tp);
       hipLaunchKernelGGL(cstext::text_scan_blocks, dim3(1), dim3(1024), 0, rs, blk_fmt, fb, 8u, fa.totals);
-      hipLaunchKernelGGL(cstext::format_offsets<4>, dim3(fb), dim3(256), 0, rs, fa, t->tp);
+      LAUNCH_NAMED(cstext::format_offsets<4>, dim3(fb), dim3(256), fa, t->tp);
     } else {
-      hipLaunchKernelGGL(cstext::format_sizes<3>, dim3(fb), dim3(256), 0, rs, fa, t->tp);
+      LAUNCH_NAMED(cstext::format_sizes<3>, dim3(fb), dim3(256), fa, t->tp);
       hipLaunchKernelGGL(cstext::text_scan_blocks, dim3(1), dim3(1024), 0, rs, blk_fmt, fb, 6u, fa.totals);
-      hipLaunchKernelGGL(cstext::format_offsets<3>, dim3(fb), dim3(256), 0, rs, fa, t->tp);
+      LAUNCH_NAMED(cstext::format_offsets<3>, dim3(fb), dim3(256), fa, t->tp);
     }
     const unsigned long long items = (unsigned long long)n_records * mates;
     const unsigned long long want = (items * 32ull + 255ull) / 256ull;
     const dim3 copy_grid((uint32_t)(want > 32768ull ? 32768ull : want));
     if (t->mixed_formats)
-      hipLaunchKernelGGL(cstext::format_copy<true>, copy_grid, dim3(256), 0, rs, fa, t->tp);
+      LAUNCH_NAMED(cstext::format_copy<true>, copy_grid, dim3(256), fa, t->tp);
     else
-      hipLaunchKernelGGL(cstext::format_copy<false>, copy_grid, dim3(256), 0, rs, fa, t->tp);
+      LAUNCH_NAMED(cstext::format_copy<false>, copy_grid, dim3(256), fa, t->tp);
     HIP_TRY(hipGetLastError());
     if (t->info) {
       hipLaunchKernelGGL(csinfo::info_sizes, dim3(fb), dim3(256), 0, rs, fa, ia);
       hipLaunchKernelGGL(cstext::text_scan_blocks, dim3(1), dim3(1024), 0, rs, s.d_iblk, fb, 1u, s.d_itotal);
       hipLaunchKernelGGL(csinfo::info_offsets, dim3(fb), dim3(256), 0, rs, fa, ia);
       const unsigned long long iwant = ((unsigned long long)n_records * 32ull + 255ull) / 256ull;
-      hipLaunchKernelGGL(csinfo::info_copy, dim3((uint32_t)(iwant > 32768ull ? 32768ull : iwant)), dim3(256), 0, rs, fa, t->tp, ia);
+      LAUNCH_NAMED(csinfo::info_copy, dim3((uint32_t)(iwant > 32768ull ? 32768ull : iwant)), dim3(256), fa, t->tp, ia);
       if (t->info & CS_INFO_GZIP) {  // one more stream for the deflate kernels: one gzip member per batch, like a route
         launch_deflate(rs, s.info_gz, s.d_info, &s.d_imeta->bytes, &s.d_imeta->gz_bytes, 1, &s.d_imeta->gz_total, 0,
                        t->literal_only, &s.d_meta->err);
       }
       HIP_TRY(hipGetLastError());
     }
+#undef LAUNCH_NAMED
     if (t->compress) {
       for (int m = 0; m < (woven_out ? 1 : mates); ++m) {  // (interleaved: mate 1's streams hold both mates)
         uint32_t fasta_classes = 0;

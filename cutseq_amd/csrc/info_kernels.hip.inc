@@ -76,7 +76,8 @@ __device__ __forceinline__ uint32_t dec_width(uint32_t x) {
 }
 
 // The record's name as the output files carry it -- format_copy's rule: SuffixRemover applied (Rec.hdr_len), the id
-// field, '_' and the captured bases when the scheme has a UMI.
+// field, '_' and the captured bases when the scheme has a UMI.  With a --rename template (cs_text_set_rename: the
+// kernels' trailing RenameTable, as in text_kernels.hip.inc) it is mate 1's name by cstext::name_len / emit_name.
 struct NameView {
   const uint8_t *id, *tag1, *tag2;
   uint32_t id_len, t1, t2, tag;
@@ -138,8 +139,8 @@ struct Recorder {  // what info_record keeps of a walk: every match, and the byt
   __device__ __forceinline__ void quality_trimmed(int) {}
 };
 
-template <int kMaxM, bool ENDS = false>
-__global__ void __launch_bounds__(64) info_record(FormatArgs a, TextParams tp, InfoArgs ia) {
+template <int kMaxM, bool ENDS = false, class... Rename>
+__global__ void __launch_bounds__(64) info_record(FormatArgs a, TextParams tp, InfoArgs ia, Rename... rn) {
   if (a.meta->err != ~0ull) return;
   const uint32_t r = blockIdx.x * 64u + threadIdx.x;
   if (r >= a.n) return;
@@ -154,11 +155,15 @@ __global__ void __launch_bounds__(64) info_record(FormatArgs a, TextParams tp, I
                                                    (int)(slot != cstext::kNotLong ? a.lrec[0][slot].len : (uint32_t)rc.len), ev);
   // the table must not disagree with the records next to it
   if ((uint32_t)w.s != v.start || (uint32_t)w.e != v.stop || w.flags != v.flags) cstext::report(a.meta, r, ERR_INFO_MISMATCH);
-  const NameView nm = name_view(a, tp, r, v);
+  uint32_t name_bytes;
+  if constexpr (sizeof...(Rename) != 0)
+    name_bytes = cstext::name_len(a, 0, r, 0u, v, tp.paired ? cstext::read_view(a, 1, r) : v, rn...);
+  else
+    name_bytes = name_view(a, tp, r, v).len();
   uint32_t row_bytes = ev.row_bytes;
   if (w.n_matches == 0)
     row_bytes = 7u + per_base * (uint32_t)(w.e - w.s);  // name "\t-1\t" seq '\t' qual "\t\n"
-  row_bytes += (uint32_t)max(w.n_matches, 1) * nm.len();
+  row_bytes += (uint32_t)max(w.n_matches, 1) * name_bytes;
   InfoRec out;
   out.start = (uint32_t)w.s;
   out.stop = (uint32_t)w.e;
@@ -199,7 +204,8 @@ __global__ void __launch_bounds__(256) info_offsets(FormatArgs a, InfoArgs ia) {
   if (threadIdx.x == 0 && *ia.total > ia.cap) cstext::report(a.meta, 0, ERR_INFO_OVERFLOW);
 }
 
-__global__ void __launch_bounds__(256) info_copy(FormatArgs a, TextParams tp, InfoArgs ia) {
+template <class... Rename>
+__global__ void __launch_bounds__(256) info_copy(FormatArgs a, TextParams tp, InfoArgs ia, Rename... rn) {
   if (a.meta->err != ~0ull) return;
   const uint32_t lane = threadIdx.x & 31u;
   const bool with_qual = ia.no_qual == 0;
@@ -231,11 +237,17 @@ __global__ void __launch_bounds__(256) info_copy(FormatArgs a, TextParams tp, In
       pos += w;
     };
     auto name = [&]() {
-      copy(nm.id, nm.id_len);
-      if (nm.tag) {
-        byte('_');
-        copy(nm.tag1, nm.t1);
-        copy(nm.tag2, nm.t2);
+      if constexpr (sizeof...(Rename) != 0) {
+        const ReadView r2 = tp.paired ? cstext::read_view(a, 1, r) : v;
+        cstext::emit_name(a, rn..., 0, r, v, r2, out + pos, lane);
+        pos += cstext::name_len(a, 0, r, 0u, v, r2, rn...);
+      } else {
+        copy(nm.id, nm.id_len);
+        if (nm.tag) {
+          byte('_');
+          copy(nm.tag1, nm.t1);
+          copy(nm.tag2, nm.t2);
+        }
       }
     };
     if (ir.n_matches == 0) {

@@ -24,6 +24,9 @@
 //                         both mates' records in ONE text, alternating, and / or ONE output stream per route, the
 //                         record of one mate followed by its partner's.  Kernels of their own: a cs_text without the
 //                         bits launches what it launched before
+//   name_len / emit_name  cutadapt's --rename (cs_text_set_rename): the record name from a template's segments.  The
+//                         format kernels (and the info table's) take the RenameTable as one more argument; without it
+//                         they are the kernels they were, instantiations of their own with it
 //
 // Everything a kernel rejects (malformed record, read longer than the row stride, mate ids that differ) lands in
 // TextMeta.err as the smallest (record index, code) key; the host raises what the reference's reader would.
@@ -515,9 +518,145 @@ __device__ __forceinline__ bool fasta_stream(const TextParams &tp, uint32_t cls,
   return (tp.fasta_routes >> (2u * cls + m)) & 1u;
 }
 
+// ---- record names ------------------------------------------------------------------------------------------------
+// The name of an output record is the run's default -- id ['_' UMI], what the reference's (PairedEnd)Renamer writes
+// (cutseq/run.py:377-380, 642-645) -- or, with cs_text_set_rename, what a template makes of the header and the captures.
+// A kernel that takes a RenameTable behind its other arguments formats by the template; every such kernel is declared
+// with a trailing pack that is empty for the default name, so that one body serves both and the default's instantiation
+// is the code it was.
+
+constexpr uint32_t kRenameSegs = CS_RENAME_MAX_SEGMENTS, kRenameLiteral = CS_RENAME_MAX_LITERAL;
+
+struct RenameTable {  // by value, behind TextParams
+  uint32_t n;
+  cs_rename_seg seg[kRenameSegs];
+  uint8_t lit[kRenameLiteral + 1u];
+};
+
+struct NameParts {  // Renamer.parse_name on the header behind the SuffixRemover chain
+  const uint8_t *hdr;
+  uint32_t hdr_len, id_off, id_len, com_off, com_len;
+};
+
+__device__ __forceinline__ NameParts name_parts(const FormatArgs &a, uint32_t m, uint32_t r) {
+  NameParts p;
+  const uint32_t idr = a.idr[m][r];
+  p.hdr = a.text[m] + a.rec[m][r].hdr_off;
+  p.hdr_len = a.rec[m][r].hdr_len;
+  p.id_off = idr & 0xffffu;
+  p.id_len = idr >> 16;
+  // two fields (text_parse_records): the comment begins behind the blank run that follows the id, its own trailing
+  // blanks stay; one field: the id is the whole header and there is no comment
+  uint32_t c = p.id_off + p.id_len;
+  while (c < p.hdr_len && is_space(p.hdr[c])) ++c;
+  p.com_off = c;
+  p.com_len = p.hdr_len - c;
+  return p;
+}
+
+// The capture a segment names: the first or second of mate 1, of mate 2 or of the written mate (a single-end r2 is r1).
+// (From copies of the fields: `c ? r1.x : r2.x` is an lvalue, a choice between two addresses, and put both views into
+// scratch.)
+struct Capture {
+  const uint8_t *at;
+  uint32_t len;
+};
+
+__device__ __forceinline__ Capture capture_of(const cs_rename_seg &s, uint32_t m, const ReadView &r1, const ReadView &r2) {
+  const bool mate2 = (s.mate == CS_RENAME_OWN ? m : (uint32_t)s.mate) != 0u, second = s.kind == CS_RENAME_CAPTURE2;
+  const uint8_t *const seq1 = r1.seq, *const seq2 = r2.seq;
+  const uint32_t off1a = r1.cap_off, off1b = r1.cap2_off, off2a = r2.cap_off, off2b = r2.cap2_off;
+  const uint32_t len1a = r1.cap_len, len1b = r1.cap2_len, len2a = r2.cap_len, len2b = r2.cap2_len;
+  Capture c;
+  c.at = mate2 ? seq2 + (second ? off2b : off2a) : seq1 + (second ? off1b : off1a);
+  c.len = mate2 ? (second ? len2b : len2a) : (second ? len1b : len1a);
+  return c;
+}
+
+__device__ __forceinline__ uint32_t segment_len(const cs_rename_seg &s, const NameParts &p, uint32_t m, const ReadView &r1,
+                                                const ReadView &r2) {
+  switch (s.kind) {
+    case CS_RENAME_LITERAL: return s.lit_len;
+    case CS_RENAME_HEADER: return p.hdr_len;
+    case CS_RENAME_ID: return p.id_len;
+    case CS_RENAME_COMMENT: return p.com_len;
+    case CS_RENAME_CAPTURE:
+    case CS_RENAME_CAPTURE2: return capture_of(s, m, r1, r2).len;
+    default: return 1u;  // CS_RENAME_MATE
+  }
+}
+
+// bytes of mate m's name: the default template's (`tag`: '_' and the captures, 0 without a UMI) ...
+__device__ __forceinline__ uint32_t name_len(const FormatArgs &a, uint32_t m, uint32_t r, uint32_t tag, const ReadView &,
+                                             const ReadView &) {
+  return (a.idr[m][r] >> 16) + tag;
+}
+
+// ... or a --rename template's
+__device__ __forceinline__ uint32_t name_len(const FormatArgs &a, uint32_t m, uint32_t r, uint32_t, const ReadView &r1,
+                                             const ReadView &r2, const RenameTable &rn) {
+  const NameParts p = name_parts(a, m, r);
+  uint32_t n = 0;
+  for (uint32_t i = 0; i < rn.n; ++i) n += segment_len(rn.seg[i], p, m, r1, r2);
+  return n;
+}
+
+// The stretch copy of format_copy (there: why), 32 lanes per stretch: a lane holds its dwords of the first 256 bytes,
+// so that a caller can issue the loads of several stretches before the first store; longer stretches finish in a loop
+// behind the stores.
+struct Held {
+  uint32_t v0, v1, tail;
+};
+
+__device__ __forceinline__ Held stretch_load(uint32_t lane, const uint8_t *src, uint32_t n) {
+  Held h{0u, 0u, 0u};
+  const uint32_t i0 = 4u * lane, i1 = i0 + 128u, r = n & 3u;
+  if (i0 + 4u <= n) __builtin_memcpy(&h.v0, src + i0, 4);
+  if (i1 + 4u <= n) __builtin_memcpy(&h.v1, src + i1, 4);
+  if (lane < r) h.tail = src[n - r + lane];
+  return h;
+}
+
+__device__ __forceinline__ void stretch_store(uint32_t lane, uint8_t *dst, const uint8_t *src, uint32_t n, const Held &h) {
+  const uint32_t i0 = 4u * lane, i1 = i0 + 128u, r = n & 3u;
+  if (i0 + 4u <= n) __builtin_memcpy(dst + i0, &h.v0, 4);
+  if (i1 + 4u <= n) __builtin_memcpy(dst + i1, &h.v1, 4);
+  if (lane < r) dst[n - r + lane] = (uint8_t)h.tail;
+  for (uint32_t i = i0 + 256u; i + 4u <= n; i += 128u) {
+    uint32_t v;
+    __builtin_memcpy(&v, src + i, 4);
+    __builtin_memcpy(dst + i, &v, 4);
+  }
+}
+
+// Mate m's name by the template, written by the record's 32 lanes; `out` stands behind the '@'.  The segments one after
+// the other, control flow uniform over the lanes: the header's pieces by the stretch copy, literals and captures a byte
+// per lane (with the loop for those beyond 32 bytes), the mate's digit by lane 0.
+__device__ __forceinline__ void emit_name(const FormatArgs &a, const RenameTable &rn, uint32_t m, uint32_t r, const ReadView &r1,
+                                          const ReadView &r2, uint8_t *out, uint32_t lane) {
+  const NameParts p = name_parts(a, m, r);
+  for (uint32_t i = 0; i < rn.n; ++i) {
+    const cs_rename_seg s = rn.seg[i];
+    const uint32_t n = segment_len(s, p, m, r1, r2);
+    if (s.kind == CS_RENAME_HEADER || s.kind == CS_RENAME_ID || s.kind == CS_RENAME_COMMENT) {
+      const uint8_t *src = p.hdr + (s.kind == CS_RENAME_ID ? p.id_off : (s.kind == CS_RENAME_COMMENT ? p.com_off : 0u));
+      const Held h = stretch_load(lane, src, n);
+      stretch_store(lane, out, src, n, h);
+    } else if (s.kind == CS_RENAME_LITERAL) {
+      for (uint32_t t = lane; t < n; t += 32u) out[t] = rn.lit[s.lit_off + t];
+    } else if (s.kind == CS_RENAME_CAPTURE || s.kind == CS_RENAME_CAPTURE2) {
+      const uint8_t *src = capture_of(s, m, r1, r2).at;
+      for (uint32_t t = lane; t < n; t += 32u) out[t] = src[t];
+    } else if (lane == 0) {
+      out[0] = (uint8_t)('1' + m);
+    }
+    out += n;
+  }
+}
+
 // kTooLong (TextParams.too_long_route; the four-route kernels): the pair TooLong catches is written, as route 3
-template <bool kTooLong = false>
-__device__ __forceinline__ RecordShape record_shape(const FormatArgs &a, const TextParams &tp, uint32_t r) {
+template <bool kTooLong = false, class... Rename>
+__device__ __forceinline__ RecordShape record_shape(const FormatArgs &a, const TextParams &tp, uint32_t r, const Rename &... rn) {
   RecordShape s;
   const ReadView r1 = read_view(a, 0, r);
   uint32_t flags = r1.flags, tag = 0;
@@ -544,12 +683,12 @@ __device__ __forceinline__ RecordShape record_shape(const FormatArgs &a, const T
     const uint32_t bc = slot != kNotLong ? a.lres[tp.demux_mate][slot].bc : a.bc[r];
     if (bc != CS_DEMUX_NONE) s.route = 3u + bc;
   }
-  // '@' id tag '\n' seq "\n+\n" qual '\n'   or, without qualities,   '>' id tag '\n' seq '\n'
+  // '@' name '\n' seq "\n+\n" qual '\n'   or, without qualities,   '>' name '\n' seq '\n'
   // -- which of the two goes by the file the (route, mate) stream is written to
   const uint32_t cls = route_class(s.route);  // (kRouteDiscard counts as 3 here: nobody looks at its sizes)
   const bool fa1 = fasta_stream(tp, cls, 0), fa2 = fasta_stream(tp, cls, 1);
-  s.len[0] = (a.idr[0][r] >> 16) + tag + (fa1 ? 1u : 2u) * (r1.stop - r1.start) + (fa1 ? 3u : 6u);
-  s.len[1] = tp.paired ? (a.idr[1][r] >> 16) + tag + (fa2 ? 1u : 2u) * (r2.stop - r2.start) + (fa2 ? 3u : 6u) : 0u;
+  s.len[0] = name_len(a, 0, r, tag, r1, r2, rn...) + (fa1 ? 1u : 2u) * (r1.stop - r1.start) + (fa1 ? 3u : 6u);
+  s.len[1] = tp.paired ? name_len(a, 1, r, tag, r1, r2, rn...) + (fa2 ? 1u : 2u) * (r2.stop - r2.start) + (fa2 ? 3u : 6u) : 0u;
   return s;
 }
 
@@ -564,13 +703,13 @@ __device__ __forceinline__ void add_discards(TextMeta *meta, uint32_t packed) {
 // kRoutes = 3: the plain plan.  kRoutes = 4: a too-long plan (TextParams.too_long_route), route 3 = the pairs TooLong
 // caught; 2 * kRoutes columns in blk / totals.  A lane behind the last record holds route kRoutes: in no column.
 // No plan but a too-long plan launches the <4> pair.
-template <uint32_t kRoutes>
-__global__ void __launch_bounds__(256) format_sizes(FormatArgs a, TextParams tp) {
+template <uint32_t kRoutes, class... Rename>
+__global__ void __launch_bounds__(256) format_sizes(FormatArgs a, TextParams tp, Rename... rn) {
   __shared__ uint32_t sh[8];
   if (a.meta->err != ~0ull) return;
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
   RecordShape s = {kRoutes, {0u, 0u}, 0u};
-  if (r < a.n) s = record_shape<kRoutes == 4u>(a, tp, r);
+  if (r < a.n) s = record_shape<kRoutes == 4u>(a, tp, r, rn...);
 #pragma unroll
   for (uint32_t c = 0; c < 2u * kRoutes; ++c) {
     uint32_t total;
@@ -579,13 +718,13 @@ __global__ void __launch_bounds__(256) format_sizes(FormatArgs a, TextParams tp)
   }
 }
 
-template <uint32_t kRoutes>
-__global__ void __launch_bounds__(256) format_offsets(FormatArgs a, TextParams tp) {
+template <uint32_t kRoutes, class... Rename>
+__global__ void __launch_bounds__(256) format_offsets(FormatArgs a, TextParams tp, Rename... rn) {
   __shared__ uint32_t sh[8];
   if (a.meta->err != ~0ull) return;
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
   RecordShape s = {kRoutes, {0u, 0u}, 0u};
-  if (r < a.n) s = record_shape<kRoutes == 4u>(a, tp, r);
+  if (r < a.n) s = record_shape<kRoutes == 4u>(a, tp, r, rn...);
   // where a route's stream starts inside the mate's buffer: behind the routes in front of it
   unsigned long long base[kRoutes][2];
   for (int m = 0; m < 2; ++m) {
@@ -651,13 +790,13 @@ __global__ void __launch_bounds__(256) format_offsets(FormatArgs a, TextParams t
 // (blk / totals hold kRoutes of them), a pair contributes len[0] + len[1]; the first mate's record stands at the pair's
 // offset and the second's behind it.  dst[0] and dst[1] are offsets into the one buffer (FormatArgs.out[1] == out[0]),
 // so format_copy runs as it is.  `second_first` (CS_INTERLEAVE_OUT_MATE2_FIRST): mate 2's record leads.
-template <uint32_t kRoutes>
-__global__ void __launch_bounds__(256) format_sizes_woven(FormatArgs a, TextParams tp) {
+template <uint32_t kRoutes, class... Rename>
+__global__ void __launch_bounds__(256) format_sizes_woven(FormatArgs a, TextParams tp, Rename... rn) {
   __shared__ uint32_t sh[8];
   if (a.meta->err != ~0ull) return;
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
   RecordShape s = {kRoutes, {0u, 0u}, 0u};
-  if (r < a.n) s = record_shape<kRoutes == 4u>(a, tp, r);
+  if (r < a.n) s = record_shape<kRoutes == 4u>(a, tp, r, rn...);
 #pragma unroll
   for (uint32_t c = 0; c < kRoutes; ++c) {
     uint32_t total;
@@ -666,13 +805,13 @@ __global__ void __launch_bounds__(256) format_sizes_woven(FormatArgs a, TextPara
   }
 }
 
-template <uint32_t kRoutes>
-__global__ void __launch_bounds__(256) format_offsets_woven(FormatArgs a, TextParams tp, uint32_t second_first) {
+template <uint32_t kRoutes, class... Rename>
+__global__ void __launch_bounds__(256) format_offsets_woven(FormatArgs a, TextParams tp, uint32_t second_first, Rename... rn) {
   __shared__ uint32_t sh[8];
   if (a.meta->err != ~0ull) return;
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
   RecordShape s = {kRoutes, {0u, 0u}, 0u};
-  if (r < a.n) s = record_shape<kRoutes == 4u>(a, tp, r);
+  if (r < a.n) s = record_shape<kRoutes == 4u>(a, tp, r, rn...);
   // where a route's stream starts inside the buffer: behind the routes in front of it
   unsigned long long base[kRoutes];
   base[0] = 0;
@@ -868,8 +1007,9 @@ __device__ __forceinline__ uint8_t complement(uint8_t c) {
 // 32 lanes per output record: byte j of the record -> the source byte it copies.  kMixed: the output files name
 // different formats, so FASTA or FASTQ is a property of the record (its route class, from the top bits of its dst,
 // and its mate); otherwise the one format of the whole grid, a scalar as before streams had formats of their own.
-template <bool kMixed>
-__global__ void __launch_bounds__(256) format_copy(FormatArgs a, TextParams tp) {
+template <bool kMixed, class... Rename>
+__global__ void __launch_bounds__(256) format_copy(FormatArgs a, TextParams tp, Rename... rn) {
+  constexpr bool kRenamed = sizeof...(Rename) != 0;  // the name by a template (emit_name), not id ['_' UMI]
   if (a.meta->err != ~0ull) return;
   const uint32_t lane = threadIdx.x & 31u;
   const uint32_t mates = tp.paired ? 2u : 1u;
@@ -880,23 +1020,30 @@ __global__ void __launch_bounds__(256) format_copy(FormatArgs a, TextParams tp) 
     if (tp.filters && a.dst[m][r] == kDiscarded) continue;  // (a discarded pair; uniform over the record's 32 lanes)
     const ReadView me = read_view(a, m, r);
     const ReadView r1 = m == 0 ? me : read_view(a, 0, r);
-    const uint32_t idr = a.idr[m][r];
-    const uint32_t id_len = idr >> 16;
-    const uint8_t *id = a.text[m] + a.rec[m][r].hdr_off + (idr & 0xffffu);
-    const uint8_t *tag1 = r1.seq + r1.cap_off, *tag2 = nullptr;
-    uint32_t t1 = 0, t2 = 0;
-    if (tp.has_umi) {
-      t1 = r1.cap_len;
-      if (tp.paired) {
-        const ReadView r2 = m == 1 ? me : read_view(a, 1, r);
-        tag2 = r2.seq + r2.cap_off;
-        t2 = r2.cap_len;
-      } else {
-        tag2 = r1.seq + r1.cap2_off;
-        t2 = r1.cap2_len;
+    const uint8_t *id = nullptr, *tag1 = nullptr, *tag2 = nullptr;
+    uint32_t id_len = 0, t1 = 0, t2 = 0, tag = 0;
+    ReadView r2 = r1;
+    if constexpr (kRenamed) {
+      if (tp.paired) r2 = m == 1 ? me : read_view(a, 1, r);
+      id_len = name_len(a, m, r, 0u, r1, r2, rn...);  // (the whole name stands where the id does)
+    } else {
+      const uint32_t idr = a.idr[m][r];
+      id_len = idr >> 16;
+      id = a.text[m] + a.rec[m][r].hdr_off + (idr & 0xffffu);
+      tag1 = r1.seq + r1.cap_off;
+      if (tp.has_umi) {
+        t1 = r1.cap_len;
+        if (tp.paired) {
+          r2 = m == 1 ? me : read_view(a, 1, r);
+          tag2 = r2.seq + r2.cap_off;
+          t2 = r2.cap_len;
+        } else {
+          tag2 = r1.seq + r1.cap2_off;
+          t2 = r1.cap2_len;
+        }
       }
+      tag = tp.has_umi ? 1u + t1 + t2 : 0u;
     }
-    const uint32_t tag = tp.has_umi ? 1u + t1 + t2 : 0u;
     const uint32_t L = me.stop - me.start;
     const uint8_t *seq = me.seq, *qual = me.qual;
     const bool rc = tp.reverse_complement && !tp.paired;
@@ -914,42 +1061,28 @@ __global__ void __launch_bounds__(256) format_copy(FormatArgs a, TextParams tp) 
     // in 0.43 ms: the text path's largest kernel.  Quads across the whole record with a byte-wise path for the ones that
     // straddle a stretch were slower still, 0.65 ms: every step of every wave has such a quad.)
     // ... and every stretch's loads are issued before the first store (the stores of one stretch used to stand between
-    // the loads of the next: uint8_t pointers may alias, so each stretch paid its own trip to memory): a lane holds its
-    // dwords of the first 256 bytes of a stretch, longer stretches finish in a loop behind the stores.
-    struct Held {
-      uint32_t v0, v1, tail;
-    };
-    auto load = [&](const uint8_t *src, uint32_t n) -> Held {
-      Held h{0u, 0u, 0u};
-      const uint32_t i0 = 4u * lane, i1 = i0 + 128u, r = n & 3u;
-      if (i0 + 4u <= n) __builtin_memcpy(&h.v0, src + i0, 4);
-      if (i1 + 4u <= n) __builtin_memcpy(&h.v1, src + i1, 4);
-      if (lane < r) h.tail = src[n - r + lane];
-      return h;
-    };
-    auto store = [&](uint8_t *dst, const uint8_t *src, uint32_t n, const Held &h) {
-      const uint32_t i0 = 4u * lane, i1 = i0 + 128u, r = n & 3u;
-      if (i0 + 4u <= n) __builtin_memcpy(dst + i0, &h.v0, 4);
-      if (i1 + 4u <= n) __builtin_memcpy(dst + i1, &h.v1, 4);
-      if (lane < r) dst[n - r + lane] = (uint8_t)h.tail;
-      for (uint32_t i = i0 + 256u; i + 4u <= n; i += 128u) {
-        uint32_t v;
-        __builtin_memcpy(&v, src + i, 4);
-        __builtin_memcpy(dst + i, &v, 4);
-      }
-    };
-    const Held h_id = load(id, id_len);
+    // the loads of the next: uint8_t pointers may alias, so each stretch paid its own trip to memory): stretch_load /
+    // stretch_store.
+    auto load = [&](const uint8_t *src, uint32_t n) -> Held { return stretch_load(lane, src, n); };
+    auto store = [&](uint8_t *dst, const uint8_t *src, uint32_t n, const Held &h) { stretch_store(lane, dst, src, n, h); };
+    Held h_id{0u, 0u, 0u};
+    if constexpr (!kRenamed) h_id = load(id, id_len);
     Held h_seq{0u, 0u, 0u}, h_qual{0u, 0u, 0u};
     if (!rc) {
       h_seq = load(seq + me.start, L);
       if (!fasta) h_qual = load(qual + me.start, L);
     }
-    uint8_t tag_byte = (uint8_t)'_';  // (tags of up to 32 bytes: one per lane; longer ones finish in the loop below)
-    if (lane > 0 && lane < tag) tag_byte = lane <= t1 ? tag1[lane - 1u] : tag2[lane - 1u - t1];
-    if (lane == 0) out[0] = fasta ? '>' : '@';
-    store(out + 1u, id, id_len, h_id);
-    if (lane < tag) out[e_id + lane] = tag_byte;
-    for (uint32_t t = lane + 32u; t < tag; t += 32u) out[e_id + t] = t <= t1 ? tag1[t - 1u] : tag2[t - 1u - t1];
+    if constexpr (kRenamed) {
+      if (lane == 0) out[0] = fasta ? '>' : '@';
+      emit_name(a, rn..., m, r, r1, r2, out + 1u, lane);
+    } else {
+      uint8_t tag_byte = (uint8_t)'_';  // (tags of up to 32 bytes: one per lane; longer ones finish in the loop below)
+      if (lane > 0 && lane < tag) tag_byte = lane <= t1 ? tag1[lane - 1u] : tag2[lane - 1u - t1];
+      if (lane == 0) out[0] = fasta ? '>' : '@';
+      store(out + 1u, id, id_len, h_id);
+      if (lane < tag) out[e_id + lane] = tag_byte;
+      for (uint32_t t = lane + 32u; t < tag; t += 32u) out[e_id + t] = t <= t1 ? tag1[t - 1u] : tag2[t - 1u - t1];
+    }
     if (lane == 1) out[e_tag] = '\n';
     if (!rc) {
       store(out + e_tag + 1u, seq + me.start, L, h_seq);

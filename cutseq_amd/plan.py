@@ -66,6 +66,8 @@ class CutadaptConfig:
         # op (None = off); -L LENGTH: mate 2's own length (None = it follows -l; -L alone shortens mate 2 only)
         self.length = None
         self.length_r2 = None
+        # cutadapt --rename TEMPLATE: the template of the chain's (PairedEnd)Renamer (None = the reference's own)
+        self.rename = None
 
 
 @dataclass
@@ -276,6 +278,7 @@ class TrimPlan:
     max_n: Optional[float] = None  # TooManyN(max_n) filter (cs_plan_set_max_n); None = no such filter
     max_length: Optional[int] = None  # TooLong(max_length) filter (cs_plan_set_max_length); None = no such filter
     max_ee: Optional[float] = None  # TooManyExpectedErrors(max_ee) filter (cs_plan_set_max_ee); None = no such filter
+    rename: Optional[str] = None  # --rename: the (PairedEnd)Renamer's template (rename.py); None = the reference's
 
     @property
     def has_filters(self) -> bool:
@@ -526,6 +529,7 @@ def compile_single(barcode: BarcodeConfig, settings: CutadaptConfig, untrimmed_r
         max_n=getattr(settings, "max_n", None),
         max_length=getattr(settings, "max_length", None),
         max_ee=getattr(settings, "max_ee", None),
+        rename=getattr(settings, "rename", None),
     )
 
 
@@ -625,6 +629,7 @@ def compile_paired(barcode: BarcodeConfig, settings: CutadaptConfig, untrimmed_r
         max_n=getattr(settings, "max_n", None),
         max_length=getattr(settings, "max_length", None),
         max_ee=getattr(settings, "max_ee", None),
+        rename=getattr(settings, "rename", None),
     )
 
 

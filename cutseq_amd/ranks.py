@@ -362,7 +362,7 @@ def _run_ranks(argv: List[str], args, world: int, shares, t0: float, how: str) -
     children, specs = [], []
     # every rank gets its share of the host threads (N pools of all cores each would oversubscribe the host N times)
     per_rank = max(1, _host_threads(args) // world)
-    child_argv = _strip_option(_strip_option(_strip_option(argv, "--ranks"), "--threads"), "-t") + ["-t", str(per_rank)]
+    argv_of_rank = child_argv(argv, per_rank)
 
     try:
         for r in range(world):
@@ -376,7 +376,7 @@ def _run_ranks(argv: List[str], args, world: int, shares, t0: float, how: str) -
                 json.dump(spec, fh)
             specs.append(spec)
             env = dict(os.environ, CUTSEQ_DEVICES=str(devices[r % len(devices)]), CUTSEQ_PROGRESS="0")  # (one Done line: the parent's)
-            children.append(subprocess.Popen([sys.executable, "-m", "cutseq_amd.run"] + child_argv + ["--rank-spec", path], env=env))
+            children.append(subprocess.Popen([sys.executable, "-m", "cutseq_amd.run"] + argv_of_rank + ["--rank-spec", path], env=env))
         left = list(range(world))
         while left:  # a rank that dies is noticed at once, whatever its number, and takes the others with it
             for r in list(left):
@@ -427,6 +427,13 @@ def _run_ranks(argv: List[str], args, world: int, shares, t0: float, how: str) -
         for name in os.listdir(work):
             os.unlink(os.path.join(work, name))
         os.rmdir(work)
+
+
+def child_argv(argv: List[str], per_rank: int) -> List[str]:
+    """A rank's command line: the parent's, so that every option reaches the children as it was given (--rename's
+    template among them: one argument, braces, blanks and all), without --ranks and with the rank's share of the host
+    threads."""
+    return _strip_option(_strip_option(_strip_option(argv, "--ranks"), "--threads"), "-t") + ["-t", str(per_rank)]
 
 
 def _strip_option(argv: List[str], name: str) -> List[str]:

@@ -21,7 +21,7 @@ import time
 from collections import deque
 from typing import List, Optional
 
-from . import __version__, abi, fanout, outputs, report, switches
+from . import __version__, abi, fanout, outputs, rename, report, switches
 from .abi import ReadTooLong
 from .common import BUILDIN_ADAPTERS, BarcodeConfig, print_builtin_adapters
 from .outputs import OUTPUT_CLASSES, _fail  # noqa: F401 -- (OUTPUT_CLASSES: under the name it had here)
@@ -129,6 +129,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Extension (cutadapt's option; a TODO of the reference): write a tab-separated table of the "
                         "adapter matches of read 1 to FILE, one row per match, in input order; reads without a match "
                         "get one row with -1. A .gz / .bz2 / .xz / .zst name compresses the table.")
+    p.add_argument("--rename", type=str, default=None, metavar="TEMPLATE",
+                   help="Extension (cutadapt's option): name every output record by TEMPLATE instead of the default "
+                        "('{id}', with a UMI '{id}_{cut_prefix}{cut_suffix}' or, paired, "
+                        "'{id}_{r1.cut_prefix}{r2.cut_prefix}'). Placeholders: {header}, {id}, {comment}; single-end "
+                        "{cut_prefix}, {cut_suffix}; paired {rn}, {cut_prefix}, {r1.cut_prefix}, {r2.cut_prefix}. "
+                        "'{{' and '}}' are braces, '\\t' is a TAB. Example: '{id} RX:Z:{r1.cut_prefix}{r2.cut_prefix}'. "
+                        "Not with --demux-barcodes.")
     p.add_argument("--interleaved", action="store_true",
                    help="Extension (cutadapt's option): paired reads in ONE file, mate 1 and mate 2 alternating. With one "
                         "input file, that file holds interleaved pairs (the run is a paired run); the outputs are "
@@ -238,6 +245,15 @@ def resolve_args(args):
                   "no error count to report.")
         if not switches.enabled("TEXT_PATH"):
             _fail("--info-file needs the text path: the table is written on the GPU (CUTSEQ_TEXT_PATH=0 is set).")
+    if args.rename is not None:
+        if args.demux_barcodes:
+            _fail("--rename cannot be combined with --demux-barcodes: the barcodes' kernels write the default names.")
+        if not switches.enabled("TEXT_PATH"):
+            _fail("--rename needs the text path: the names are built on the GPU (CUTSEQ_TEXT_PATH=0 is set).")
+        try:
+            rename.check(args.rename, len(inputs) == 2 or interleaved_in or interleaved_out)
+        except ValueError as exc:
+            _fail(str(exc))
     if args.too_long_file:
         if args.max_length is None:
             _fail("--too-long-output needs -M/--max-length: without it no read is too long.")
@@ -284,6 +300,7 @@ def settings_from_args(args) -> CutadaptConfig:
     st.min_quality_front_r2 = args.min_quality_front_r2
     st.length = args.length
     st.length_r2 = args.length_r2
+    st.rename = args.rename
     st.dry_run = args.dry_run
     st.auto_rc = args.auto_rc
     st.json_file = args.json_file
@@ -308,13 +325,14 @@ def dry_run_steps(tp: TrimPlan) -> List[str]:
     adapter and UMI steps, the (PairedEnd)Renamer right behind the UMI step (run.py:377-380, 642-645), then masks,
     poly-A, quality trimming (and the single-end reverse complement).  The text of a step is this build's own
     (cutadapt's ``repr``s are not available here); the ORDER is the reference's."""
+    template = tp.rename if tp.rename is not None else rename.default_template(tp.has_umi, tp.paired)
     if tp.paired:
         # (-L without -l: mate 2's chain ends one step behind mate 1's, which has None there)
         steps = [f"({a}, {b})" for a, b in itertools.zip_longest(tp.r1.describe(), tp.r2.describe(), fillvalue="None")]
-        renamer = f"PairedEndRenamer({'{id}_{r1.cut_prefix}{r2.cut_prefix}' if tp.has_umi else '{id}'!r})"
+        renamer = f"PairedEndRenamer({template!r})"
     else:
         steps = list(tp.r1.describe())
-        renamer = f"Renamer({'{id}_{cut_prefix}{cut_suffix}' if tp.has_umi else '{id}'!r})"
+        renamer = f"Renamer({template!r})"
     at = len(tp.r1.ops) if tp.r1.rename_at is None else tp.r1.rename_at
     steps.insert(len(tp.r1.name_suffixes) + at, renamer)
     if not tp.paired and tp.reverse_complement:

@@ -31,7 +31,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import abi, codec, fanout, fastq, report, switches, textpath
+from . import abi, codec, fanout, fastq, rename, report, switches, textpath
 from .abi import ReadTooLong
 from .outputs import TextOptions
 
@@ -625,6 +625,8 @@ class TextWorker(fanout.Worker):
         super().__init__(f"cutseq-gpu{device}")
         self.tp, self.device, self.chunk_reads, self.options = tp, device, chunk_reads, options
         self.mates_out = 2 if tp.paired and not options.interleave_out else 1  # (a woven route comes back as one stream)
+        # --rename: the plan's template as the segments cs_text_set_rename takes (None: the reference's own names)
+        self.rename = rename.compile_template(tp.rename, tp) if tp.rename is not None else None
         self.text = None
         self.stride, self.capacity, self.want_stride = 152, 0, 152
 
@@ -647,7 +649,8 @@ class TextWorker(fanout.Worker):
         self.stride = stride
         self.capacity = max(self.capacity, int(text_bytes * 1.25) + (1 << 20))
         self.text = textpath.TextEngine(self.engine, slots=self.SLOTS, max_text_bytes=self.capacity,
-                                        max_records=self.chunk_reads, stride=self.stride, **dataclasses.asdict(self.options))
+                                        max_records=self.chunk_reads, stride=self.stride, rename=self.rename,
+                                        **dataclasses.asdict(self.options))
 
     def submit(self, slot: int, item):
         b1, b2 = item

@@ -64,8 +64,10 @@ class TextEngine:
     def __init__(self, engine: TrimEngine, slots: int = 3, max_text_bytes: int = 64 << 20, max_records: int = 1 << 18,
                  stride: int = 152, compress: bool = False, bins: int = 0, fasta: bool = False,
                  fasta_routes: int = 0, info: int = 0, too_long_route: bool = False,
-                 interleave_in: bool = False, interleave_out: bool = False, mate2_first: bool = False):
-        """``interleave_in`` / ``interleave_out`` / ``mate2_first``: cutadapt's ``--interleaved`` on a paired plan
+                 interleave_in: bool = False, interleave_out: bool = False, mate2_first: bool = False, rename=None):
+        """``rename``: a :class:`cutseq_amd.rename.Compiled` -- cutadapt's ``--rename``, every record's name by that template
+        (``cs_text_set_rename``) in place of the plan's default; not with ``bins``.
+        ``interleave_in`` / ``interleave_out`` / ``mate2_first``: cutadapt's ``--interleaved`` on a paired plan
         (``cs_text_create_interleaved``) -- :meth:`submit` takes ONE text of ``2 * n_records`` records, mate 1 and mate 2
         alternating; every route's two streams leave as one in mate 1's buffer, mate 1's record first (``mate2_first``:
         mate 2's), and the sizes of mate 2's streams are 0.  Not with ``bins``.
@@ -112,6 +114,13 @@ class TextEngine:
         else:
             capi.check(self.L.cs_text_create(engine._eng_h, C.byref(p), slots, max_text_bytes, max_records, stride,
                                              C.byref(self._h)))
+        if rename is not None:
+            _template, segments, literals = rename
+            table = (abi.cs_rename_seg * max(len(segments), 1))(*segments)
+            rc = self.L.cs_text_set_rename(self._h, table, len(segments), literals, len(literals))
+            if rc:
+                self.close()
+            capi.check(rc)
 
     def close(self):
         if getattr(self, "_h", None):

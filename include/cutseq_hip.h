@@ -500,6 +500,40 @@ enum { CS_INTERLEAVE_IN = 1, CS_INTERLEAVE_OUT = 2, CS_INTERLEAVE_OUT_MATE2_FIRS
 int cs_text_create_interleaved(cs_engine *eng, const cs_text_params *params, uint32_t interleave,
                                uint32_t n_slots, uint64_t max_text_bytes, uint32_t max_records,
                                uint32_t stride, cs_text **out);
+/* cutadapt's --rename: the name of every output record from a template, in place of the default the reference's
+ * (PairedEnd)Renamer writes (id, and '_' and the captures with cs_text_params.has_umi).  The template arrives compiled:
+ * up to CS_RENAME_MAX_SEGMENTS segments, written one behind the other; the literal segments index `literals`
+ * (n_bytes of them, no terminator needed; the lit_len of all literal segments sum to CS_RENAME_MAX_LITERAL at most).
+ * One template serves both mates of a paired plan, each with its own header.
+ *
+ *   CS_RENAME_LITERAL   literals[lit_off .. lit_off + lit_len)
+ *   CS_RENAME_HEADER    the header behind the SuffixRemover chain
+ *   CS_RENAME_ID        Renamer.parse_name's id: the first of two blank-separated fields, else the whole header
+ *   CS_RENAME_COMMENT   ... its comment: the second field with its trailing blanks, empty without one
+ *   CS_RENAME_CAPTURE   the bases the first capturing CS_OP_CUT of `mate`'s chain took (0 mate 1, 1 mate 2,
+ *                       CS_RENAME_OWN the mate being written); CS_RENAME_CAPTURE2: the second one's (single-end plans)
+ *   CS_RENAME_MATE      '1' or '2': the mate being written
+ *
+ * At most CS_RENAME_MAX_HEADER segments of the three header kinds.  n = 0 is legal: every name is empty.  Call it on a
+ * created cs_text before its first cs_text_submit (CS_ERR_ARG afterwards, and for a malformed table, mate 2 on a
+ * single-end plan, a cs_text with n_bins): the output buffers are sized again, since max_tag no longer bounds what a
+ * name gains -- per record the literals, every captured segment and the mate digits, plus the text once more per header
+ * segment; the info table's bound likewise, its column 1 is mate 1's name by the template.  CS_ERR_ARG too when that
+ * takes a mate's output to 1 GiB or the info table to 4 GiB.  A cs_text without the call launches the kernels it
+ * launched before this function existed; one with it, instantiations of their own. */
+enum { CS_RENAME_LITERAL = 0, CS_RENAME_HEADER = 1, CS_RENAME_ID = 2, CS_RENAME_COMMENT = 3, CS_RENAME_CAPTURE = 4,
+       CS_RENAME_CAPTURE2 = 5, CS_RENAME_MATE = 6 };
+enum { CS_RENAME_OWN = 2 };
+#define CS_RENAME_MAX_SEGMENTS 16
+#define CS_RENAME_MAX_LITERAL 255
+#define CS_RENAME_MAX_HEADER 4
+typedef struct cs_rename_seg {
+  uint8_t kind;    /* CS_RENAME_*                                          */
+  uint8_t mate;    /* CS_RENAME_CAPTURE / _CAPTURE2: whose capture         */
+  uint8_t lit_off; /* CS_RENAME_LITERAL: where in `literals`, how many     */
+  uint8_t lit_len;
+} cs_rename_seg;
+int cs_text_set_rename(cs_text *t, const cs_rename_seg *segments, uint32_t n, const char *literals, uint32_t n_bytes);
 void cs_text_destroy(cs_text *t);
 /* Asynchronous: upload (text1 / text2: host memory, pinned for true overlap; they must stay untouched until
  * cs_text_wait returns), record index, trimming kernels, output formatting.  text2 == NULL for single-end. */
