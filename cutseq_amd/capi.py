@@ -15,7 +15,7 @@ LIB_PATH = Path(__file__).with_name("libcutseq_hip.so")
 
 EXPORTS = (
     "cs_abi_version", "cs_last_error", "cs_device_count", "cs_plan_create", "cs_plan_destroy", "cs_plan_set_demux", "cs_plan_set_demux_ops", "cs_plan_set_max_n",
-    "cs_plan_set_max_length", "cs_plan_set_max_ee", "cs_plan_set_ee_reversed", "cs_plan_walk_info", "cs_xflag_counts_fetch", "cs_text_discards",
+    "cs_plan_set_max_length", "cs_plan_set_max_ee", "cs_plan_set_ee_reversed", "cs_plan_walk_info", "cs_plan_demux_view", "cs_xflag_counts_fetch", "cs_text_discards",
     "cs_engine_create", "cs_engine_destroy", "cs_trim_device", "cs_trim_device_pipelined", "cs_join", "cs_trim_batch", "cs_sync",
     "cs_stats_fetch", "cs_last_kernel_ms", "cs_last_kernel_split_ms", "cs_kernel_time_totals", "cs_alloc_pinned", "cs_alloc_pinned_huge", "cs_free_pinned", "cs_alloc_device",
     "cs_free_device", "cs_copy_to_device", "cs_copy_to_host",
@@ -72,6 +72,10 @@ def load() -> C.CDLL:
     if hasattr(L, "cs_plan_walk_info"):  # (an older build loaded through CUTSEQ_HIP_LIB for an A/B has none)
         L.cs_plan_walk_info.restype = i32
         L.cs_plan_walk_info.argtypes = [vp, i32, C.POINTER(u32 * 6)]
+    if hasattr(L, "cs_plan_demux_view"):  # (likewise)
+        L.cs_plan_demux_view.restype = i32
+        L.cs_plan_demux_view.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(C.POINTER(u32)), C.POINTER(C.c_size_t),
+                                         C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
     L.cs_xflag_counts_fetch.restype = i32
     L.cs_xflag_counts_fetch.argtypes = [vp, vp, i32]
     L.cs_text_discards.restype = i32

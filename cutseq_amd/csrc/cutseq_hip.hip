@@ -949,6 +949,23 @@ int cs_plan_set_demux_ops(cs_plan *plan, int mate, int op_index, const cs_op *op
   return CS_OK;
 }
 
+int cs_plan_demux_view(const cs_plan *plan, int mate, int op_index, int *depth, const uint32_t **first, size_t *n_first,
+                       const uint8_t **pool, size_t *n_pool) {
+  if (!plan || !depth || !first || !n_first || !pool || !n_pool) return fail(CS_ERR_ARG, "null plan or output");
+  if (mate < 1 || mate > 2 || op_index < 0 || op_index >= plan->host.n_ops[mate - 1])
+    return fail(CS_ERR_ARG, "mate %d op %d: no such op", mate, op_index);
+  const csdev::DevOp &d = plan->host.ops[mate - 1][op_index];
+  const DemuxLong &dl = plan->demux_long[mate - 1][op_index];
+  if (d.op.kind != CS_OP_DEMUX || !d.filter_mode || dl.ops.empty())
+    return fail(CS_ERR_ARG, "mate %d op %d: no CS_OP_DEMUX op with its barcode ops (cs_plan_set_demux_ops)", mate, op_index);
+  *depth = dl.depth;
+  *first = dl.first.data();
+  *n_first = dl.first.size();
+  *pool = dl.pool.data();
+  *n_pool = dl.pool.size();
+  return CS_OK;
+}
+
 void cs_engine_destroy(cs_engine *eng) {
   if (!eng) return;
   if (eng->device >= 0) (void)hipSetDevice(eng->device);

@@ -284,6 +284,17 @@ int cs_plan_set_demux(cs_plan *plan, int mate, int op_index, const uint16_t *tab
  * above.  Reads of such a plan all pass through the resolve kernel: slower than the table form, same results. */
 int cs_plan_set_demux_ops(cs_plan *plan, int mate, int op_index, const cs_op *ops, int n_ops);
 
+/* The candidate table that cs_plan_set_demux_ops derived, read-only; for tests and tools, no caller needs it.  *depth:
+ * how many bases the table looks at (min(m + k, 9), fewer where the lists outgrew the format).  first[0 .. n_first): one
+ * entry per prefix of length 0 .. depth in the layout of cs_plan_set_demux (a read shorter than depth has the slot of its
+ * own length's block; a 3' op indexes the read's LAST bases, last base first): offset into `pool` << 8 | candidates, 0
+ * where no barcode can match.  pool[0 .. n_pool): the lists, barcode indices in ascending order -- the order the device
+ * tries them in, which is what makes "the lowest index claims the read" hold.  The pointers go into the plan's own
+ * storage: valid until cs_plan_destroy or the next cs_plan_set_demux_ops on that op.  CS_ERR_ARG for an op that is not a
+ * CS_OP_DEMUX op with its barcode ops attached. */
+int cs_plan_demux_view(const cs_plan *plan, int mate, int op_index, int *depth, const uint32_t **first, size_t *n_first,
+                       const uint8_t **pool, size_t *n_pool);
+
 /* cutadapt's --max-n filter, TooManyN(count), on both mates (reference TODO, cutseq/run.py:452, 770): a read whose
  * final interval seq[start:stop] holds too many 'N' / 'n' bases gets CS_X_TOO_MANY_N.  count < 1 is a proportion:
  * stop > start and n / (stop - start) > count (IEEE double); count >= 1 is a number: n > count.  INFINITY never fires.

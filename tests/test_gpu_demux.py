@@ -335,7 +335,8 @@ def test_long_read_walk_demultiplexes_like_the_rows(form, length):
 
 
 def test_demux_table_matches_the_oracle_on_every_prefix():
-    """The device-built table against the CPU oracle's PrefixAdapter on all 5^0 + ... + 5^(m+k) prefixes."""
+    """The device-built table against the CPU oracle's PrefixAdapter on all 5^0 + ... + 5^(m+k) prefixes, merged by the
+    pinned rule."""
     rng = random.Random(3)
     codes = barcode_set(rng, 5, 5, 3)
     op = planmod.DemuxOp(codes, 0.2, abi.CS_F_INLINE)
@@ -343,10 +344,12 @@ def test_demux_table_matches_the_oracle_on_every_prefix():
     seq, lens = demux.all_prefixes(op.m + op.k)
     batch = util.batch_from_reads([(bytes(seq[i, : lens[i]]).decode(), "I" * int(lens[i])) for i in range(len(lens))])
     n_match = np.zeros(len(lens), dtype=int)
+    runs = []
     for index, code in enumerate(codes):
         one = planmod.TrimPlan(r1=planmod.MateChain([planmod.prefix(code, 0.2, abi.CS_F_INLINE)]), r2=None, has_umi=False,
                                min_length=0, untrimmed_filter=False)
         (o1, _, _), _ = util.oracle_run(one, batch, threads=8)
+        runs.append(o1)
         hit = (o1["flags"] & abi.CS_F_INLINE) != 0
         n_match += hit
         mine = (op.table & 0xFF) == index
@@ -354,6 +357,13 @@ def test_demux_table_matches_the_oracle_on_every_prefix():
         assert np.array_equal((op.table[mine] >> 8) & 0xF, o1["start"][mine])  # ... and removes as many bases
     assert np.array_equal((op.table & 0xFF) == abi.CS_DEMUX_NONE, n_match == 0)
     assert np.array_equal((op.table & 0x4000) != 0, n_match > 1)
+    # ... and WHICH of its claimants an entry names is the merge rule's choice (tests/demux_rule.py): an exact copy of a
+    # barcode first, else the lowest index
+    import demux_rule
+    want = demux_rule.merge(runs, codes, (batch.seq1, batch.qual1, batch.len1))
+    assert np.array_equal(op.table & 0xFF, want.bc)
+    assert np.array_equal((op.table >> 8) & 0xF, want.res["start"])
+    assert np.array_equal(demux_rule.table_index(batch.seq1, batch.len1, op.m + op.k), np.arange(len(lens)))
 
 
 @pytest.mark.parametrize("switch", ["", "CUTSEQ_TEXT_PATH=0", "CUTSEQ_GPU_DEFLATE=0"])
