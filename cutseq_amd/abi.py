@@ -197,6 +197,24 @@ class cs_text_result(C.Structure):
     ]
 
 
+# cs_inflate_bgzf: per-block verdicts, the block table's entry, the call's result
+(CS_INFLATE_OK, CS_INFLATE_ERR_BTYPE, CS_INFLATE_ERR_STORED, CS_INFLATE_ERR_CODE, CS_INFLATE_ERR_REPEAT,
+ CS_INFLATE_ERR_NO_EOB, CS_INFLATE_ERR_SYMBOL, CS_INFLATE_ERR_INPUT, CS_INFLATE_ERR_OUTPUT, CS_INFLATE_ERR_DISTANCE,
+ CS_INFLATE_ERR_ISIZE, CS_INFLATE_ERR_CRC, CS_INFLATE_ERR_TRAILING) = range(13)
+
+
+class cs_inflate_block(C.Structure):
+    _fields_ = [("comp_off", C.c_uint64), ("out_off", C.c_uint64), ("comp_len", C.c_uint32), ("out_len", C.c_uint32),
+                ("crc32", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class cs_inflate_result(C.Structure):
+    _fields_ = [("verdict", C.c_int32), ("block", C.c_uint32)]
+
+
+INFLATE_BLOCK_DTYPE = [("comp_off", "<u8"), ("out_off", "<u8"), ("comp_len", "<u4"), ("out_len", "<u4"), ("crc32", "<u4"),
+                       ("reserved", "<u4")]  # numpy's view of a block table
+assert C.sizeof(cs_inflate_block) == 32 and C.sizeof(cs_inflate_result) == 8
 assert C.sizeof(cs_text_params) == 48 and C.sizeof(cs_text_result) == 176 and C.sizeof(cs_rename_seg) == 4
 assert C.sizeof(cs_op) == 284 and cs_op.q_cutoff_front.offset == 282, C.sizeof(cs_op)
 assert cs_op.seq.offset == 24 and cs_op.length.offset == 24 and cs_op.thr.offset == 152

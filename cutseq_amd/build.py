@@ -11,7 +11,8 @@ HERE = Path(__file__).resolve().parent
 SRC = HERE / "csrc" / "cutseq_hip.hip"
 DEPS = [SRC, HERE / "csrc" / "trim_kernel.hip.inc", HERE / "csrc" / "long_kernel.hip.inc",
         HERE / "csrc" / "text_kernels.hip.inc", HERE / "csrc" / "deflate_kernels.hip.inc",
-        HERE / "csrc" / "info_kernels.hip.inc", HERE.parent / "include" / "cutseq_hip.h"]
+        HERE / "csrc" / "info_kernels.hip.inc", HERE / "csrc" / "inflate_kernels.hip.inc",
+        HERE.parent / "include" / "cutseq_hip.h", HERE.parent / "include" / "cutseq_inflate.h"]
 OUT = HERE / "libcutseq_hip.so"
 
 

@@ -21,6 +21,8 @@ EXPORTS = (
     "cs_free_device", "cs_copy_to_device", "cs_copy_to_host",
     "cs_text_create", "cs_text_destroy", "cs_text_submit", "cs_text_wait", "cs_text_routes", "cs_text_fetch",
     "cs_text_info", "cs_text_fetch_info", "cs_text_create_interleaved", "cs_text_set_rename",
+    "cs_copy_on_device", "cs_text_submit_device", "cs_dtext_after_kth_newline", "cs_inflate_create", "cs_inflate_destroy",
+    "cs_inflate_bgzf",
 )
 
 
@@ -141,6 +143,19 @@ def load() -> C.CDLL:
     L.cs_text_info.argtypes = [vp, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.cs_text_fetch_info.restype = i32
     L.cs_text_fetch_info.argtypes = [vp, u32, vp]
+    if hasattr(L, "cs_inflate_bgzf"):  # (an older build loaded through CUTSEQ_HIP_LIB for an A/B has none)
+        L.cs_copy_on_device.restype = i32
+        L.cs_copy_on_device.argtypes = [i32, vp, vp, C.c_size_t]
+        L.cs_text_submit_device.restype = i32
+        L.cs_text_submit_device.argtypes = [vp, u32, vp, u64, vp, u64, u32]
+        L.cs_dtext_after_kth_newline.restype = i32
+        L.cs_dtext_after_kth_newline.argtypes = [i32, vp, u64, C.c_int64, C.POINTER(C.c_int64)]
+        L.cs_inflate_create.restype = i32
+        L.cs_inflate_create.argtypes = [i32, u64, u32, C.POINTER(vp)]
+        L.cs_inflate_destroy.restype = None
+        L.cs_inflate_destroy.argtypes = [vp]
+        L.cs_inflate_bgzf.restype = i32
+        L.cs_inflate_bgzf.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp, vp, C.POINTER(abi.cs_inflate_result)]
     if L.cs_abi_version() != abi.CS_ABI_VERSION:
         raise HipUnavailable(f"ABI mismatch: library {L.cs_abi_version()} vs python {abi.CS_ABI_VERSION}")
     _lib = L

@@ -117,6 +117,29 @@ def _bgzf_block_size(buf, pos: int) -> int:
     return 0
 
 
+def bgzf_index(buf, lo: int, hi: int):
+    """The block table of the BGZF run that starts at ``lo`` -> (rows, end): one row per block, (offset of its deflate
+    payload, payload bytes, ISIZE, CRC-32), and the offset at which the run ends -- ``hi`` or the end of the data, a
+    member that is not a BGZF block, or a block that does not lie inside ``buf[:hi]`` whole (a truncated file; a caller
+    that walks a file in spans sees its next span start there).  The EOF marker, a block with ISIZE 0, is an ordinary
+    row.  A block that promises more than the format's 64 KiB of text ends the run too: it is not BGZF."""
+    rows = []
+    pos = lo
+    hi = min(hi, len(buf))
+    while pos < hi:
+        size = _bgzf_block_size(buf, pos)
+        if size == 0 or pos + size > hi:
+            break
+        payload = pos + 12 + struct.unpack_from("<H", buf, pos + 10)[0]
+        nbytes = pos + size - 8 - payload
+        crc, isize = struct.unpack_from("<II", buf, pos + size - 8)
+        if nbytes < 0 or isize > 65536:
+            break
+        rows.append((payload, nbytes, isize, crc))
+        pos += size
+    return rows, pos
+
+
 def _np_take(nbytes: int):
     import numpy as np
     return np.empty(nbytes, dtype=np.uint8)

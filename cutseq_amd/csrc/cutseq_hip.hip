@@ -24,6 +24,7 @@
 #include "text_kernels.hip.inc"
 #include "deflate_kernels.hip.inc"
 #include "info_kernels.hip.inc"
+#include "inflate_kernels.hip.inc"
 
 namespace {
 
@@ -1448,6 +1449,11 @@ int cs_copy_to_host(int device, void *dst, const void *src, size_t bytes) {
   HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
   return CS_OK;
 }
+int cs_copy_on_device(int device, void *dst, const void *src, size_t bytes) {
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToDevice));
+  return CS_OK;
+}
 
 }  // extern "C"
 
@@ -1960,8 +1966,10 @@ int cs_text_set_rename(cs_text *t, const cs_rename_seg *segments, uint32_t n, co
   return CS_OK;
 }
 
-int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1, const void *text2, uint64_t bytes2,
-                   uint32_t n_records) {
+// cs_text_submit and cs_text_submit_device: `kind` says where the texts are; everything behind the copy into the slot's
+// text buffers is the same
+static int text_submit_from(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1, const void *text2, uint64_t bytes2,
+                            uint32_t n_records, hipMemcpyKind kind) {
   if (!t || !text1) return fail(CS_ERR_ARG, "null text engine or text");
   if (slot >= t->slots.size()) return fail(CS_ERR_ARG, "slot %u out of range", slot);
   cs_engine *eng = t->eng;
@@ -1986,7 +1994,7 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
   t->submitted = true;
   hipStream_t st = eng->stream, rs = eng->resolve_stream;
   for (int m = 0; m < texts; ++m)
-    if (bytes[m]) HIP_TRY(hipMemcpyAsync(s.d_text[m], src[m], bytes[m], hipMemcpyHostToDevice, t->h2d));
+    if (bytes[m]) HIP_TRY(hipMemcpyAsync(s.d_text[m], src[m], bytes[m], kind, t->h2d));
   HIP_TRY(hipEventRecord(s.uploaded, t->h2d));
   HIP_TRY(hipStreamWaitEvent(st, s.uploaded, 0));
   hipLaunchKernelGGL(text_init_meta, dim3(1), dim3(64), 0, st, s.d_meta);
@@ -2193,6 +2201,16 @@ int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1
   return CS_OK;
 }
 
+int cs_text_submit(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1, const void *text2, uint64_t bytes2,
+                   uint32_t n_records) {
+  return text_submit_from(t, slot, text1, bytes1, text2, bytes2, n_records, hipMemcpyHostToDevice);
+}
+
+int cs_text_submit_device(cs_text *t, uint32_t slot, const void *dtext1, uint64_t bytes1, const void *dtext2, uint64_t bytes2,
+                          uint32_t n_records) {
+  return text_submit_from(t, slot, dtext1, bytes1, dtext2, bytes2, n_records, hipMemcpyDefault);
+}
+
 int cs_text_wait(cs_text *t, uint32_t slot, cs_text_result *res) {
   if (!t || !res) return fail(CS_ERR_ARG, "null argument");
   if (slot >= t->slots.size()) return fail(CS_ERR_ARG, "slot %u out of range", slot);
@@ -2321,6 +2339,128 @@ int cs_text_fetch_info(cs_text *t, uint32_t slot, void *dst) {
   if (!dst) return fail(CS_ERR_ARG, "%zu bytes of info table and no buffer", bytes);
   HIP_TRY(hipMemcpyAsync(dst, gz ? s.info_gz.gz : s.d_info, bytes, hipMemcpyDeviceToHost, t->d2h));
   HIP_TRY(hipStreamSynchronize(t->d2h));
+  return CS_OK;
+}
+
+// ---- BGZF input inflated on the device (inflate_kernels.hip.inc) -----------------------------------------------------
+
+struct cs_inflate {
+  int device = -1;
+  hipStream_t stream = nullptr;
+  uint64_t max_comp = 0;
+  uint32_t max_blocks = 0;
+  uint8_t *d_comp = nullptr;
+  cs_inflate_block *d_blocks = nullptr;
+  uint32_t *d_out = nullptr;  // verdict[max_blocks], lines[max_blocks]
+  uint32_t *h_out = nullptr;  // the same, pinned
+};
+
+void cs_inflate_destroy(cs_inflate *h) {
+  if (!h) return;
+  if (hipSetDevice(h->device) == hipSuccess) {
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    if (h->d_comp) (void)hipFree(h->d_comp);
+    if (h->d_blocks) (void)hipFree(h->d_blocks);
+    if (h->d_out) (void)hipFree(h->d_out);
+    if (h->h_out) (void)hipHostFree(h->h_out);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+  }
+  delete h;
+}
+
+int cs_inflate_create(int device, uint64_t max_comp_bytes, uint32_t max_blocks, cs_inflate **out) {
+  if (!out) return fail(CS_ERR_ARG, "out is null");
+  *out = nullptr;
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  if (e != hipSuccess || ndev <= 0)
+    return fail(CS_ERR_NO_GPU, "no HIP device visible (%s); the decoder has no CPU fallback",
+                e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+  if (device < 0 || device >= ndev) return fail(CS_ERR_ARG, "device %d out of range (0..%d)", device, ndev - 1);
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(CS_ERR_NO_GPU, "device %d is %s; the kernels are built for gfx950 (MI355X) only", device, prop.gcnArchName);
+  if (max_comp_bytes >= (1ull << 40)) return fail(CS_ERR_ARG, "max_comp_bytes %llu", (unsigned long long)max_comp_bytes);
+  cs_inflate *h = new (std::nothrow) cs_inflate;
+  if (!h) return fail(CS_ERR_NOMEM, "out of host memory");
+  h->device = device;
+  h->max_comp = max_comp_bytes;
+  h->max_blocks = max_blocks;
+  const size_t nb = max_blocks ? max_blocks : 1;
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
+      hipMalloc(&h->d_comp, max_comp_bytes ? max_comp_bytes : 1) != hipSuccess ||
+      hipMalloc(&h->d_blocks, nb * sizeof(cs_inflate_block)) != hipSuccess ||
+      hipMalloc(&h->d_out, nb * 2 * sizeof(uint32_t)) != hipSuccess ||
+      hipHostMalloc(&h->h_out, nb * 2 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    cs_inflate_destroy(h);
+    return fail(CS_ERR_NOMEM, "cs_inflate_create: no memory for %llu compressed bytes and %u blocks on device %d",
+                (unsigned long long)max_comp_bytes, max_blocks, device);
+  }
+  *out = h;
+  return CS_OK;
+}
+
+int cs_inflate_bgzf(cs_inflate *h, const void *comp, uint64_t comp_bytes, const cs_inflate_block *blocks, uint32_t n_blocks,
+                    void *dtext, uint64_t dtext_cap, uint32_t *lines_out, int32_t *verdicts_out, cs_inflate_result *res) {
+  if (!h || !res) return fail(CS_ERR_ARG, "null handle or result");
+  res->verdict = CS_INFLATE_OK;
+  res->block = 0;
+  if (n_blocks == 0) return CS_OK;
+  if (!blocks || !lines_out || !dtext || (!comp && comp_bytes)) return fail(CS_ERR_ARG, "null argument");
+  if (comp_bytes > h->max_comp || n_blocks > h->max_blocks)
+    return fail(CS_ERR_ARG, "%llu compressed bytes in %u blocks exceed the handle (%llu bytes, %u blocks)",
+                (unsigned long long)comp_bytes, n_blocks, (unsigned long long)h->max_comp, h->max_blocks);
+  for (uint32_t i = 0; i < n_blocks; ++i) {  // the kernel stays inside what an entry names; this keeps the entries inside the buffers
+    const cs_inflate_block &b = blocks[i];
+    if (b.comp_off > comp_bytes || b.comp_len > comp_bytes - b.comp_off)
+      return fail(CS_ERR_ARG, "block %u: payload [%llu, +%u) leaves the %llu compressed bytes", i, (unsigned long long)b.comp_off,
+                  b.comp_len, (unsigned long long)comp_bytes);
+    if (b.out_off > dtext_cap || b.out_len > dtext_cap - b.out_off)
+      return fail(CS_ERR_ARG, "block %u: text [%llu, +%u) leaves the %llu bytes of dtext", i, (unsigned long long)b.out_off,
+                  b.out_len, (unsigned long long)dtext_cap);
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  if (comp_bytes) HIP_TRY(hipMemcpyAsync(h->d_comp, comp, comp_bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_blocks, blocks, (size_t)n_blocks * sizeof(cs_inflate_block), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(csinflate::inflate_bgzf, dim3(n_blocks), dim3(64), 0, h->stream, h->d_comp, h->d_blocks, n_blocks,
+                     static_cast<uint8_t *>(dtext), h->d_out, h->d_out + n_blocks);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h->h_out, h->d_out, (size_t)n_blocks * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  bool failed = false;
+  for (uint32_t i = 0; i < n_blocks; ++i) {
+    lines_out[i] = h->h_out[n_blocks + i];
+    if (verdicts_out) verdicts_out[i] = (int32_t)h->h_out[i];
+    if (h->h_out[i] != CS_INFLATE_OK && !failed) {
+      failed = true;
+      res->verdict = (int32_t)h->h_out[i];
+      res->block = i;
+    }
+  }
+  return CS_OK;
+}
+
+int cs_dtext_after_kth_newline(int device, const void *dtext, uint64_t nbytes, int64_t k, int64_t *offset) {
+  if (!offset || (!dtext && nbytes)) return fail(CS_ERR_ARG, "null argument");
+  if (k < 1) {
+    *offset = 0;
+    return CS_OK;
+  }
+  *offset = -1;
+  if (nbytes == 0) return CS_OK;
+  HIP_TRY(hipSetDevice(device));
+  long long *d_result = nullptr;
+  HIP_TRY(hipMalloc(&d_result, sizeof(long long)));
+  hipLaunchKernelGGL(csinflate::after_kth_newline, dim3(1), dim3(csinflate::kNlThreads), 0, nullptr,
+                     static_cast<const uint8_t *>(dtext), nbytes, (uint64_t)k, d_result);
+  long long got = -1;
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpy(&got, d_result, sizeof got, hipMemcpyDeviceToHost);
+  (void)hipFree(d_result);
+  if (e != hipSuccess) return fail(CS_ERR_HIP, "cs_dtext_after_kth_newline: %s", hipGetErrorString(e));
+  *offset = got;
   return CS_OK;
 }
 

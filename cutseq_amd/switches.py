@@ -31,6 +31,7 @@ TABLE = (
     Switch("CUTSEQ_TEXT_PATH", FLAG_ON, True, "python", "0: the record path (host parser and formatter) instead of the text path"),
     Switch("CUTSEQ_GPU_DEFLATE", FLAG_ON, True, "python", "0: gzip outputs are deflated in the host pool, not on the device"),
     Switch("CUTSEQ_GPU_LZ", FLAG_ON, True, "native", "0: the device's gzip members without their LZ77 stage"),
+    Switch("CUTSEQ_GPU_INFLATE", FLAG_OFF, False, "python", "1: BGZF FASTQ input is inflated on the device and its text stays there (one GPU, no --ranks)"),
     Switch("CUTSEQ_OWN_INFLATE", FLAG_ON, True, "python", "0: libdeflate inflates gzip input, not the package's decoder"),
     Switch("CUTSEQ_PARALLEL_INFLATE", FLAG_ON, True, "python", "0: single-member gzip input is inflated serially"),
     Switch("CUTSEQ_PAIR", FLAG_ON, True, "native", "0: the chain's leading 5' + 3' ops as two scans, not one merged walk"),

@@ -59,6 +59,14 @@ def _tick(key: str, t0: float) -> float:
     return now
 
 
+_inflate_blocks = {"device_blocks": 0, "host_blocks": 0}  # (CUTSEQ_PROFILE=1: who inflated the gzip inputs' blocks)
+
+
+def _count_inflate(key: str, n: int) -> None:
+    with _prof_lock:
+        _inflate_blocks[key] += n
+
+
 def _host():
     L = fastq._lib()
     if not getattr(L, "_text_bound", False):
@@ -74,17 +82,26 @@ def _host():
 
 
 class TextBlock:
-    """``n_records`` complete records in ``buf[:nbytes]`` (a pinned arena buffer)."""
+    """``n_records`` complete records in ``buf[:nbytes]`` (a pinned arena buffer) -- or, from a reader in device mode,
+    in the first ``nbytes`` of ``dbuf``, a buffer of the inflater ``owner`` (``buf`` is None then)."""
 
-    __slots__ = ("buf", "nbytes", "n", "first_record")
+    __slots__ = ("buf", "nbytes", "n", "first_record", "dbuf", "owner")
 
-    def __init__(self, buf: np.ndarray, nbytes: int, n: int, first_record: int):
+    def __init__(self, buf: Optional[np.ndarray], nbytes: int, n: int, first_record: int, dbuf=None, owner=None):
         self.buf, self.nbytes, self.n, self.first_record = buf, nbytes, n, first_record
+        self.dbuf, self.owner = dbuf, owner
+
+    def text_address(self) -> int:
+        """Where the text is: a host address, or a device address (``dbuf``)."""
+        return self.owner.address(self.dbuf) if self.dbuf is not None else self.buf.ctypes.data
 
     def release(self) -> None:
         if self.buf is not None:
             fastq.PINNED.give(self.buf)
             self.buf = None
+        if self.dbuf is not None:
+            self.owner.give(self.dbuf)
+            self.dbuf = None
 
 
 class TextReader(threading.Thread):
@@ -92,14 +109,18 @@ class TextReader(threading.Thread):
     then ``None``.  Exceptions travel through the queue."""
 
     def __init__(self, path: str, chunk_reads: int, start: int = 0, skip_lines: int = 0, max_records: Optional[int] = None,
-                 stop: Optional[int] = None, interleaved: bool = False):
+                 stop: Optional[int] = None, interleaved: bool = False, inflater=None):
         """``interleaved``: the file holds pairs, mate 1 and mate 2 alternating (``--interleaved``).  ``chunk_reads`` still
         counts records and must be even, so every block holds whole pairs; a block's ``n`` and ``first_record`` count
         pairs.  A file that ends on an odd record is refused (:meth:`pair_count`).
         ``start`` / ``skip_lines`` / ``max_records`` / ``stop``: one rank's share of the file in the multi-process form
         (``ranks.py``): begin at byte ``start`` (plain text) or at the gzip member that starts there, drop
         ``skip_lines`` lines, stop behind ``max_records`` records (None = to the end of the file) or in front of the
-        gzip member that starts at compressed offset ``stop``."""
+        gzip member that starts at compressed offset ``stop``.
+        ``inflater``: a callable that makes an inflater (``inflater.py``) -- the device mode, for a whole gzip FASTQ file
+        that starts with a BGZF block: the blocks are inflated into the inflater's buffers (device memory), the blocks
+        handed out hold such a buffer, and only what is left when the BGZF run ends comes back to the host path.  Any
+        other input ignores it (the callable is not called)."""
         super().__init__(daemon=True, name=f"cutseq-read-{os.path.basename(path)}")
         self.path, self.chunk_reads = path, chunk_reads
         self.start_at, self.skip_lines, self.max_records, self.stop_at = start, skip_lines, max_records, stop
@@ -118,6 +139,12 @@ class TextReader(threading.Thread):
         if (self.sequential or self.fasta or (stop is not None and not self.gz)) and (
                 start or skip_lines or max_records is not None or stop is not None):
             raise ValueError(f"{path}: only plain and gzip FASTQ files can be split between ranks")
+        self._make_inflater = None
+        if (inflater is not None and self.gz and not self.fasta and not interleaved and codec.libdeflate() is not None
+                and not (start or skip_lines or max_records is not None or stop is not None)):
+            with open(path, "rb") as fh:
+                if codec._bgzf_block_size(fh.read(1 << 16), 0):
+                    self._make_inflater = inflater
         self.start()
 
     # -- plumbing ---------------------------------------------------------------------------------------
@@ -237,13 +264,20 @@ class TextReader(threading.Thread):
                 eof = True
         return buf, fill + total, marks, eof
 
-    def _run(self):
+    def _run(self, resume=None):
+        """``resume``: (buffer, fill, lines, records done, compressed offset) -- where the device mode's BGZF run ended;
+        the host path goes on from that state, through the same end-of-input code."""
         L = _host()
         need = 4 * self.chunk_reads
         est = 400  # bytes per record, corrected by every block that goes out
-        buf = fastq.PINNED.take(int(self.chunk_reads * est * 1.25) + 2 * _BLOCK)
         fill, lines, done = 0, 0, 0
         marks: List[tuple] = []  # (offset, nbytes, newlines) of every piece behind buf[:fill]
+        if resume is None:
+            buf = fastq.PINNED.take(int(self.chunk_reads * est * 1.25) + 2 * _BLOCK)
+            member_at = self.start_at
+        else:
+            buf, fill, lines, done, member_at = resume
+            marks = [(0, fill, lines)]
         eof = False
         fd, pos, gen = -1, self.start_at, None
         skip = self.skip_lines
@@ -252,7 +286,9 @@ class TextReader(threading.Thread):
         if self.gz and not self.fasta:
             src = codec.GzipSource(self.path, fastq._pool(), fastq.ARENA.take, fastq.ARENA.give,
                                    post=lambda addr, nbytes: int(L.csh_count_newlines(addr, nbytes)))
-            gen = src.blocks(self.start_at) if self.stop_at is None else self._members_until(src, self.start_at, self.stop_at)
+            gen = src.blocks(member_at) if self.stop_at is None else self._members_until(src, self.start_at, self.stop_at)
+            if resume is not None and member_at >= src.size:  # (the BGZF run was the whole file)
+                gen = iter(())
         elif self.gz or self.sequential:
             if self.gz:  # (FASTA in a gzip file: the members still inflate in the pool)
                 src = codec.GzipSource(self.path, fastq._pool(), fastq.ARENA.take, fastq.ARENA.give)
@@ -298,6 +334,8 @@ class TextReader(threading.Thread):
                             eof = True
                             break
                         text, nbytes = item
+                        if self.gz and PROFILE:
+                            _count_inflate("host_blocks", 1)
                         if buf.size - fill < nbytes:
                             for f in copies:
                                 f.result()
@@ -396,14 +434,107 @@ class TextReader(threading.Thread):
             if buf is not None:
                 fastq.PINNED.give(buf)
             if gen is not None:
-                gen.close()
+                if hasattr(gen, "close"):
+                    gen.close()
                 src.close()
             if fd >= 0:
                 os.close(fd)
 
+    # -- device mode: BGZF blocks inflate into the inflater's buffers, the bookkeeping above mirrored on them -------------
+    def _refused(self, mapped, lo: int, hi: int, index: int):
+        """The inflater refused block ``index`` of the span [lo, hi): the host path decides.  What it raises for a corrupt
+        file today, it raises now; if it takes the span, the two decoders disagree, and that is an engine fault."""
+        out, _used = codec._inflate_span(mapped, lo, hi, 4 * (hi - lo), fastq.ARENA.take, fastq.ARENA.give)
+        fastq.ARENA.give(out)
+        raise RuntimeError(f"{self.path}: the device decoder disagrees with libdeflate: it refused BGZF block {index} of "
+                           f"the blocks at compressed offset {lo}, which libdeflate inflates without an error")
+
+    def _run_device(self):
+        from .inflater import SPAN
+        inf = self._make_inflater()
+        need = 4 * self.chunk_reads
+        est = 400
+        fh = open(self.path, "rb")
+        mm = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
+        mapped = np.frombuffer(mm, dtype=np.uint8)
+        buf = inf.take(int(self.chunk_reads * est * 1.25) + 2 * _BLOCK)
+        fill, lines, done, pos = 0, 0, 0, 0
+        marks: List[tuple] = []  # one per BGZF block behind buf[:fill]: (offset, ISIZE, newlines from the inflater)
+        resume = None
+        try:
+            while not self._halt:
+                ended = False
+                while lines < need and not ended:
+                    rows, end = codec.bgzf_index(mm, pos, pos + SPAN + (1 << 16))
+                    if not rows:  # the end of the file, a member that is not BGZF, or a block cut short
+                        ended = True
+                        break
+                    total = sum(r[2] for r in rows)  # (known beforehand: the ISIZE prefix sums are the output offsets)
+                    if buf.size - fill < total:
+                        bigger = inf.take(max(buf.size + buf.size // 2, fill + total))
+                        inf.copy(bigger, 0, buf, 0, fill)
+                        inf.give(buf)
+                        buf = bigger
+                    t0 = time.perf_counter()
+                    got, bad = inf.inflate(mapped, pos, rows, buf, fill)
+                    _tick("device_inflate", t0)
+                    if bad >= 0:
+                        self._refused(mm, pos, end, bad)
+                    for (_, _, isize, _), found in zip(rows, got):
+                        marks.append((fill, isize, int(found)))
+                        fill += isize
+                        lines += int(found)
+                    if PROFILE:
+                        _count_inflate("device_blocks", len(rows))
+                    pos = end
+                if lines < need:
+                    break  # the BGZF run has ended: less than one block of records is left
+                t0 = time.perf_counter()
+                cum, cut, at = 0, -1, 0
+                for at, (off, nbytes, found) in enumerate(marks):
+                    if cum + found >= need:
+                        cut = off + inf.after_kth_newline(buf, off, nbytes, need - cum)
+                        break
+                    cum += found
+                assert cut > 0
+                nxt = inf.take(max(buf.size, int(self.chunk_reads * est * 1.25) + 2 * _BLOCK))
+                carry = fill - cut
+                inf.copy(nxt, 0, buf, cut, carry)
+                block = TextBlock(None, cut, need // 4, done, dbuf=buf, owner=inf)
+                done += need // 4
+                est = max(64, cut // (need // 4) + 1)
+                off, nbytes, found = marks[at]  # the block the cut went through keeps its rest, the others move up
+                marks = [(0, off + nbytes - cut, found - (need - cum))] + [(o - cut, n, f) for o, n, f in marks[at + 1:]]
+                buf, fill, lines = nxt, carry, lines - need
+                _tick("cut+carry", t0)
+                if not self._put(block):
+                    block.release()
+                    return
+            if self._halt:
+                return
+            # End of the run: what is left goes to a pinned host buffer, and the host path finishes -- a foreign tail
+            # member, blank lines, a missing final newline, an empty last read are all its business, in one place.
+            hbuf = fastq.PINNED.take(fill + 2 * _BLOCK)
+            inf.to_host(hbuf, buf, 0, fill)
+            resume = (hbuf, fill, lines, done, pos)
+        finally:
+            if buf is not None:
+                inf.give(buf)
+            del mapped
+            try:
+                mm.close()
+            except BufferError:
+                pass
+            fh.close()
+            inf.close()
+        self._run(resume=resume)
+
     def run(self):
         try:
-            self._run()
+            if self._make_inflater is not None:
+                self._run_device()
+            else:
+                self._run()
         except BaseException as exc:
             self._put(fastq._Failure(exc))
 
@@ -654,6 +785,12 @@ class TextWorker(fanout.Worker):
 
     def submit(self, slot: int, item):
         b1, b2 = item
+        if b1.dbuf is not None or (b2 is not None and b2.dbuf is not None):
+            # a reader in device mode: the text is on the device already (a mate that came the host's way is copied by
+            # the same call: the copy goes by where each pointer lives)
+            self.text.submit_device(slot, b1.text_address(), b1.nbytes, b2.text_address() if b2 is not None else 0,
+                                    b2.nbytes if b2 is not None else 0, b1.n)
+            return item
         self.text.submit(slot, b1.buf, b1.nbytes, b2.buf if b2 is not None else None, b2.nbytes if b2 is not None else 0, b1.n)
         return item
 
@@ -812,6 +949,13 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
     if woven_in and shares is not None:
         raise ValueError("an interleaved input cannot be split between ranks")
     share = shares or [{}, {}]
+    make_inflater = None
+    if (switches.enabled("GPU_INFLATE") and len(devices) == 1 and shares is None and not woven_in and tp.demux is None):
+        # BGZF FASTQ inputs inflate on the device and stay there (each reader decides for its own file)
+        def make_inflater():
+            from .inflater import DeviceInflater
+            return DeviceInflater(devices[0])
+        share = [dict(s, inflater=make_inflater) for s in share]
     if woven_in:
         r1 = TextReader(args.input_file[0], 2 * chunk_reads, interleaved=True)
     else:
@@ -936,6 +1080,8 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         import sys
         with _prof_lock:
             print(json.dumps({"cutseq_profile": {k: round(v, 3) for k, v in sorted(_prof.items())},
-                              "seconds": round(totals["seconds"], 3)}), file=sys.stderr)
+                              "seconds": round(totals["seconds"], 3), "inflate": dict(_inflate_blocks)}), file=sys.stderr)
             _prof.clear()
+            for key in _inflate_blocks:
+                _inflate_blocks[key] = 0
     return totals

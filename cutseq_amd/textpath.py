@@ -139,6 +139,11 @@ class TextEngine:
         returns."""
         capi.check(self.L.cs_text_submit(self._h, slot, _address(text1), bytes1, _address(text2) or None, bytes2, n_records))
 
+    def submit_device(self, slot: int, dtext1: int, bytes1: int, dtext2: int = 0, bytes2: int = 0, n_records: int = 0) -> None:
+        """:meth:`submit` for texts that are on the engine's device already (``cs_text_submit_device``): ``dtext1`` /
+        ``dtext2`` are device addresses (0: no such mate), complete when the call is made."""
+        capi.check(self.L.cs_text_submit_device(self._h, slot, dtext1 or None, bytes1, dtext2 or None, bytes2, n_records))
+
     def wait(self, slot: int, first_record: int = 0, names=("mate 1", "mate 2")) -> abi.cs_text_result:
         """Blocks until the batch is formatted on the device.  Raises what the reference's reader would raise for a
         bad record.  Reads longer than the rows are not an error: they took the long-read kernel (``res.n_long``)."""

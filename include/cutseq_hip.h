@@ -582,6 +582,75 @@ void *cs_alloc_device(int device, size_t bytes);
 void cs_free_device(int device, void *p);
 int cs_copy_to_device(int device, void *dst, const void *src, size_t bytes);
 int cs_copy_to_host(int device, void *dst, const void *src, size_t bytes);
+/* device to device, both pointers on `device`; the ranges must not overlap.  Blocks until the copy is done. */
+int cs_copy_on_device(int device, void *dst, const void *src, size_t bytes);
+
+/* ---- text that is already on the device -------------------------------------------------------------------------
+ * cs_text_submit without the upload: dtext1 / dtext2 are device pointers on the cs_text's device that hold complete
+ * text when the call is made (cs_inflate_bgzf and the cs_copy_* calls block, so what they wrote is).  Everything else
+ * is cs_text_submit's: the same arguments, checks and errors, the same lifetime rule -- the texts stay untouched until
+ * cs_text_wait returns --, the same kernels behind it, and interleave, rename, info, compress and the too-long route
+ * work as they do there.  (The texts are copied into the slot's own buffers on the device, where cs_text_submit
+ * uploads them to; the copy goes by where each pointer lives, so the one mate of a pair that still is in host memory
+ * may be passed as it is.) */
+int cs_text_submit_device(cs_text *t, uint32_t slot, const void *dtext1, uint64_t bytes1, const void *dtext2,
+                          uint64_t bytes2, uint32_t n_records);
+
+/* The device twin of the host library's csh_after_kth_newline: *offset = the offset behind newline number k of
+ * dtext[0 .. nbytes) (device memory on `device`), 0 for k < 1, -1 when the text holds fewer than k.  Blocks. */
+int cs_dtext_after_kth_newline(int device, const void *dtext, uint64_t nbytes, int64_t k, int64_t *offset);
+
+/* ---- BGZF input inflated on the device ---------------------------------------------------------------------------
+ * A BGZF file (the htslib toolchain's .gz: `bgzip`) is a series of gzip members of at most 64 KiB of text, each with
+ * its compressed size in the header and CRC-32 and ISIZE in the trailer: the host knows every input and output offset
+ * before a bit is decoded.  It parses headers and trailers and hands over a table of blocks; one launch decodes them,
+ * one wavefront per block (RFC 1951 complete: stored, fixed and dynamic blocks, several per member), checks ISIZE and
+ * CRC-32 of every block on the device and counts its line ends in the same pass.
+ *
+ * A block describes the DEFLATE PAYLOAD only.  The decoder reads nothing outside comp[comp_off .. comp_off + comp_len)
+ * and writes nothing outside dtext[out_off .. out_off + out_len), whatever the bytes are; no alignment is asked of
+ * either offset.  A block that fails gets a verdict and leaves the other blocks of the call alone (its own output
+ * range holds unspecified bytes). */
+enum {
+  CS_INFLATE_OK = 0,
+  CS_INFLATE_ERR_BTYPE = 1,     /* block type 3                                                               */
+  CS_INFLATE_ERR_STORED = 2,    /* stored block: LEN / NLEN mismatch                                          */
+  CS_INFLATE_ERR_CODE = 3,      /* over-subscribed code, or an incomplete one where zlib refuses it; too many codes */
+  CS_INFLATE_ERR_REPEAT = 4,    /* code-length repeat without a predecessor (or past the last code)           */
+  CS_INFLATE_ERR_NO_EOB = 5,    /* no end-of-block code                                                       */
+  CS_INFLATE_ERR_SYMBOL = 6,    /* invalid symbol                                                             */
+  CS_INFLATE_ERR_INPUT = 7,     /* input exhausted                                                            */
+  CS_INFLATE_ERR_OUTPUT = 8,    /* output overrun: more text than out_len                                     */
+  CS_INFLATE_ERR_DISTANCE = 9,  /* distance too far: in front of the block's own text                         */
+  CS_INFLATE_ERR_ISIZE = 10,    /* less text than out_len                                                     */
+  CS_INFLATE_ERR_CRC = 11,      /* CRC-32 mismatch                                                            */
+  CS_INFLATE_ERR_TRAILING = 12  /* payload bytes left behind the final deflate block                          */
+};
+typedef struct cs_inflate_block {
+  uint64_t comp_off; /* the deflate payload: comp[comp_off .. comp_off + comp_len)                           */
+  uint64_t out_off;  /* its text: dtext[out_off .. out_off + out_len)                                        */
+  uint32_t comp_len;
+  uint32_t out_len;  /* ISIZE                                                                                 */
+  uint32_t crc32;    /* the trailer's                                                                         */
+  uint32_t reserved; /* 0                                                                                     */
+} cs_inflate_block;
+typedef struct cs_inflate_result {
+  int32_t verdict; /* CS_INFLATE_OK, or the verdict of the first block that failed */
+  uint32_t block;  /* ... and its index                                             */
+} cs_inflate_result;
+typedef struct cs_inflate cs_inflate;
+
+/* Device buffers for calls of up to max_comp_bytes compressed bytes and max_blocks blocks, and a stream. */
+int cs_inflate_create(int device, uint64_t max_comp_bytes, uint32_t max_blocks, cs_inflate **out);
+void cs_inflate_destroy(cs_inflate *h);
+/* Uploads comp[0 .. comp_bytes) (host memory, pinned for speed) and the table, decodes into dtext (device memory on the
+ * handle's device, dtext_cap bytes) and blocks until that is done.  lines_out[n_blocks]: '\n' per block's text (0 for a
+ * failed block); verdicts_out[n_blocks]: CS_INFLATE_* per block, may be NULL; *res: the first failing block, or OK.
+ * n_blocks == 0 is legal.  CS_ERR_ARG -- and nothing launched -- for a table entry that leaves comp[0 .. comp_bytes) or
+ * dtext[0 .. dtext_cap), and for more bytes or blocks than the handle was made for.  A failing block is NOT an error
+ * of the call (CS_OK, the verdict in *res).  One call at a time per handle. */
+int cs_inflate_bgzf(cs_inflate *h, const void *comp, uint64_t comp_bytes, const cs_inflate_block *blocks, uint32_t n_blocks,
+                    void *dtext, uint64_t dtext_cap, uint32_t *lines_out, int32_t *verdicts_out, cs_inflate_result *res);
 
 #ifdef __cplusplus
 }

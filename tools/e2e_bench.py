@@ -3,6 +3,9 @@
 
   python tools/e2e_bench.py [pairs] [workdir] [--forms plain_warm,plain_to_gz] [--tree DIR] [--keep] [--extra='-M 100']
 
+``--forms bgzf_to_gz`` (only when named) adds BGZF input: the same records bgzip-style, read with and without
+``CUTSEQ_GPU_INFLATE=1`` (the caller sets it), once cold and once warm.
+
 Writes a synthetic paired data set once (plain text and multi-member gzip), then runs
 ``cutseq_amd.run.main`` on it: plain -> plain twice (the second run has warm buffers and page cache),
 gz -> gz once.  Prints one JSON object.  Not the headline metric: bench.py reports the HBM-resident rate.
@@ -68,7 +71,8 @@ def main():
     out["gunzip_s"] = round(time.perf_counter() - t0, 2)
 
     def run(tag, inputs, outputs):
-        if opts.forms and tag not in opts.forms and not (tag == "plain_cold" and "plain_warm" in opts.forms):
+        if opts.forms and tag not in opts.forms and not (tag == "plain_cold" and "plain_warm" in opts.forms) \
+                and not (tag == "bgzf_to_gz_warm" and "bgzf_to_gz" in opts.forms):
             return
         for old in work.glob("o[12].fastq"), work.glob("s[12].fastq"), work.glob("gzout_*"):
             for f in old:  # a run writes NEW files: freeing the previous run's gigabytes of tmpfs pages is not its job
@@ -91,6 +95,14 @@ def main():
     run("gz_to_gz", gz_in, ["-O", str(work / "gzout")])
     run("gz_to_gz_warm", gz_in, ["-O", str(work / "gzout")])
     run("plain_to_gz", plain_in, ["-O", str(work / "gzout")])
+    if opts.forms and "bgzf_to_gz" in opts.forms:
+        # bgzip'd input (what CUTSEQ_GPU_INFLATE=1 inflates on the device): written with the tests' BGZF writer -- there
+        # is no bgzip here --, 65 280 bytes of text per block at zlib level 6 (bgzip's default), the pool compressing
+        bgzf_in = [str(work / f"bgzf_R{m}.fastq.gz") for m in (1, 2)]
+        if not (opts.keep and all(Path(p).exists() for p in bgzf_in)):
+            write_bgzf(plain_in, bgzf_in)
+        run("bgzf_to_gz", bgzf_in, ["-O", str(work / "gzout")])
+        run("bgzf_to_gz_warm", bgzf_in, ["-O", str(work / "gzout")])
     # the usual sequencer output: ONE gzip member per file (gzip -1 of the first half of the records), which no
     # reader can enter in the middle
     n_single = n // 2
@@ -111,6 +123,25 @@ def main():
     out["single_member_gz_to_gz"]["pairs"] = n_single
     n = n_all
     finish(work, out, opts.keep)
+
+
+def write_bgzf(sources, targets, level=6, piece=64 * 65280):
+    sys.path.insert(0, str(ROOT / "tests"))
+    import bgzf_rule
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(len(os.sched_getaffinity(0))) as pool:
+        for src, dst in zip(sources, targets):
+            with open(src, "rb") as fin, open(dst, "wb") as fout:
+                pending = []
+                while True:
+                    data = fin.read(piece)
+                    if data:
+                        pending.append(pool.submit(bgzf_rule.bgzf, data, 65280, level))
+                    while pending and (not data or len(pending) > 64):
+                        fout.write(pending.pop(0).result())
+                    if not data:
+                        break
+                fout.write(bgzf_rule.EOF_MARKER)
 
 
 def finish(work, out, keep):
