@@ -15,6 +15,7 @@ CS_LEN_SKIP = 0xFFFF
 CS_MAX_READ = 1 << 24
 
 CS_OP_ADAPTER, CS_OP_CUT, CS_OP_QTRIM, CS_OP_DEMUX, CS_OP_NTRIM, CS_OP_NEXTSEQ, CS_OP_SHORTEN = 1, 2, 3, 4, 5, 6, 7
+CS_OP_POLYA = 8  # cutadapt's PolyATrimmer (--poly-a); cs_op.reversed = 1: the head form (poly-T at the 5' end)
 # cutoff + base of a quality-trimming op: CS_OP_QTRIM is clamped to this range, CS_OP_NEXTSEQ refused outside it
 CS_Q_SUM_LOW, CS_Q_SUM_HIGH = -1, 256
 CS_DEMUX_NONE = 0xFF

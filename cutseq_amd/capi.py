@@ -22,7 +22,7 @@ EXPORTS = (
     "cs_text_create", "cs_text_destroy", "cs_text_submit", "cs_text_wait", "cs_text_routes", "cs_text_fetch",
     "cs_text_info", "cs_text_fetch_info", "cs_text_create_interleaved", "cs_text_set_rename",
     "cs_copy_on_device", "cs_text_submit_device", "cs_dtext_after_kth_newline", "cs_inflate_create", "cs_inflate_destroy",
-    "cs_inflate_bgzf",
+    "cs_inflate_bgzf", "cs_polya_bp_fetch",
 )
 
 
@@ -82,6 +82,9 @@ def load() -> C.CDLL:
     L.cs_xflag_counts_fetch.argtypes = [vp, vp, i32]
     L.cs_text_discards.restype = i32
     L.cs_text_discards.argtypes = [vp, C.c_uint32, vp]
+    if hasattr(L, "cs_polya_bp_fetch"):  # (an older build loaded through CUTSEQ_HIP_LIB for an A/B has none)
+        L.cs_polya_bp_fetch.restype = i32
+        L.cs_polya_bp_fetch.argtypes = [vp, vp, i32]
     L.cs_plan_destroy.restype = None
     L.cs_plan_destroy.argtypes = [vp]
     L.cs_engine_create.restype = i32

@@ -138,6 +138,7 @@ struct cs_engine {
   bool ends = false;     // some CS_OP_QTRIM op has a front cutoff, or the plan has a CS_OP_NTRIM op (FILT_ENDS kernels)
   bool nextseq = false;  // the plan has a CS_OP_NEXTSEQ op: `ends` is set too (the ENDS walks), tile kernels FILT_NEXTSEQ
   bool shorten = false;  // the plan has a CS_OP_SHORTEN op: `ends` is set too (the ENDS walks), tile kernels FILT_SHORTEN
+  bool polya = false;    // the plan has a CS_OP_POLYA op: the FILT_POLYA tile kernels, the POLYA long-read and info walks
   int n_cus = 256;
   uint32_t n_table_ops = 1;
   uint32_t col_dwords = 0;   // per-wave DP scratch the plan needs (resolve kernel)
@@ -257,6 +258,9 @@ int build_dev_op(const cs_op &in, csdev::DevOp &out, int index, int mate) {
     }
     case CS_OP_NTRIM:
       break;
+    case CS_OP_POLYA:  // one field: the tail form (0) or the head form (1)
+      if (op.reversed > 1) return fail(CS_ERR_ARG, "mate %d op %d: poly-A op with reversed = %u", mate, index, op.reversed);
+      break;
     case CS_OP_SHORTEN:
       // Every int32 is a length (include/cutseq_hip.h).  Nothing to refuse, and no test here that negates the field: the
       // kernels form |length| as 0u - (uint32_t)length, which is 2^31 for INT32_MIN, and take the minimum with n unsigned.
@@ -302,6 +306,9 @@ const void *kernel_variant(const cs_engine *eng) {
 }
 template <int MODE>
 const void *kernel_of(const cs_engine *eng) {  // plans with filters take the kernels that decide them
+  // CS_OP_POLYA: the op's own instantiations -- on the lowest rung for a plan that adds nothing else, else on the highest
+  if (eng->polya && !eng->ends && !eng->filters) return kernel_variant<MODE, csdev::FILT_NONE | csdev::FILT_POLYA>(eng);
+  if (eng->polya) return kernel_variant<MODE, csdev::FILT_SHORTEN | csdev::FILT_POLYA>(eng);
   if (eng->shorten) return kernel_variant<MODE, csdev::FILT_SHORTEN>(eng);  // (every read-end op's code plus CS_OP_SHORTEN)
   if (eng->nextseq) return kernel_variant<MODE, csdev::FILT_NEXTSEQ>(eng);  // (the read-end ops' code plus CS_OP_NEXTSEQ)
   if (eng->ends) return kernel_variant<MODE, csdev::FILT_ENDS>(eng);  // (... and whatever filters the plan has)
@@ -1042,6 +1049,7 @@ int cs_engine_create(const cs_plan *plan, int device, uint32_t n_slots, uint32_t
         eng->ends = true;
       if (d.op.kind == CS_OP_NEXTSEQ) eng->nextseq = true;
       if (d.op.kind == CS_OP_SHORTEN) eng->shorten = true;
+      if (d.op.kind == CS_OP_POLYA) eng->polya = true;
       if (d.op.kind == CS_OP_DEMUX && d.filter_mode) {
         // the resolve kernel runs the barcodes' own ops, one column per lane
         has_long_demux = true;
@@ -1147,7 +1155,7 @@ int cs_engine_create(const cs_plan *plan, int device, uint32_t n_slots, uint32_t
     ENG_TRY(hipMemcpyToSymbol(HIP_SYMBOL(csdev::c_plans), &dp, sizeof(csdev::DevPlan),
                               (size_t)eng->plan_slot * sizeof(csdev::DevPlan), hipMemcpyHostToDevice));
   }
-  ENG_TRY(hipMalloc(&eng->d_stats, csdev::kStatsBlockWords * 8));  // (the two cs_stats, then the XST_* words)
+  ENG_TRY(hipMalloc(&eng->d_stats, csdev::kStatsBlockWords * 8));  // (the two cs_stats, the XST_* words, the poly-A words)
   ENG_TRY(hipMemset(eng->d_stats, 0, csdev::kStatsBlockWords * 8));
   eng->slots.resize(n_slots);
   const size_t bytes = (size_t)max_reads * max_stride;
@@ -1319,6 +1327,21 @@ int cs_xflag_counts_fetch(cs_engine *eng, uint64_t counts[2][CS_X_COUNTS], int r
     counts[m][1] = rest[m][csdev::XST_TOO_LONG];
     counts[m][2] = rest[m][csdev::XST_TOO_MANY_EE];
   }
+  return CS_OK;
+}
+
+int cs_polya_bp_fetch(cs_engine *eng, uint64_t bp[2], int reset) {
+  if (!eng || !bp) return fail(CS_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(eng->device));
+  for (Lane &ln : eng->lanes)
+    if (ln.used) HIP_TRY(hipStreamWaitEvent(eng->stream, ln.done, 0));
+  unsigned long long words[2];
+  unsigned long long *src = eng->d_stats + csdev::kPolyABase;
+  HIP_TRY(hipMemcpyAsync(words, src, sizeof words, hipMemcpyDeviceToHost, eng->stream));
+  if (reset) HIP_TRY(hipMemsetAsync(src, 0, sizeof words, eng->stream));
+  HIP_TRY(hipStreamSynchronize(eng->stream));
+  bp[0] = words[0];
+  bp[1] = words[1];
   return CS_OK;
 }
 
@@ -2041,7 +2064,9 @@ static int text_submit_from(cs_text *t, uint32_t slot, const void *text1, uint64
       la.plan_slot = (uint32_t)eng->plan_slot;
       la.mate = m;
       la.gate = &s.d_meta->err;
-      if (eng->ends)  // (a front cutoff, a CS_OP_NTRIM, _NEXTSEQ or _SHORTEN op: the walk that knows them, with every filter)
+      if (eng->polya)  // (a CS_OP_POLYA op: the walk that knows it and everything below)
+        hipLaunchKernelGGL(cslong::long_kernel_polya, dim3(256), dim3(64), 0, st, la);
+      else if (eng->ends)  // (a front cutoff, a CS_OP_NTRIM, _NEXTSEQ or _SHORTEN op: the walk that knows them, with every filter)
         hipLaunchKernelGGL((cslong::long_kernel<true, true>), dim3(256), dim3(64), 0, st, la);
       else if (eng->filters & (CS_X_TOO_LONG | CS_X_TOO_MANY_EE))
         hipLaunchKernelGGL(cslong::long_kernel<true>, dim3(256), dim3(64), 0, st, la);
@@ -2110,7 +2135,11 @@ static int text_submit_from(cs_text *t, uint32_t slot, const void *text1, uint64
       ia.cap = t->info_cap;
       HIP_TRY(hipMemsetAsync(s.d_imeta, 0, sizeof(csinfo::InfoMeta), rs));
       const dim3 rec_grid((n_records + 63u) / 64u);
-      if (eng->ends && eng->info_max_m <= 48u)
+      if (eng->polya && eng->info_max_m <= 48u)
+        LAUNCH_NAMED(csinfo::info_record_polya<48>, rec_grid, dim3(64), fa, t->tp, ia);
+      else if (eng->polya)
+        LAUNCH_NAMED(csinfo::info_record_polya<CS_MAX_ADAPTER>, rec_grid, dim3(64), fa, t->tp, ia);
+      else if (eng->ends && eng->info_max_m <= 48u)
         LAUNCH_NAMED((csinfo::info_record<48, true>), rec_grid, dim3(64), fa, t->tp, ia);
       else if (eng->ends)
         LAUNCH_NAMED((csinfo::info_record<CS_MAX_ADAPTER, true>), rec_grid, dim3(64), fa, t->tp, ia);

@@ -137,10 +137,11 @@ struct Recorder {  // what info_record keeps of a walk: every match, and the byt
   }
   __device__ __forceinline__ void cut(const cs_op &, int, int) {}
   __device__ __forceinline__ void quality_trimmed(int) {}
+  __device__ __forceinline__ void polya_trimmed(int) {}  // (cutadapt's PolyATrimmer writes no row: the final read narrows)
 };
 
-template <int kMaxM, bool ENDS = false, class... Rename>
-__global__ void __launch_bounds__(64) info_record(FormatArgs a, TextParams tp, InfoArgs ia, Rename... rn) {
+template <int kMaxM, bool ENDS, bool POLYA, class... Rename>
+__device__ __forceinline__ void info_record_body(FormatArgs a, TextParams tp, InfoArgs ia, Rename... rn) {
   if (a.meta->err != ~0ull) return;
   const uint32_t r = blockIdx.x * 64u + threadIdx.x;
   if (r >= a.n) return;
@@ -151,7 +152,7 @@ __global__ void __launch_bounds__(64) info_record(FormatArgs a, TextParams tp, I
   const ReadView v = cstext::read_view(a, 0, r);  // what the trimming kernels made of the record
   const uint32_t per_base = ia.no_qual ? 1u : 2u;
   Recorder ev{ia.match + (size_t)r * ia.n_adapters, ia.n_adapters, ia.uniq_flags, v.flags, per_base, kMaxM};
-  const cslong::Walk w = cslong::walk_chain<kMaxM, ENDS>(plan, 0, env, a.text[0] + rc.seq_off, a.text[0] + rc.qual_off,
+  const cslong::Walk w = cslong::walk_chain<kMaxM, ENDS, POLYA>(plan, 0, env, a.text[0] + rc.seq_off, a.text[0] + rc.qual_off,
                                                    (int)(slot != cstext::kNotLong ? a.lrec[0][slot].len : (uint32_t)rc.len), ev);
   // the table must not disagree with the records next to it
   if ((uint32_t)w.s != v.start || (uint32_t)w.e != v.stop || w.flags != v.flags) cstext::report(a.meta, r, ERR_INFO_MISMATCH);
@@ -170,6 +171,16 @@ __global__ void __launch_bounds__(64) info_record(FormatArgs a, TextParams tp, I
   out.n_matches = (uint32_t)w.n_matches;
   out.bytes = row_bytes;
   ia.rec[r] = out;
+}
+
+template <int kMaxM, bool ENDS = false, class... Rename>
+__global__ void __launch_bounds__(64) info_record(FormatArgs a, TextParams tp, InfoArgs ia, Rename... rn) {
+  info_record_body<kMaxM, ENDS, false>(a, tp, ia, rn...);
+}
+// the instantiations for plans with a CS_OP_POLYA op (cslong::walk_chain's POLYA walk)
+template <int kMaxM, class... Rename>
+__global__ void __launch_bounds__(64) info_record_polya(FormatArgs a, TextParams tp, InfoArgs ia, Rename... rn) {
+  info_record_body<kMaxM, true, true>(a, tp, ia, rn...);
 }
 
 __global__ void __launch_bounds__(256) info_sizes(FormatArgs a, InfoArgs ia) {

@@ -227,6 +227,26 @@ __device__ __forceinline__ int quality_stop_nextseq(const cs_op &op, const uint8
   return stop;
 }
 
+// cutadapt poly_a_trim_index (CS_OP_POLYA) on seq[0, n): how many bases stay -- of the front for the tail form, of the
+// back for the head form (`head`: poly-T, walked from the 5' end).  The loop of include/cutseq_hip.h with the error
+// count folded into the score (errors * 5 <= l  <=>  5 * score >= 2 * l) and its two exits: no later position can beat
+// the best score, or qualify.  |score| <= 2 * CS_MAX_READ = 2^25: an int.
+__device__ __forceinline__ int polya_keep(const uint8_t *seq, int n, bool head) {
+  static_assert(5ll * 3 * CS_MAX_READ < (1ll << 31), "polya_keep: 5 * (score + bases left) in an int");
+  const uint8_t match = head ? 0x54u : 0x41u;
+  int score = 0, best = 0, index = n;
+  for (int l = 1; l <= n; ++l) {  // l: the candidate's length
+    score += seq[head ? l - 1 : n - l] == match ? 1 : -2;
+    if (score > best && 5 * score >= 2 * l) {
+      best = score;
+      index = n - l;
+    }
+    const int reach = score + (n - l);  // the score of the whole rest matching
+    if (reach <= best || 5 * reach < 2 * n) break;
+  }
+  return index > n - 3 ? n : index;  // tails shorter than 3 are ignored
+}
+
 // Where a demultiplexing table keeps the first `depth` bases of q[0, n) -- read from the 5' end, or backwards from the
 // 3' end -- : the block of the prefixes of min(n, depth) bases, then the prefix in base 5 (A, C, G, T, anything else).
 __device__ __forceinline__ uint32_t prefix_index(const uint8_t *q, int n, int depth, bool from_end, bool fold) {
@@ -257,9 +277,11 @@ struct Walk {  // a read on its way through the chain
 //   cut(op, off, c)            a cutter took c bases at off
 //   quality_trimmed(k)         the quality trimmer took k bases
 //   demux(d, v, seq, w)        a CS_OP_DEMUX op, the caller's to apply (Events::kDemux; compiled out where false)
+//   polya_trimmed(k)           a CS_OP_POLYA op took k bases (POLYA instantiations only)
 // ENDS: the instantiation for plans with a front cutoff, a CS_OP_NTRIM, CS_OP_NEXTSEQ or CS_OP_SHORTEN op (cs_engine::ends), the only
-// one that holds their code; every other plan runs the walk it ran before they came.
-template <int kMaxM, bool ENDS, class Events>
+// one that holds their code; every other plan runs the walk it ran before they came.  POLYA: likewise for plans with a
+// CS_OP_POLYA op (cs_engine::polya); it comes with ENDS, whose walk is the one that knows every op.
+template <int kMaxM, bool ENDS, bool POLYA = false, class Events>
 __device__ __forceinline__ Walk walk_chain(const DevPlan *plan, int mate, const Env &v, const uint8_t *seq, const uint8_t *qual,
                                            int len, Events &ev) {
   Walk w = {0, len, 0u, 0};
@@ -326,6 +348,15 @@ __device__ __forceinline__ Walk walk_chain(const DevPlan *plan, int mate, const 
         ev.quality_trimmed(n - stop);
         w.e = w.s + stop;
       }
+    } else if (op.kind == CS_OP_POLYA) {  // cutadapt's PolyATrimmer: the tail (reversed: the poly-T head) goes
+      if constexpr (POLYA) {
+        const int keep = polya_keep(seq + w.s, n, op.reversed != 0);
+        ev.polya_trimmed(n - keep);
+        if (op.reversed)
+          w.s = w.e - keep;
+        else
+          w.e = w.s + keep;
+      }
     } else if (op.kind == CS_OP_SHORTEN) {  // cutadapt's Shortener: min(n, |length|) bases stay, first or (< 0) last ones
       if constexpr (ENDS) {
         // 32 bits against 32 bits: intervals here exceed 16 bits, and |INT32_MIN| exists as an unsigned value only
@@ -370,6 +401,7 @@ struct LongEvents {  // what long_kernel keeps of a walk besides the interval an
   static constexpr bool kDemux = true;
   unsigned long long *stats;
   uint32_t bc = CS_DEMUX_NONE, cap_off = 0, cap_len = 0, cap2_off = 0, cap2_len = 0, qtrimmed = 0;
+  uint32_t polya = 0;  // (POLYA instantiation only; no other walk calls polya_trimmed)
 
   __device__ __forceinline__ bool adapter_runs(const cs_op &) const { return true; }
   __device__ __forceinline__ void adapter_matched(const cs_op &op, const Walk &, int, int, int) {
@@ -385,6 +417,7 @@ struct LongEvents {  // what long_kernel keeps of a walk besides the interval an
     cap2_len = two ? (uint32_t)c : cap2_len;
   }
   __device__ __forceinline__ void quality_trimmed(int k) { qtrimmed += (uint32_t)k; }
+  __device__ __forceinline__ void polya_trimmed(int k) { polya += (uint32_t)k; }
 
   __device__ __forceinline__ void demux(const DevOp &d, const Env &v, const uint8_t *seq, Walk &w) {
     const cs_op &op = d.op;
@@ -445,8 +478,9 @@ struct LongEvents {  // what long_kernel keeps of a walk besides the interval an
 
 // MORE: the instantiation that also decides TooLong and TooManyExpectedErrors (plans with cs_plan_set_max_length or
 // cs_plan_set_max_ee); every other plan runs the kernel it ran before those filters came.
-template <bool MORE, bool ENDS = false>
-__global__ void __launch_bounds__(64) long_kernel(LongArgs a) {
+// POLYA: the walk that knows CS_OP_POLYA, and its counter.
+template <bool MORE, bool ENDS, bool POLYA>
+__device__ __forceinline__ void long_body(LongArgs a) {
   if (a.gate && *a.gate != ~0ull) return;
   const DevPlan *plan = &csdev::c_plans[a.plan_slot];
   const Env v(plan);
@@ -455,7 +489,7 @@ __global__ void __launch_bounds__(64) long_kernel(LongArgs a) {
     const LongRec lr = a.rec[it];
     const uint8_t *seq = a.text + lr.seq_off;
     LongEvents ev{a.stats};
-    const Walk w = walk_chain<CS_MAX_ADAPTER, ENDS>(plan, a.mate, v, seq, a.text + lr.qual_off, (int)lr.len, ev);
+    const Walk w = walk_chain<CS_MAX_ADAPTER, ENDS, POLYA>(plan, a.mate, v, seq, a.text + lr.qual_off, (int)lr.len, ev);
     uint32_t xflags = 0;
     if (plan->max_n_on) {  // TooManyN on the final interval: the read's own bytes, up to CS_MAX_READ of them
       uint32_t nn = 0;
@@ -501,7 +535,18 @@ __global__ void __launch_bounds__(64) long_kernel(LongArgs a) {
     atomicAdd(&a.stats[csdev::ST_QTRIM_BP], (unsigned long long)ev.qtrimmed);
     if (w.flags & CS_F_TOO_SHORT) atomicAdd(&a.stats[csdev::ST_TOO_SHORT], 1ull);
     if (w.flags & CS_F_UNTRIMMED) atomicAdd(&a.stats[csdev::ST_UNTRIMMED], 1ull);
+    if constexpr (POLYA) {  // (the mate's word behind both mates' XST_* words, reached from this mate's)
+      unsigned long long *polya = a.xstats + (2 - a.mate) * csdev::kXStatWords + a.mate;
+      if (ev.polya) atomicAdd(polya, (unsigned long long)ev.polya);
+    }
   }
 }
+
+template <bool MORE, bool ENDS = false>
+__global__ void __launch_bounds__(64) long_kernel(LongArgs a) {
+  long_body<MORE, ENDS, false>(a);
+}
+// the instantiation for plans with a CS_OP_POLYA op: every filter, every read-end op, and that op
+__global__ void __launch_bounds__(64) long_kernel_polya(LongArgs a) { long_body<true, true, true>(a); }
 
 }  // namespace cslong

@@ -29,6 +29,8 @@
 //          forward walk from the 5' end.  NTRIM (FILT_ENDS kernels only): the runs of 'N' at both ends of [s, e)
 //   SHORTEN (FILT_SHORTEN kernels only): min(n, |length|) bases stay, from the 5' end or, length < 0, from the 3' end
 //   NEXTSEQ (FILT_NEXTSEQ kernels and above only): QTRIM's 3' walk with the read's bases beside its qualities, a 'G' adds 1
+//   POLYA (FILT_POLYA kernels only): cutadapt's poly-A walk, a running score with a rate condition, as a maximum over
+//          (score, position) keys; the wave walks: the first 64 bases of 16 reads a turn, tails four reads a turn
 //
 // No block-wide barrier is needed after staging.  Result: 8 bytes per read.  Integer work: no MFMA.
 
@@ -2458,7 +2460,9 @@ static_assert(sizeof(cs_stats) == kStatWords * 8, "cs_stats layout");
 // keep their size): word kXStatBase + mate * kXStatWords + XST_*; cs_xflag_counts_fetch reads them.
 enum { XST_TOO_LONG = 0, XST_TOO_MANY_EE, kXStatWords };
 constexpr int kXStatBase = 2 * kStatWords;
-constexpr int kStatsBlockWords = kXStatBase + 2 * kXStatWords;
+// ... and behind those the bases CS_OP_POLYA ops removed, one word per mate (cs_polya_bp_fetch)
+constexpr int kPolyABase = kXStatBase + 2 * kXStatWords;
+constexpr int kStatsBlockWords = kPolyABase + 2;
 
 // ---- TooManyN (cs_plan_set_max_n, cutadapt --max-n): 'N' / 'n' bases in [s, e) of a row, and the filter's rule.
 // Raw bytes (ASCII rows in HBM, or a raw tile: its case folding only turns 'n' into 'N'): exact zero-byte test on
@@ -2569,14 +2573,25 @@ enum { MODE_SCAN = 0, MODE_RESOLVE = 1 };
 // of the 16 FILT 3 / FILT 4 kernels (the coded wide scan kernel: 9 -> 11 spilled VGPRs; profiles/length_ab.log), and
 // the same kind of change cost the -q 20,20 --trim-n plan 1.1 % when CS_OP_NEXTSEQ was tried there.  Here every kernel a
 // plan without the op runs is the parent's, figure for figure.
-enum { FILT_NONE = 0, FILT_MAXN = 1, FILT_ALL = 2, FILT_ENDS = 3, FILT_NEXTSEQ = 4, FILT_SHORTEN = 5 };
-template <bool CODED, bool WIDE, int MODE, int FILT>
+//
+// FILT_POLYA is no rung but a bit on top of one: the instantiations that hold CS_OP_POLYA (cutadapt --poly-a).  On the
+// ladder the op would sit above FILT_SHORTEN, and a plain --poly-a plan -- the common one: the RNA presets with nothing
+// else switched on -- would run the read-end ops' and the filters' code, 17-20 % of the trimming kernels' throughput
+// (README), for an op that needs none of it.  So the bit exists on two rungs only: FILT_NONE | FILT_POLYA for plans
+// whose only addition is the op, FILT_SHORTEN | FILT_POLYA for plans that have it next to any filter or read-end op.
+// Sixteen instantiations; the kernels of a plan without the op are the ones it ran before, figure for figure
+// (profiles/poly_a_ab.log).  Inside the kernel FILT means the rung.
+enum { FILT_NONE = 0, FILT_MAXN = 1, FILT_ALL = 2, FILT_ENDS = 3, FILT_NEXTSEQ = 4, FILT_SHORTEN = 5, FILT_POLYA = 8 };
+template <bool CODED, bool WIDE, int MODE, int FILT_ARG>
 __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) trim_kernel(KArgs a) {
   if (a.gate && *a.gate != ~0ull) return;  // (wave-uniform: one wave per block)
   const DevPlan *plan = &c_plans[a.plan_slot];
   extern __shared__ uint32_t smem[];
   constexpr int TILE = kWave;  // blocks are one wave (the host launches 64 threads, __launch_bounds__ says so)
   constexpr bool SCAN = MODE != MODE_RESOLVE;
+  constexpr int FILT = FILT_ARG & (FILT_POLYA - 1);      // the rung of the ladder
+  constexpr bool POLYA = (FILT_ARG & FILT_POLYA) != 0;   // ... and whether CS_OP_POLYA's code is here
+  uint32_t polya_bp = 0;  // bases this lane's CS_OP_POLYA ops removed, all tiles (POLYA only; dead code elsewhere)
   const int tid = threadIdx.x;
   const int mate = blockIdx.y;
   const MateArgs &ma = a.mate[mate];
@@ -3670,6 +3685,167 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
           e = s + stop;
         }
       }
+    } else if (kind == CS_OP_POLYA) {
+      if constexpr (POLYA) {
+        // cutadapt's PolyATrimmer (--poly-a), poly_a_trim_index: from the read's 3' end a base 'A' adds 1 to the score,
+        // any other byte takes 2 and counts as an error; a position qualifies while errors * 5 <= length, and the FIRST
+        // qualifying position of the highest score > 0 is where the tail begins; tails shorter than 3 stay.
+        // With score = length - 3 * errors the rate test is 5 * score >= 2 * length: no error count is kept, and the
+        // result is a maximum over (score << kPosBits | position) keys, CS_OP_QTRIM's key (a lower position wins only
+        // with a higher score).  Unlike that walk this one has no "sum < 0" end: it is over when no later position can
+        // beat the best score (score + bases left <= best) or qualify (5 * (score + bases left) < 2 * n), on random
+        // bases after about 0.27 n of them.  Every read walks, so the WAVE walks from the start, in rounds of 64 bases
+        // (16 dwords) of a read.  The FIRST round of every read is served statically, 16 reads at a time, four lanes
+        // each: lane q of a quad takes the read's dwords 4q .. 4q + 3 below its top one, scores by a prefix scan over
+        // the quad, the best key a quad maximum -- four turns a tile, and a 150-base read without a tail is settled.
+        // Reads that go on (tails, long rows) are then served four at a time, 16 lanes each, a dword a lane, as
+        // CS_OP_QTRIM serves its live reads: scores by a prefix scan over the group, the best key a row maximum.
+        // The read's OWN bytes decide on every tile, as for CS_OP_NEXTSEQ and for its reasons: case matters ('a' is an
+        // error, raw tiles fold it), and a lane serves other lanes' reads.
+        // The head form (reversed: poly-T at the 5' end) is the same walk on the mirrored row: position p of the row is
+        // position 2047 - p, so dword d is dword 511 - d with its bytes swapped, [s, e) is [2048 - e, 2048 - s), and the
+        // first position in walk order is again the highest one.  |score| <= 2 * CS_MAX_STRIDE: the key fits an int.
+        constexpr int kPosBits = 11, kTop = (1 << kPosBits) - 1;
+        static_assert(CS_MAX_STRIDE <= kTop + 1 && (kTop & 3) == 3 && 2ll * CS_MAX_STRIDE < (1ll << (31 - kPosBits)),
+                      "POLYA key: score << kPosBits | (mirrored) position must fit an int");
+        const bool rev = op.reversed != 0;            // wave-uniform
+        const uint32_t match = rev ? 0x54u : 0x41u;   // 'T' / 'A', upper case only
+        const bool live = on && n > 0;
+        const int ms = rev ? (kTop + 1) - e : s;      // the interval in walk coordinates: [ms, ms + n)
+        const int p_last = ms + n - 1;
+        int sum = 0, bestkey = kTop;  // score 0 at a position beyond every real one: only scores > 0 replace it
+        int dw = max(p_last, 0) >> 2;  // next dword of this lane's read (walk coordinates)
+        bool run = live;
+        const int grp = lane >> 4, idx = lane & 15;
+        unsigned long long todo = __ballot(run);
+        auto settled = [&](int score, int best, int left) -> bool {  // no base left, or none that could change the result
+          return left <= 0 || score + left <= best || 5 * (score + left) < 2 * n;
+        };
+        for (int turn = 0; turn < 4; ++turn) {  // the first round, lanes 16 * turn .. 16 * turn + 15; wave-uniform
+          if (((todo >> (16 * turn)) & 0xffffull) == 0ull) continue;
+          const int from = 16 * turn + (lane >> 2), quad = lane & 3;
+          const bool r_run = ((todo >> from) & 1ull) != 0ull;
+          const uint32_t r_pk = (uint32_t)__shfl((int)((uint32_t)ms | ((uint32_t)max(p_last, 0) << 12) | ((uint32_t)dw << 23)), from, 64);
+          const uint32_t r_gr = SCAN ? row0 + (uint32_t)from : (uint32_t)__shfl((int)gr, from, 64);
+          const int r_ms = (int)(r_pk & 0xfffu), r_last = (int)((r_pk >> 12) & 0x7ffu), r_dw = (int)(r_pk >> 23);
+          const uint32_t *rowp = ma.seq + (size_t)r_gr * a.stride_dw;
+          const int d0 = r_dw - 4 * quad;  // this lane's four dwords: d0 down to d0 - 3
+          uint32_t g4[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {  // (a dword inside the interval's dwords, and so is its mirror image: inside the row)
+            const int dd = d0 - j;
+            g4[j] = 0;
+            if (r_run && dd >= (r_ms >> 2)) g4[j] = rev ? __builtin_bswap32(rowp[(kTop >> 2) - dd]) : rowp[dd];
+          }
+          int sc[16], tot = 0;  // the scores inside the lane's 16 bases, 3' -> 5'; bases outside the interval add nothing
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int b = 3; b >= 0; --b) {
+              const int p = 4 * (d0 - j) + b;
+              const bool in = r_run && p >= r_ms && p <= r_last;
+              tot += !in ? 0 : ((g4[j] >> (b * 8)) & 0xffu) == match ? 1 : -2;
+              sc[4 * j + 3 - b] = tot;
+            }
+          int incl = tot;  // inclusive scan over the quad (the read's score starts at 0: this is its first round)
+          const int up1 = __builtin_amdgcn_update_dpp(0, incl, 0x90 /* quad_perm:[0,0,1,2] */, 0xf, 0xf, false);
+          incl += quad >= 1 ? up1 : 0;
+          const int up2 = __builtin_amdgcn_update_dpp(0, incl, 0x44 /* quad_perm:[0,1,0,1] */, 0xf, 0xf, false);
+          incl += quad >= 2 ? up2 : 0;
+          const int off = incl - tot;
+          int kmax = 0;
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int b = 3; b >= 0; --b) {
+              const int p = 4 * (d0 - j) + b, s1 = off + sc[4 * j + 3 - b];
+              const bool q = r_run && p >= r_ms && p <= r_last && s1 > 0 && 5 * s1 >= 2 * (r_last - p + 1);
+              kmax = max(kmax, q ? ((s1 << kPosBits) | p) : 0);
+            }
+          kmax = max(kmax, __builtin_amdgcn_update_dpp(0, kmax, 0xB1 /* quad_perm:[1,0,3,2] */, 0xf, 0xf, false));
+          kmax = max(kmax, __builtin_amdgcn_update_dpp(0, kmax, 0x4E /* quad_perm:[2,3,0,1] */, 0xf, 0xf, false));
+          // back to the reads' own lanes: lane 16 * turn + i was served by quad i, whose last lane has the read's score
+          const int back = 4 * (lane & 15) + 3;
+          const int g_key = __shfl(kmax, back, 64);
+          const int g_sum = __shfl(incl, back, 64);
+          if ((lane >> 4) == turn && run) {
+            bestkey = max(bestkey, g_key);
+            sum = g_sum;
+            dw -= 16;
+            run = !settled(sum, bestkey >> kPosBits, 4 * dw + 4 - ms);
+          }
+        }
+        todo = __ballot(run);
+        while (todo) {  // wave-uniform
+          unsigned long long tt = todo;
+          const int l0 = __builtin_ctzll(tt);
+          tt &= tt - 1ull;
+          const int l1 = tt ? __builtin_ctzll(tt) : -1;
+          tt &= tt - 1ull;
+          const int l2 = tt ? __builtin_ctzll(tt) : -1;
+          tt &= tt - 1ull;
+          const int l3 = tt ? __builtin_ctzll(tt) : -1;
+          const int src = grp == 0 ? l0 : grp == 1 ? l1 : grp == 2 ? l2 : l3;  // the read this lane's group serves
+          const int from = max(src, 0);
+          const int r_sum = __shfl(sum, from, 64);
+          const uint32_t r_pk = (uint32_t)__shfl((int)((uint32_t)ms | ((uint32_t)max(p_last, 0) << 12) | ((uint32_t)dw << 23)), from, 64);
+          const uint32_t r_gr = SCAN ? row0 + (uint32_t)from : (uint32_t)__shfl((int)gr, from, 64);
+          const int r_ms = (int)(r_pk & 0xfffu), r_last = (int)((r_pk >> 12) & 0x7ffu), r_dw = (int)(r_pk >> 23);
+          const int dd = r_dw - idx;  // this lane's dword of that read
+          const bool ok = src >= 0 && dd >= (r_ms >> 2);
+          uint32_t g = 0;
+          if (ok) {  // (dd lies inside the interval's dwords, and so does its mirror image: both inside the row)
+            g = (ma.seq + (size_t)r_gr * a.stride_dw)[rev ? (kTop >> 2) - dd : dd];
+            if (rev) g = __builtin_bswap32(g);
+          }
+          const int pb = 4 * dd;
+          auto term = [&](int b) -> int {  // what byte b adds; nothing outside the interval (top and lowest dword)
+            const bool in = ok && pb + b >= r_ms && pb + b <= r_last;
+            return !in ? 0 : ((g >> (b * 8)) & 0xffu) == match ? 1 : -2;
+          };
+          const int c3 = term(3), c2 = term(2), c1 = term(1), c0 = term(0);
+          const int p3 = c3, p2 = p3 + c2, p1 = p2 + c1, p0 = p1 + c0;  // scores inside the dword, 3' -> 5'
+          const int tot = p0;
+          int incl = tot;  // inclusive scan over the 16 lanes of the group
+          incl += __builtin_amdgcn_update_dpp(0, incl, 0x111 /* row_shr:1 */, 0xf, 0xf, false);
+          incl += __builtin_amdgcn_update_dpp(0, incl, 0x112 /* row_shr:2 */, 0xf, 0xf, false);
+          incl += __builtin_amdgcn_update_dpp(0, incl, 0x114 /* row_shr:4 */, 0xf, 0xf, false);
+          incl += __builtin_amdgcn_update_dpp(0, incl, 0x118 /* row_shr:8 */, 0xf, 0xf, false);
+          const int off = r_sum + incl - tot;  // the read's score in front of this dword
+          auto key = [&](int b, int sc) -> int {  // the candidate that ends at byte b with score sc
+            const int p = pb + b;
+            const bool q = ok && p >= r_ms && p <= r_last && sc > 0 && 5 * sc >= 2 * (r_last - p + 1);
+            return q ? ((sc << kPosBits) | p) : 0;
+          };
+          int kmax = max(max(key(3, off + p3), key(2, off + p2)), max(key(1, off + p1), key(0, off + p0)));
+          kmax = max(kmax, __builtin_amdgcn_update_dpp(0, kmax, 0x121 /* row_ror:1 */, 0xf, 0xf, false));
+          kmax = max(kmax, __builtin_amdgcn_update_dpp(0, kmax, 0x122 /* row_ror:2 */, 0xf, 0xf, false));
+          kmax = max(kmax, __builtin_amdgcn_update_dpp(0, kmax, 0x124 /* row_ror:4 */, 0xf, 0xf, false));
+          kmax = max(kmax, __builtin_amdgcn_update_dpp(0, kmax, 0x128 /* row_ror:8 */, 0xf, 0xf, false));
+          // back to the reads' own lanes: from the last lane of the group that served them
+          const int mine = lane == l0 ? 0 : lane == l1 ? 1 : lane == l2 ? 2 : lane == l3 ? 3 : -1;
+          const int back = 16 * max(mine, 0) + 15;
+          const int g_key = __shfl(kmax, back, 64);
+          const int g_sum = __shfl(r_sum + incl, back, 64);  // the read's score behind the group's 64 bases
+          if (mine >= 0) {
+            bestkey = max(bestkey, g_key);
+            sum = g_sum;
+            dw -= 16;
+            run = !settled(sum, bestkey >> kPosBits, 4 * dw + 4 - ms);  // (bases of the interval below the position reached)
+          }
+          todo = __ballot(run);
+        }
+        if (on) {
+          int index = n;
+          if (live && (bestkey >> kPosBits) > 0) index = (bestkey & kTop) - ms;
+          if (index > n - 3) index = n;
+          polya_bp += (uint32_t)(n - index);
+          if (rev)
+            s = e - index;
+          else
+            e = s + index;
+        }
+      }
     } else if (kind == CS_OP_SHORTEN) {
       if constexpr (FILT >= FILT_SHORTEN) {
         // cutadapt's Shortener (-l / -L): min(n, |length|) bases stay, the first ones or, length < 0, the last ones.
@@ -3898,6 +4074,10 @@ __global__ void __launch_bounds__(64, MODE == MODE_RESOLVE ? 4 : CS_SCAN_WAVES) 
   // one global atomic per counter per block (the LDS accumulators are 32-bit: a block sees
   // far fewer than 2^32 bases)
   const int tid_end = SCAN ? (int)wave_lane_fresh() : tid;
+  if constexpr (POLYA) {  // (a lane's own 32-bit sum, the wave's in 64 bits)
+    const unsigned long long w_polya = (unsigned long long)wave_sum(polya_bp & 0xffffu) + ((unsigned long long)wave_sum(polya_bp >> 16) << 16);
+    if (tid_end == 0 && w_polya) atomicAdd(&a.stats[kPolyABase + mate], w_polya);
+  }
   if (tid_end < kStatWords && sacc[tid_end])
     atomicAdd(&a.stats[(size_t)mate * kStatWords + tid_end], (unsigned long long)sacc[tid_end]);
 }

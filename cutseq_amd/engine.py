@@ -185,6 +185,12 @@ class TrimEngine:
         capi.check(self.L.cs_stats_fetch(self._eng_h, C.byref(st), 1 if reset else 0))
         return st[0], st[1]
 
+    def polya_bp(self, reset: bool = False) -> Tuple[int, int]:
+        """Per mate: the bases its ``PolyATrimOp`` removed (cutadapt's ``PolyATrimmer.trimmed_bases``)."""
+        bp = (C.c_uint64 * 2)()
+        capi.check(self.L.cs_polya_bp_fetch(self._eng_h, C.byref(bp), 1 if reset else 0))
+        return int(bp[0]), int(bp[1])
+
     def xflag_counts(self, reset: bool = False) -> Tuple[dict, dict]:
         """Per mate: how many reads got each ``CS_X_*`` bit (per-mate counts: no pairs, no precedence)."""
         counts = ((C.c_uint64 * abi.CS_X_COUNTS) * 2)()

@@ -31,6 +31,7 @@ class Worker(threading.Thread):
         self.submitted = 0
         self.engine = None
         self.stats = None  # summed cs_stats of every engine this device has had
+        self.poly_a_bp = None  # ... and, for a plan with a PolyATrimOp, the bases those removed per mate
         self.error: Optional[BaseException] = None
 
     def begin(self) -> None:
@@ -60,6 +61,8 @@ class Worker(threading.Thread):
     def _collect_stats(self) -> None:
         part = [s.as_dict() for s in self.engine.stats()]
         self.stats = part if self.stats is None else [shard.merge_stats([a, b]) for a, b in zip(self.stats, part)]
+        if getattr(getattr(self.engine, "plan", None), "has_poly_a", False):  # (engines without the op have no such count)
+            self.poly_a_bp = [a + b for a, b in zip(self.poly_a_bp or (0, 0), self.engine.polya_bp())]
 
     def _finish_oldest(self) -> None:
         k, slot, handle = self.inflight.popleft()

@@ -4,7 +4,7 @@ Counterpart of the modifier-list assembly in the reference's ``pipeline_single``
 (cutseq/run.py:326-426) and ``pipeline_paired`` (cutseq/run.py:533-731).  Where the
 reference instantiates cutadapt ``Modifier`` objects, this module emits plain
 descriptors (:class:`AdapterOp`, :class:`CutOp`, :class:`NextSeqTrimOp`, :class:`QTrimOp`,
-:class:`ShortenOp`, :class:`NTrimOp`) in the same order;
+:class:`ShortenOp`, :class:`NTrimOp`, :class:`PolyATrimOp`) in the same order;
 ``TrimPlan.pack()`` turns them into the ``cs_op`` POD table of ``include/cutseq_hip.h``.
 Header work (SuffixRemover, Renamer) stays on the host and is described by
 ``MateChain.name_suffixes`` / ``TrimPlan.has_umi``.
@@ -68,6 +68,8 @@ class CutadaptConfig:
         self.length_r2 = None
         # cutadapt --rename TEMPLATE: the template of the chain's (PairedEnd)Renamer (None = the reference's own)
         self.rename = None
+        # cutadapt --poly-a: a PolyATrimmer at step 7, where --trim-polyA puts its adapters (the two exclude each other)
+        self.poly_a = False
 
 
 @dataclass
@@ -174,6 +176,17 @@ class ShortenOp:
 
 
 @dataclass
+class PolyATrimOp:
+    """cutadapt's ``PolyATrimmer(revcomp)`` (``--poly-a``): the scored walk from the read's 3' end that removes a poly-A
+    tail or, ``revcomp=True``, from its 5' end a poly-T head (CS_OP_POLYA; the rule: ``include/cutseq_hip.h``)."""
+
+    revcomp: bool = False
+
+    def __repr__(self):
+        return f"PolyATrimmer(revcomp={self.revcomp})"
+
+
+@dataclass
 class NTrimOp:
     """cutadapt's ``NEndTrimmer()`` (``--trim-n``): the runs of upper-case ``N`` at both ends of the read go."""
 
@@ -233,7 +246,7 @@ class DemuxOp:
                 f"max_error_rate={self.max_error_rate}))")
 
 
-Op = Union[AdapterOp, CutOp, QTrimOp, DemuxOp, NTrimOp, NextSeqTrimOp, ShortenOp]
+Op = Union[AdapterOp, CutOp, QTrimOp, DemuxOp, NTrimOp, NextSeqTrimOp, ShortenOp, PolyATrimOp]
 
 
 def info_adapter_names(ops: Sequence["Op"]) -> dict:
@@ -289,6 +302,11 @@ class TrimPlan:
     def has_nextseq(self) -> bool:
         """Some chain holds a NextSeqTrimOp: its result depends on real quality values, FASTA input is refused."""
         return any(isinstance(o, NextSeqTrimOp) for c in (self.r1, self.r2) if c is not None for o in c.ops)
+
+    @property
+    def has_poly_a(self) -> bool:
+        """Some chain holds a PolyATrimOp: the engine counts ``PolyATrimmer.trimmed_bases`` (``cs_polya_bp_fetch``)."""
+        return any(isinstance(o, PolyATrimOp) for c in (self.r1, self.r2) if c is not None for o in c.ops)
 
     @property
     def paired(self) -> bool:
@@ -379,6 +397,9 @@ def pack_ops(ops: Sequence[Op], limit: int = abi.CS_MAX_OPS):
             c.q_base = op.base
         elif isinstance(op, NTrimOp):
             c.kind = abi.CS_OP_NTRIM
+        elif isinstance(op, PolyATrimOp):
+            c.kind = abi.CS_OP_POLYA
+            c.reversed = 1 if op.revcomp else 0
         elif isinstance(op, ShortenOp):  # (every int32 is a length: nothing is clamped, nothing refused below)
             c.kind = abi.CS_OP_SHORTEN
             if not -2 ** 31 <= op.length < 2 ** 31:
@@ -433,6 +454,22 @@ def _poly_a():
 
 def _poly_t():
     return non_internal_front("T" * POLY_LENGTH, POLY_MAX_ERRORS, abi.CS_F_POLY)
+
+
+def _poly_a_trimmers(barcode: BarcodeConfig, settings):
+    """--poly-a -> (revcomp of mate 1's PolyATrimmer, revcomp of mate 2's), or None without the option.  The direction
+    follows the scheme's strand the way --trim-polyA's adapters do; a scheme without one gets cutadapt's own pair
+    (read 1 tail, read 2 head): the option was asked for by name."""
+    if not getattr(settings, "poly_a", False):
+        return None
+    if settings.trim_polyA:
+        raise ValueError("--poly-a and --trim-polyA are two poly-A trimmers at one step: use one of them")
+    if barcode.strand == "-":
+        return True, False
+    if barcode.strand != "+":
+        logging.info("No strand information provided: --poly-a trims as cutadapt does, "
+                     "a poly-A tail of read 1 and a poly-T head of read 2.")
+    return False, True
 
 
 def _demux_op(barcode: BarcodeConfig, settings, paired: bool):
@@ -501,6 +538,9 @@ def compile_single(barcode: BarcodeConfig, settings: CutadaptConfig, untrimmed_r
             ops.append(_poly_t())
         else:
             logging.info("No strand information provided, skip polyA trimming.")
+    poly_a = _poly_a_trimmers(barcode, settings)  # (cutadapt --poly-a: its PolyATrimmer at the same step)
+    if poly_a is not None:
+        ops.append(PolyATrimOp(poly_a[0]))
     # step 8 (--nextseq-trim: cutadapt runs its NextseqQualityTrimmer in front of the QualityTrimmer)
     if getattr(settings, "nextseq_trim", None) is not None:
         ops.append(NextSeqTrimOp(settings.nextseq_trim))
@@ -591,6 +631,10 @@ def compile_paired(barcode: BarcodeConfig, settings: CutadaptConfig, untrimmed_r
             o2.append(_poly_a())
         else:
             logging.info("No strand information provided, skip polyA trimming.")
+    poly_a = _poly_a_trimmers(barcode, settings)  # (cutadapt --poly-a: PolyATrimmer() / PolyATrimmer(revcomp=True))
+    if poly_a is not None:
+        o1.append(PolyATrimOp(poly_a[0]))
+        o2.append(PolyATrimOp(poly_a[1]))
     # step 8
     if getattr(settings, "nextseq_trim", None) is not None:
         o1.append(NextSeqTrimOp(settings.nextseq_trim))

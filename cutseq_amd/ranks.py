@@ -459,5 +459,7 @@ def load_spec(path: str) -> dict:
 def dump_totals(spec: dict, totals: dict) -> None:
     keep = {k: totals[k] for k in ("in_pairs", "routes", "in_bp", "out_bp", "written_bp", "too_many_n", "too_long",
                                    "too_many_ee", "stats", "devices")}
+    if "poly_a_bp" in totals:  # (--poly-a runs: summed over the ranks by report.merge_totals)
+        keep["poly_a_bp"] = totals["poly_a_bp"]
     with open(spec["totals_file"], "w") as fh:
         json.dump(keep, fh)

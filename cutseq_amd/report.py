@@ -83,6 +83,8 @@ def merge_totals(into: dict, part: dict) -> None:
     into["in_pairs"] += part["in_pairs"]
     for key, _bit in DISCARD_ORDER:
         into[key] = into.get(key, 0) + part.get(key, 0)
+    if "poly_a_bp" in part:  # (--poly-a runs only)
+        into["poly_a_bp"] = [a + b for a, b in zip(into.get("poly_a_bp", (0, 0)), part["poly_a_bp"])]
     for key in ("routes", "in_bp", "out_bp", "written_bp"):
         if len(into[key]) < len(part[key]):  # demultiplexing runs: one more stream per barcode
             into[key].extend([0] * (len(part[key]) - len(into[key])))
@@ -184,6 +186,9 @@ def json_report(tp: TrimPlan, totals: dict, barcode, input1, input2, output1, ou
     if tp.max_ee is not None:
         filtered["too_many_expected_errors"] = totals.get("too_many_ee", 0)
     q1, q2 = _mate_sum(totals, 0, "qualtrim_bp"), (_mate_sum(totals, 1, "qualtrim_bp") if paired else None)
+    # cutadapt's PolyATrimmer.trimmed_bases (--poly-a); null without the option: --trim-polyA's adapters count as adapters
+    pa = totals.get("poly_a_bp") if tp.has_poly_a else None
+    pa1, pa2 = (pa[0], pa[1] if paired else None) if pa is not None else (None, None)
     engine = {"name": "cutseq_amd", "version": __version__, "devices": totals.get("devices"),
               "seconds": totals.get("seconds"), "is_untrimmed_any": totals["routes"][2] if tp.untrimmed_filter else None,
               "per_device": totals["stats"],
@@ -226,9 +231,9 @@ def json_report(tp: TrimPlan, totals: dict, barcode, input1, input2, output1, ou
             "quality_trimmed": q1 + (q2 or 0),
             "quality_trimmed_read1": q1,
             "quality_trimmed_read2": q2,
-            "poly_a_trimmed": None,  # cutadapt's PolyATrimmer is not in the reference's chain
-            "poly_a_trimmed_read1": None,
-            "poly_a_trimmed_read2": None,
+            "poly_a_trimmed": None if pa is None else pa1 + (pa2 or 0),  # (not in the reference's chain: --poly-a only)
+            "poly_a_trimmed_read1": pa1,
+            "poly_a_trimmed_read2": pa2,
             "output": sum(totals["written_bp"]),
             "output_read1": totals["written_bp"][0],
             "output_read2": totals["written_bp"][1] if paired else None,

@@ -82,6 +82,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--trim-polyA", action="store_true", help="Enable trimming of polyA/T tails.")
     p.add_argument("--trim-polyA-wo-direction", action="store_true",
                    help="Trim polyA/T tails regardless of strand information.")
+    p.add_argument("--poly-a", dest="poly_a", action="store_true",
+                   help="Extension (cutadapt's option, cutadapt >= 4.4): trim poly-A tails with cutadapt's own poly-A "
+                        "trimmer, which its manual recommends over an adapter of A's: a scored walk from the read's end "
+                        "that allows one foreign base in five and ignores tails shorter than three. It stands where "
+                        "--trim-polyA's adapters stand; on a (+) library read 1 loses a poly-A tail and read 2 a poly-T "
+                        "head, on a (-) library the other way round, without strand information as on (+). Not with "
+                        "--trim-polyA.")
     p.add_argument("--conditional-cutter", action=argparse.BooleanOptionalAction, default=True,
                    help="Enable/disable conditional cutting for UMIs/masks.")
     p.add_argument("--force-trim-min-length", type=int, default=50,
@@ -231,6 +238,8 @@ def resolve_args(args):
     if nextseq is not None and not abi.CS_Q_SUM_LOW <= nextseq + 33 <= abi.CS_Q_SUM_HIGH:
         # (unlike -q's, this cutoff is not clamped: a G's term is +1 whatever it is -- include/cutseq_hip.h, CS_OP_NEXTSEQ)
         _fail(f"--nextseq-trim: the cutoff must lie in [{abi.CS_Q_SUM_LOW - 33}, {abi.CS_Q_SUM_HIGH - 33}] (got {nextseq}).")
+    if args.poly_a and args.trim_polyA:
+        _fail("--poly-a cannot be combined with --trim-polyA: they are two poly-A trimmers at one step, use one of them.")
     interleaved_in, interleaved_out = resolve_interleaved(args, inputs)
     if args.min_quality_r2 is not None and len(inputs) == 1 and not interleaved_in:
         _fail("-Q sets the quality cutoff of the second read: it needs two input files.")
@@ -301,6 +310,7 @@ def settings_from_args(args) -> CutadaptConfig:
     st.length = args.length
     st.length_r2 = args.length_r2
     st.rename = args.rename
+    st.poly_a = args.poly_a
     st.dry_run = args.dry_run
     st.auto_rc = args.auto_rc
     st.json_file = args.json_file
@@ -528,6 +538,8 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
     progress.close()
     totals["bin_names"] = list(args.demux[0]) if n_bins else None
     totals["stats"] = stats
+    if tp.has_poly_a:  # (--poly-a: PolyATrimmer.trimmed_bases per mate; a run without the option has no such key)
+        totals["poly_a_bp"] = [sum(w.poly_a_bp[m] for w in workers if w.poly_a_bp is not None) for m in range(2)]
     totals["devices"] = devices
     return totals
 

@@ -1073,6 +1073,8 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
     progress.close()
     totals["bin_names"] = list(args.demux[0]) if options.bins else None
     totals["stats"] = stats
+    if tp.has_poly_a:  # (--poly-a: PolyATrimmer.trimmed_bases per mate; a run without the option has no such key)
+        totals["poly_a_bp"] = [sum(w.poly_a_bp[m] for w in workers if w.poly_a_bp is not None) for m in range(2)]
     totals["devices"] = devices
     totals["path"] = "text"
     if PROFILE:

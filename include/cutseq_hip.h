@@ -51,7 +51,8 @@ typedef enum cs_status {
 /* ---- op table: what cutseq/run.py:305-433 (single) and :493-731 (paired) compile -- */
 
 enum {
-  CS_OP_ADAPTER = 1, CS_OP_CUT = 2, CS_OP_QTRIM = 3, CS_OP_DEMUX = 4, CS_OP_NTRIM = 5, CS_OP_NEXTSEQ = 6, CS_OP_SHORTEN = 7
+  CS_OP_ADAPTER = 1, CS_OP_CUT = 2, CS_OP_QTRIM = 3, CS_OP_DEMUX = 4, CS_OP_NTRIM = 5, CS_OP_NEXTSEQ = 6, CS_OP_SHORTEN = 7,
+  CS_OP_POLYA = 8
 };
 
 /* CS_OP_QTRIM -- cutadapt's QualityTrimmer(cutoff_front, cutoff_back, base), quality_trim_index on the interval [s, e)
@@ -96,6 +97,28 @@ enum {
  * filters and the info table's final read see the result; qualtrim_bp and CS_F_QTRIMMED do not change.  cutadapt's order:
  * behind the chain's CS_OP_QTRIM, in front of its CS_OP_NTRIM.  A plan with the op runs the read-end instantiations of the
  * long-read and info kernels and tile kernels of its own, which hold all the read-end ops' code and this op's; every
+ * other plan the kernels it ran before.
+ *
+ * CS_OP_POLYA -- cutadapt's PolyATrimmer (--poly-a; cutadapt >= 4.4), poly_a_trim_index on the interval [s, e) the op
+ * sees (n = e - s, bases b[0..n)); one field, `reversed` (1 = the head form, PolyATrimmer(revcomp=True)).  Bytes are
+ * compared exactly: only 'A' (0x41; head form: 'T', 0x54) is a match -- 'a', 'N' and everything else is an error.
+ *     tail (reversed = 0):  score = errors = best = 0; index = n
+ *         for i = n - 1 down to 0:
+ *             if b[i] == 'A': score += 1   else: score -= 2; errors += 1
+ *             if score > best and errors * 5 <= n - i:   best = score; index = i
+ *         if index > n - 3: index = n              tails shorter than 3 are ignored
+ *         [s, s + index) is left                   the counter gains n - index
+ *     head (reversed = 1):  the mirror image: 'T', i = 0 .. n - 1, condition errors * 5 <= i + 1, index = i + 1;
+ *         if index < 3: index = 0;  [s + index, e) is left;  the counter gains index
+ * Equivalent facts (held to the loop by enumeration, tests/test_polya_cpu.py): a candidate of length l with e errors has
+ * score l - 3e, so errors * 5 <= l  <=>  5 * score >= 2 * l; the result is the FIRST position in walk order that attains
+ * the maximum score among the qualifying positions with score > 0 -- a maximum over (score, position) keys, the shape of
+ * CS_OP_QTRIM's key; a walk that stands at length l with score sc is settled as soon as sc + (n - l) <= best or
+ * 5 * (sc + n - l) < 2 * n (no later position can beat the best one, or qualify).  |score| <= 2 * n.
+ * No flag (cs_result.flags has no free bit, and cutadapt records nothing per read); the counter
+ * PolyATrimmer.trimmed_bases per mate comes through cs_polya_bp_fetch.  out_bp, TooShort, the filters and the info
+ * table's final read see the result.  cutadapt's order: behind the adapter cutters, in front of the quality trimmers.  A
+ * plan with the op runs tile, long-read and info kernels of its own (instantiations that hold this op's code); every
  * other plan the kernels it ran before. */
 
 /* CS_OP_DEMUX -- extension, not a reference capability (BASELINE.json config 5): ONE pass
@@ -174,6 +197,7 @@ typedef struct cs_op {
   uint8_t align_flags;   /* ADAPTER: CS_WHERE_*                                       */
   uint8_t reversed;      /* ADAPTER: 1 = RightmostFrontAdapter: `seq` holds the reversed
                             adapter, the aligner walks the read right-to-left;
+                            POLYA: 1 = the head form (poly-T at the 5' end);
                             DEMUX: 1 = the barcodes end the read (SuffixAdapter ops through
                             cs_plan_set_demux_ops: CS_WHERE_SUFFIX, CS_REMOVE_AFTER)     */
   uint8_t remove;        /* ADAPTER: CS_REMOVE_BEFORE (read[rstop:]) / _AFTER (read[:rstart]) */
@@ -379,6 +403,11 @@ int cs_stats_fetch(cs_engine *eng, cs_stats stats[2], int reset);
  * synchronous like cs_stats_fetch.  counts[m][0] is cs_stats.n_too_many_n; `reset` zeroes all six counters (that word
  * of cs_stats included), and cs_stats_fetch's reset leaves the other four alone. */
 int cs_xflag_counts_fetch(cs_engine *eng, uint64_t counts[2][CS_X_COUNTS], int reset);
+
+/* cutadapt's PolyATrimmer.trimmed_bases: bp[mate] = the bases every CS_OP_POLYA op of that mate's chain removed (0 for a
+ * plan without the op).  Ordered and synchronous like cs_stats_fetch; `reset` zeroes both counters, and neither
+ * cs_stats_fetch's nor cs_xflag_counts_fetch's reset touches them. */
+int cs_polya_bp_fetch(cs_engine *eng, uint64_t bp[2], int reset);
 
 /* Timing of the last cs_trim_device / cs_trim_device_pipelined call, measured with HIP events recorded
  * around each kernel on the stream it ran on (ms, the two kernels added).  Synchronises on the stop event. */

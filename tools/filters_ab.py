@@ -23,6 +23,12 @@ both mates.  Without --length the median final length of a sample of the same re
 op) is taken and printed.
 
   python tools/filters_ab.py --shorten [--length N] [--sample 1000000]
+
+--poly-a: the headline configuration in three variants -- "trim_polya" (--trim-polyA: the reference's poly-A adapters,
+what bench.py times), "poly_a" (--poly-a in their place: cutadapt's PolyATrimmer, CS_OP_POLYA) and "neither" -- with the
+bases each poly step removed per call where the engine counts them.
+
+  python tools/filters_ab.py --poly-a
 """
 from __future__ import annotations
 
@@ -47,6 +53,14 @@ def plan_for(filters):
     from cutseq_amd import plan as planmod
     tp = workloads.make_plan("config3")
     tp.max_length, tp.max_n, tp.max_ee = filters.get("max_length"), filters.get("max_n"), filters.get("max_ee")
+    if filters.get("poly") is not None:  # "trim_polya": the plan as it is; "poly_a": a PolyATrimOp in the adapters' place
+        for chain in (tp.r1, tp.r2):
+            at = [i for i, o in enumerate(chain.ops) if isinstance(o, planmod.AdapterOp) and o.match_flag == abi.CS_F_POLY]
+            assert len(at) == 1
+            if filters["poly"] == "poly_a":  # NonInternalFrontAdapter (poly-T head) -> revcomp, as plan.py's strand rule
+                chain.ops[at[0]] = planmod.PolyATrimOp(chain.ops[at[0]].kind_name == "NonInternalFrontAdapter")
+            elif filters["poly"] == "neither":
+                del chain.ops[at[0]]
     for chain in (tp.r1, tp.r2):
         if filters.get("drop_qtrim"):
             chain.ops = [o for o in chain.ops if not isinstance(o, planmod.QTrimOp)]
@@ -140,7 +154,8 @@ def leg(d, n, stride, filters, steps, warmup, with_xflags):
         elapsed = time.perf_counter() - t0
         calls, scan_ms, resolve_ms = eng.kernel_time_totals()
         c1, c2 = eng.xflag_counts()
-    return {"filters": filters, "mpairs_s": n * steps / elapsed / 1e6, "scan_ms": scan_ms / calls,
+        poly_a_bp = [b // steps for b in eng.polya_bp()] if tp.has_poly_a else None
+    return {"filters": filters, **({"poly_a_bp": poly_a_bp} if poly_a_bp is not None else {}), "mpairs_s": n * steps / elapsed / 1e6, "scan_ms": scan_ms / calls,
             "resolve_ms": resolve_ms / calls, "flagged": {k: [c1[k] // steps, c2[k] // steps] for k in c1}}
 
 
@@ -161,6 +176,8 @@ def main():
     ap.add_argument("--cutoff", type=int, default=20, help="--nextseq: the cutoff")
     ap.add_argument("--shorten", action="store_true", help="the legs of -l LENGTH instead of the filters'")
     ap.add_argument("--length", type=int, default=None, help="--shorten: the length (default: the median final length)")
+    ap.add_argument("--poly-a", dest="poly_a", action="store_true",
+                    help="the headline with --trim-polyA, with --poly-a in its place and with neither, instead of the filters' legs")
     ap.add_argument("--only", type=str, default=None, help="run these legs alone (comma-separated)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -188,6 +205,8 @@ def main():
             length = median_final_length(d, min(n, args.sample), stride)
             print(json.dumps({"median_final_length": length, "sample_pairs": min(n, args.sample)}), flush=True)
         legs = (("off", {}), ("shorten", {"shorten": length}))
+    if args.poly_a:  # ("off" is what the summary compares with: the headline as bench.py runs it)
+        legs = (("off", {"poly": "trim_polya"}), ("poly_a", {"poly": "poly_a"}), ("neither", {"poly": "neither"}))
     if args.only:
         legs = tuple(leg_ for leg_ in legs if leg_[0] in args.only.split(","))
     res = {key: [] for key, _ in legs}

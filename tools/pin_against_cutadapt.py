@@ -170,6 +170,11 @@ def build_chain(barcode, settings, paired: bool, untrimmed_requested: bool = Fal
             each(tail(), head())
         elif barcode.strand == "-":
             each(head(), tail())
+    if _get(settings, "poly_a", False):  # --poly-a: cutadapt's own trimmer at step 7 (cutadapt >= 4.4), by the strand
+        if barcode.strand == "-":
+            each(M.PolyATrimmer(revcomp=True), M.PolyATrimmer())
+        else:  # '+', and cutadapt's own pair for a scheme without a strand
+            each(M.PolyATrimmer(), M.PolyATrimmer(revcomp=True))
     # step 8 (--nextseq-trim: cutadapt's order of its two trimmers, NextseqQualityTrimmer first)
     ns = _get(settings, "nextseq_trim", None)
     if ns is not None:
@@ -351,6 +356,45 @@ def collect_cases(n_synth: int = 2000):
     return cases
 
 
+POLY_A_FLAGS = ({"poly_a": True},
+                {"poly_a": True, "nextseq_trim": 20, "min_quality_front": 15, "min_quality": 10, "length": 100, "trim_n": True})
+
+
+def collect_poly_a_cases(limit=2000):
+    """--poly-a (cutadapt's PolyATrimmer, a recalled rule: DESIGN.md 0).  These cases go to a fixture of their own,
+    tests/golden/polya_cutadapt_<version>.json.gz, which tests/test_polya_cpu.py consumes: the C oracle does not know
+    the op, so the consumer of the main fixture cannot replay them."""
+    from cutseq_amd.common import BUILDIN_ADAPTERS
+    rec1, rec2 = fixture_records(limit)
+    cases = [poly_a_case()]
+    for scheme in (BUILDIN_ADAPTERS["TAKARAV3"], BUILDIN_ADAPTERS["TAKARAV3"].replace("<", ">")):
+        for flags in POLY_A_FLAGS:
+            cases.append(chain_case(f"fixture10k[:{limit}]/{scheme}/{sorted(flags)}", scheme, flags, True,
+                                    {"fixture": "fixture10k", "limit": limit}, rec1, rec2))
+    return cases
+
+
+def poly_a_case():
+    """cutadapt's PolyATrimmer on the enumerated reads of tests/polya_rule.py (universes E and M, both ends).  Only the
+    reads on which cutadapt and the restated loop DIFFER are written down (none, if the recollection is right), with
+    the number of reads compared."""
+    import dnaio
+    import polya_rule
+    _, M, ModificationInfo, _, _, _ = _classes()
+    differ, total = [], 0
+    for head in (False, True):
+        trimmer = M.PolyATrimmer(revcomp=head)
+        for read in polya_rule.universe_e(head) + polya_rule.universe_m(head):
+            text = read.decode()
+            rec = dnaio.SequenceRecord("r", text, "I" * len(text))
+            got = trimmer(rec, ModificationInfo(rec)).sequence
+            start, stop = polya_rule.keep(read, head)
+            total += 1
+            if got != text[start:stop]:
+                differ.append([head, text, got, text[start:stop]])
+    return {"id": "poly_a_rule", "kind": "poly_a", "reads": total, "differ": differ}
+
+
 def time_cutadapt_chain(workload: str, batch, m: int) -> dict:
     """bench.py's ``cpu_baseline_cutadapt`` leg: the real cutadapt chain of the workload, one thread, ``m`` pairs."""
     from cutseq_amd import synth, workloads
@@ -382,6 +426,12 @@ def main():
     with gzip.open(out, "wt") as fh:
         json.dump({"cutadapt_version": cutadapt_version(), "generator": "tools/pin_against_cutadapt.py", "cases": cases}, fh)
     print(f"wrote {out} ({len(cases)} cases)")
+    if hasattr(_classes()[1], "PolyATrimmer"):  # (cutadapt >= 4.4)
+        cases = collect_poly_a_cases()
+        out = ROOT / "tests" / "golden" / f"polya_cutadapt_{cutadapt_version()}.json.gz"
+        with gzip.open(out, "wt") as fh:
+            json.dump({"cutadapt_version": cutadapt_version(), "generator": "tools/pin_against_cutadapt.py", "cases": cases}, fh)
+        print(f"wrote {out} ({len(cases)} cases)")
     return 0
 
 
