@@ -1,10 +1,12 @@
 """Inflaters for the reader's device mode (``textio.TextReader``, ``CUTSEQ_GPU_INFLATE=1``): BGZF blocks go from the
-mapped file straight into a text buffer, and the reader's bookkeeping -- k-th newline, carry, what is left at the end
--- works on that buffer through the same object.
+mapped file straight into a text buffer.  The reader has one cutting loop (``textio._Pending``: k-th newline, carry,
+growth) and two memories it runs in: the pinned arena (``textio._HostMemory``, which has ``take`` / ``give`` / ``copy`` /
+``after_kth_newline`` below and nothing else) and an inflater, the memory of the BGZF source.  When that source ends,
+``to_host`` brings what is left to the pinned arena, where the end of the input is decided.
 
 Two of them with the same methods: :class:`DeviceInflater` wraps ``cs_inflate_*`` (the buffers are device memory, the
 decoder is ``csrc/inflate_kernels.hip.inc``); :class:`HostInflater` does the same over numpy arrays with zlib, for the
-CPU tests of the reader's bookkeeping.  Imported only when the switch is on.
+CPU tests of the reader's loop.  Imported only when the switch is on.
 
   take(nbytes) -> buffer (``.size``; reused ones come from a pool)     give(buffer)
   inflate(mapped, lo, rows, buffer, at) -> (newlines per block, index of the first refused block or -1)

@@ -6,8 +6,10 @@ count and k-th newline, no per-record work -- and write (or deflate) the finishe
 order.  Counterpart of ``runner.run(pipeline, Progress(), outfiles)`` with ``make_runner(cores=N)``
 (cutseq/run.py:436, 473, 753, 794): reader, chunk fan-out to workers, ordered merge.
 
-  TextReader    one thread per input file: page cache (several ``pread`` calls at once) or inflate pool -> pinned
-                block buffer -> ``TextBlock(buf, nbytes, n_records)``
+  TextReader    one thread per input file and one cutting loop with two memories: a source (page cache, several
+                ``pread`` calls at once; the inflate pool; BGZF spans through an inflater, CUTSEQ_GPU_INFLATE) appends
+                to ``_Pending``, which cuts behind newline 4 * chunk_reads and carries the rest -- in pinned memory or
+                in the inflater's (device memory) -> ``TextBlock(buf, nbytes, n_records)``
   TextWorker    one thread per GPU (a ``fanout.Worker``): a ``TrimEngine`` + ``TextEngine``, three batches in flight;
                 grows the row stride or the text capacity when a batch needs it
   run_text_pipeline   pairs the mates' blocks and hands them to ``fanout.run_ordered`` (round-robin deal, results back
@@ -20,6 +22,7 @@ behind ``CUTSEQ_TEXT_PATH=0``, held to the same outputs by the tests' switch mat
 """
 from __future__ import annotations
 
+import concurrent.futures
 import ctypes as C
 import dataclasses
 import mmap
@@ -102,6 +105,133 @@ class TextBlock:
         if self.dbuf is not None:
             self.owner.give(self.dbuf)
             self.dbuf = None
+
+
+class _HostMemory:
+    """The pinned arena under the inflater's method names (``inflater.py``): the memory the reader cuts host text in."""
+
+    def take(self, nbytes: int) -> np.ndarray:
+        return fastq.PINNED.take(nbytes)
+
+    def give(self, buf: np.ndarray) -> None:
+        fastq.PINNED.give(buf)
+
+    def copy(self, dst: np.ndarray, dst_at: int, src: np.ndarray, src_at: int, nbytes: int) -> None:
+        C.memmove(dst.ctypes.data + dst_at, src.ctypes.data + src_at, nbytes)
+
+    def after_kth_newline(self, buf: np.ndarray, at: int, nbytes: int, k: int) -> int:
+        return int(_host().csh_after_kth_newline(buf.ctypes.data + at, nbytes, k))
+
+
+_HOST = _HostMemory()
+
+
+class _Pending:
+    """The text behind the last block that went out: ``buf[:fill]``, a buffer of ``mem`` (:class:`_HostMemory` or an
+    inflater), holds ``lines`` newlines; ``marks`` has one (offset, nbytes, newlines) per piece a source appended.
+    ``goal`` (the lines the loop is filling up to) and ``est`` are there for the sources to size their reads by."""
+
+    def __init__(self, mem, chunk_reads: int):
+        self.mem, self.chunk_reads = mem, chunk_reads
+        self.est = 400  # bytes per record, corrected by every block that goes out
+        self.buf = mem.take(self.size())
+        self.fill = self.lines = self.goal = 0
+        self.marks: List[tuple] = []
+        self.copies: List = []  # pieces on their way into `buf` (copied by the pool)
+
+    def size(self) -> int:
+        return int(self.chunk_reads * self.est * 1.25) + 2 * _BLOCK
+
+    def settle(self) -> None:
+        """Pooled copies into ``buf`` are awaited before it is read, grown, cut, moved or given back: here, all of them."""
+        copies, self.copies = self.copies, []
+        for f in concurrent.futures.wait(copies).done:
+            f.result()
+
+    def room(self, nbytes: int) -> None:
+        """``nbytes`` free bytes behind ``fill``, in a bigger buffer if need be."""
+        if self.buf.size - self.fill < nbytes:
+            self.settle()
+            bigger = self.mem.take(max(self.buf.size + self.buf.size // 2, self.fill + nbytes))
+            self.mem.copy(bigger, 0, self.buf, 0, self.fill)
+            self.mem.give(self.buf)
+            self.buf = bigger
+
+    def added(self, nbytes: int, newlines: int) -> None:
+        self.marks.append((self.fill, nbytes, newlines))
+        self.fill += nbytes
+        self.lines += newlines
+
+    def cut(self, k: int):
+        """-> (buffer, cut): the text up to newline ``k`` leaves in its buffer, what is behind it is carried into a
+        fresh one.  ``marks`` say which piece holds the newline, and only that piece is searched for it."""
+        cum = 0
+        for at, (off, nbytes, found) in enumerate(self.marks):
+            if cum + found >= k:
+                break
+            cum += found
+        cut = off + self.mem.after_kth_newline(self.buf, off, nbytes, k - cum)
+        assert cum + found >= k and cut > 0
+        nxt = self.mem.take(max(self.buf.size, self.size()))
+        self.mem.copy(nxt, 0, self.buf, cut, self.fill - cut)
+        # the piece the cut went through keeps its rest, the others move up
+        self.marks = [(0, off + nbytes - cut, found - (k - cum))] + [(o - cut, n, f) for o, n, f in self.marks[at + 1:]]
+        old, self.buf = self.buf, nxt
+        self.fill, self.lines = self.fill - cut, self.lines - k
+        return old, cut
+
+    def drop_lines(self, k: int) -> None:
+        self.mem.give(self.cut(k)[0])
+
+    def to_host(self, spare: int) -> None:
+        """From an inflater's buffer into a pinned one with ``spare`` bytes of room (the pieces stay where they are)."""
+        buf = _HOST.take(self.fill + spare)
+        self.mem.to_host(buf, self.buf, 0, self.fill)
+        self.mem.give(self.buf)
+        self.mem, self.buf = _HOST, buf
+
+    def close(self) -> None:
+        try:
+            self.settle()
+        except BaseException:
+            pass
+        if self.buf is not None:
+            self.mem.give(self.buf)
+            self.buf = None
+
+
+def _copy_in(dst: int, text: np.ndarray, nbytes: int) -> None:
+    C.memmove(dst, text.ctypes.data, nbytes)
+    if isinstance(text.base, fastq.mmap.mmap):
+        fastq.ARENA.give(text)
+
+
+def _end_of_input(text, path: str):
+    """``text``: what is left at the end of the input -> (end, records, append_newline): ``text[:end]`` is the last
+    block's ``records`` whole records, after a '\\n' is written at ``text[end - 1]`` if ``append_newline`` says so.
+
+    What is left must be whole records; blank lines behind the last one are tolerated.  The last NON-BLANK line
+    decides: it is line 4k + 3 (a quality line: the record ends with it, the device takes the end of the text for its
+    missing line end) or line 4k + 2 (a '+' line: the record has an empty read, "@id\\n\\n+\\n\\n", and its empty quality
+    line is the first blank line behind it).  Only whole blank lines beyond that are dropped -- stripping all trailing
+    white space took the empty quality line with it and turned a valid file into "truncated"."""
+    view = memoryview(text)
+    fill = end = len(view)
+    while end > 0 and view[end - 1] in b"\n\r \t":
+        end -= 1
+    if end == 0:
+        return 0, 0, False
+    last = int(_host().csh_count_newlines(np.frombuffer(view, dtype=np.uint8).ctypes.data, end))  # index of the last non-blank line
+    if last % 4 == 3:
+        return end, (last + 1) // 4, False
+    if last % 4 == 2 and end < fill:
+        # the '+' line's own line end, then the empty quality line (its '\n' is written if the file lacks it)
+        tail = bytes(view[end:fill])  # white space only
+        nl1 = tail.find(b"\n")
+        if nl1 >= 0:
+            nl2 = tail.find(b"\n", nl1 + 1)
+            return (end + nl2 + 1 if nl2 >= 0 else fill + 1), (last + 2) // 4, nl2 < 0
+    raise fastq.FastqFormatError(f"{path}: truncated FASTQ record at end of file")
 
 
 class TextReader(threading.Thread):
@@ -189,27 +319,13 @@ class TextReader(threading.Thread):
                 "has no partner.")
         return records // 2
 
-    def _block(self, buf: np.ndarray, nbytes: int, records: int, done: int) -> TextBlock:
-        """The block of ``records`` records behind the ``done`` records handed out so far."""
+    def _block(self, mem, buf, nbytes: int, records: int, done: int) -> TextBlock:
+        """The block of ``records`` records behind the ``done`` records handed out so far, in a buffer of ``mem``."""
+        if mem is not _HOST:
+            return TextBlock(None, nbytes, records, done, dbuf=buf, owner=mem)
         if self.interleaved:
             return TextBlock(buf, nbytes, self.pair_count(records, self.path), done // 2)
         return TextBlock(buf, nbytes, records, done)
-
-    # -- sources: append text behind buf[:fill] -> (buf, fill, [(offset, nbytes, newlines)], eof) ------------------
-    @staticmethod
-    def _room(buf: np.ndarray, fill: int, want: int) -> np.ndarray:
-        if buf.size - fill >= want:
-            return buf
-        bigger = fastq.PINNED.take(max(buf.size + buf.size // 2, fill + want))
-        C.memmove(bigger.ctypes.data, buf.ctypes.data, fill)
-        fastq.PINNED.give(buf)
-        return bigger
-
-    @staticmethod
-    def _copy_in(dst: int, text: np.ndarray, nbytes: int) -> None:
-        C.memmove(dst, text.ctypes.data, nbytes)
-        if isinstance(text.base, fastq.mmap.mmap):
-            fastq.ARENA.give(text)
 
     @staticmethod
     def _members_until(src, start: int, stop: int):
@@ -232,64 +348,55 @@ class TextReader(threading.Thread):
                                               C.byref(consumed), C.byref(records), C.byref(err_line))
         return int(produced), int(consumed.value), int(err_line.value)
 
-    def _read_plain(self, fd: int, pos: int, buf: np.ndarray, fill: int, want: int):
-        """``want`` bytes of the file from ``pos`` on, several preads (and newline counts) at once in the pool."""
+    # -- sources: generators that append text to a _Pending, one round per step, and end with their input ------------
+    def _plain_text(self, pend: _Pending, pos: int):
+        """The plain file from byte ``pos`` on: several preads (and newline counts) at once in the pool."""
         L = _host()
-        pieces = max(1, min(16, (want + _BLOCK - 1) // _BLOCK))  # (a block of 262 144 short-read records: 11 pieces, one round)
-        want = pieces * _BLOCK
-        buf = self._room(buf, fill, want)
-        base = buf.ctypes.data
-        mv = memoryview(buf)
+        fd = os.open(self.path, os.O_RDONLY)
+        try:
+            eof = False
+            while not eof:
+                t0 = time.perf_counter()
+                want = max(_BLOCK, int((pend.goal - pend.lines) / 4 * pend.est * 1.05))
+                pieces = max(1, min(16, (want + _BLOCK - 1) // _BLOCK))  # (a block of 262 144 short-read records: 11 pieces, one round)
+                pend.room(pieces * _BLOCK)
+                fill, base, mv = pend.fill, pend.buf.ctypes.data, memoryview(pend.buf)
 
-        def job(i):
-            off = fill + i * _BLOCK
-            got = 0
-            while got < _BLOCK:  # a short read is not the end of the file (FUSE, network mounts): only 0 bytes is
-                more = os.preadv(fd, [mv[off + got:off + _BLOCK]], pos + i * _BLOCK + got)
-                if more <= 0:
-                    break
-                got += more
-            return got, (int(L.csh_count_newlines(base + off, got)) if got else 0)
+                def job(i):
+                    off = fill + i * _BLOCK
+                    got = 0
+                    while got < _BLOCK:  # a short read is not the end of the file (FUSE, network mounts): only 0 bytes is
+                        more = os.preadv(fd, [mv[off + got:off + _BLOCK]], pos + i * _BLOCK + got)
+                        if more <= 0:
+                            break
+                        got += more
+                    return got, (int(L.csh_count_newlines(base + off, got)) if got else 0)
 
-        pool = fastq._pool()
-        results = [f.result() for f in [pool.submit(job, i) for i in range(pieces)]] if pieces > 1 else [job(0)]
-        marks, eof, total = [], False, 0
-        for i, (got, lines) in enumerate(results):
-            if eof and got:  # a short piece in the middle: the file changed under us
-                raise OSError(f"{self.path}: short read")
-            if got:
-                marks.append((fill + i * _BLOCK, got, lines))
-                total += got
-            if got < _BLOCK:
-                eof = True
-        return buf, fill + total, marks, eof
+                pool = fastq._pool()
+                results = [f.result() for f in [pool.submit(job, i) for i in range(pieces)]] if pieces > 1 else [job(0)]
+                for got, lines in results:
+                    if eof and got:  # a short piece in the middle: the file changed under us
+                        raise OSError(f"{self.path}: short read")
+                    if got:
+                        pend.added(got, lines)
+                    eof = got < _BLOCK
+                pos += pend.fill - fill
+                _tick("read", t0)
+                yield True
+        finally:
+            os.close(fd)
 
-    def _run(self, resume=None):
-        """``resume``: (buffer, fill, lines, records done, compressed offset) -- where the device mode's BGZF run ended;
-        the host path goes on from that state, through the same end-of-input code."""
+    def _block_text(self, pend: _Pending, pos: int):
+        """Blocks of text from a generator -- gzip members from compressed offset ``pos`` on, inflated in the pool, or a
+        sequential stream, FASTA re-shaped into four-line records --, copied in by the pool."""
         L = _host()
-        need = 4 * self.chunk_reads
-        est = 400  # bytes per record, corrected by every block that goes out
-        fill, lines, done = 0, 0, 0
-        marks: List[tuple] = []  # (offset, nbytes, newlines) of every piece behind buf[:fill]
-        if resume is None:
-            buf = fastq.PINNED.take(int(self.chunk_reads * est * 1.25) + 2 * _BLOCK)
-            member_at = self.start_at
-        else:
-            buf, fill, lines, done, member_at = resume
-            marks = [(0, fill, lines)]
-        eof = False
-        fd, pos, gen = -1, self.start_at, None
-        skip = self.skip_lines
-        left = self.max_records  # records still to hand out (None: everything)
-        copies: List = []  # inflated blocks on their way into `buf` (copied by the pool, awaited before `buf` is read)
         if self.gz and not self.fasta:
             src = codec.GzipSource(self.path, fastq._pool(), fastq.ARENA.take, fastq.ARENA.give,
                                    post=lambda addr, nbytes: int(L.csh_count_newlines(addr, nbytes)))
-            gen = src.blocks(member_at) if self.stop_at is None else self._members_until(src, self.start_at, self.stop_at)
-            if resume is not None and member_at >= src.size:  # (the BGZF run was the whole file)
+            gen = src.blocks(pos) if self.stop_at is None else self._members_until(src, pos, self.stop_at)
+            if pos >= src.size:  # (a BGZF run that went through the inflater was the whole file)
                 gen = iter(())
-        elif self.gz or self.sequential:
+        else:
             if self.gz:  # (FASTA in a gzip file: the members still inflate in the pool)
                 src = codec.GzipSource(self.path, fastq._pool(), fastq.ARENA.take, fastq.ARENA.give)
             else:
@@ -297,150 +404,25 @@ class TextReader(threading.Thread):
             if self.fasta:
                 src = codec.FastaSource(src, self._fasta_convert, fastq.ARENA.take, fastq.ARENA.give, self.path)
             gen = src.blocks(0)
-        else:
-            fd = os.open(self.path, os.O_RDONLY)
         try:
-            while not self._halt:
-                if left is not None:
-                    if left == 0:
-                        fastq.PINNED.give(buf)
-                        buf = None
-                        self._put(None)
-                        return
-                    need = 4 * min(self.chunk_reads, left)
-                while skip and not eof and lines < skip:  # (the share starts `skip` lines into its first gzip member)
-                    item = next(gen, None)
-                    if item is None:
-                        eof = True
-                        break
-                    text, nbytes = item
-                    buf = self._room(buf, fill, nbytes)
-                    C.memmove(buf.ctypes.data + fill, text.ctypes.data, nbytes)
-                    if isinstance(text.base, fastq.mmap.mmap):
-                        fastq.ARENA.give(text)
-                    lines += int(L.csh_count_newlines(buf.ctypes.data + fill, nbytes))
-                    fill += nbytes
-                if skip and lines >= skip:
-                    cut = int(L.csh_after_kth_newline(buf.ctypes.data, fill, skip))
-                    C.memmove(buf.ctypes.data, buf.ctypes.data + cut, fill - cut)
-                    fill -= cut
-                    lines -= skip
-                    marks = [(0, fill, lines)]
-                    skip = 0
-                while lines < need and not eof:
-                    if gen is not None:
-                        item = next(gen, None)
-                        if item is None:
-                            eof = True
-                            break
-                        text, nbytes = item
-                        if self.gz and PROFILE:
-                            _count_inflate("host_blocks", 1)
-                        if buf.size - fill < nbytes:
-                            for f in copies:
-                                f.result()
-                            copies = []
-                            buf = self._room(buf, fill, nbytes)
-                        got = src.side(text)
-                        if got is None:
-                            got = int(L.csh_count_newlines(text.ctypes.data, nbytes))
-                        copies.append(fastq._pool().submit(self._copy_in, buf.ctypes.data + fill, text, nbytes))
-                        marks.append((fill, nbytes, got))
-                        fill += nbytes
-                        lines += got
-                    else:
-                        missing = max(_BLOCK, int((need - lines) / 4 * est * 1.05) - 0)
-                        t0 = time.perf_counter()
-                        buf, fill, more, eof = self._read_plain(fd, pos, buf, fill, missing)
-                        _tick("read", t0)
-                        pos += sum(m[1] for m in more)
-                        lines += sum(m[2] for m in more)
-                        marks += more
-                for f in copies:
-                    f.result()
-                copies = []
-                if lines >= need:
-                    # the block ends right behind newline number `need`: find the piece that holds it, then the byte
-                    t0 = time.perf_counter()
-                    cum, cut = 0, -1
-                    for off, nbytes, got in marks:
-                        if cum + got >= need:
-                            cut = off + int(L.csh_after_kth_newline(buf.ctypes.data + off, nbytes, need - cum))
-                            break
-                        cum += got
-                    assert cut > 0
-                    nxt = fastq.PINNED.take(max(buf.size, int(self.chunk_reads * est * 1.25) + 2 * _BLOCK))
-                    carry = fill - cut
-                    C.memmove(nxt.ctypes.data, buf.ctypes.data + cut, carry)
-                    block = self._block(buf, cut, need // 4, done)
-                    done += need // 4
-                    if left is not None:
-                        left -= need // 4
-                    est = max(64, cut // (need // 4) + 1)
-                    buf, fill, lines = nxt, carry, lines - need
-                    marks = [(0, carry, lines)]
-                    _tick("cut+carry", t0)
-                    if not self._put(block):
-                        block.release()
-                        return
-                    continue
-                # End of input: what is left must be whole records; blank lines behind the last one are tolerated.
-                # The last NON-BLANK line decides: it is line 4k + 3 (a quality line: the record ends with it, the
-                # device takes the end of the text for its missing line end) or line 4k + 2 (a '+' line: the record
-                # has an empty read, "@id\n\n+\n\n", and its empty quality line is the first blank line behind it).
-                # Only whole blank lines beyond that are dropped -- stripping all trailing white space took the
-                # empty quality line with it and turned a valid file into "truncated".
-                end = fill
-                view = memoryview(buf)
-                while end > 0 and view[end - 1] in b"\n\r \t":
-                    end -= 1
-                if end == 0:
-                    fastq.PINNED.give(buf)
-                    buf = None
-                    self._put(None)
-                    return
-                last = int(L.csh_count_newlines(buf.ctypes.data, end))  # index of the last non-blank line
-                if last % 4 == 3:
-                    tail_lines = last + 1
-                elif last % 4 == 2 and end < fill:
-                    # the '+' line's own line end, then the empty quality line (its '\n' is written if the file lacks it)
-                    tail = bytes(view[end:fill])  # white space only
-                    nl1 = tail.find(b"\n")
-                    if nl1 < 0:
-                        raise fastq.FastqFormatError(f"{self.path}: truncated FASTQ record at end of file")
-                    nl2 = tail.find(b"\n", nl1 + 1)
-                    if nl2 >= 0:
-                        end += nl2 + 1
-                    else:
-                        buf = self._room(buf, fill, 1)
-                        buf[fill] = 0x0A
-                        end = fill + 1
-                    tail_lines = last + 2
-                else:
-                    raise fastq.FastqFormatError(f"{self.path}: truncated FASTQ record at end of file")
-                block = self._block(buf, end, tail_lines // 4, done)
-                buf = None
-                if self._put(block):
-                    self._put(None)
-                else:
-                    block.release()
-                return
+            for text, nbytes in gen:
+                if self.gz and PROFILE:
+                    _count_inflate("host_blocks", 1)
+                pend.room(nbytes)
+                got = src.side(text)
+                if got is None:
+                    got = int(L.csh_count_newlines(text.ctypes.data, nbytes))
+                pend.copies.append(fastq._pool().submit(_copy_in, pend.buf.ctypes.data + pend.fill, text, nbytes))
+                pend.added(nbytes, got)
+                yield True
         finally:
-            for f in copies:
-                try:
-                    f.result()
-                except BaseException:
-                    pass
-            if buf is not None:
-                fastq.PINNED.give(buf)
-            if gen is not None:
-                if hasattr(gen, "close"):
-                    gen.close()
-                src.close()
-            if fd >= 0:
-                os.close(fd)
+            if hasattr(gen, "close"):
+                gen.close()
+            src.close()
 
-    # -- device mode: BGZF blocks inflate into the inflater's buffers, the bookkeeping above mirrored on them -------------
+    def _host_text(self, pend: _Pending, pos: int):
+        return self._block_text(pend, pos) if self.gz or self.sequential else self._plain_text(pend, pos)
+
     def _refused(self, mapped, lo: int, hi: int, index: int):
         """The inflater refused block ``index`` of the span [lo, hi): the host path decides.  What it raises for a corrupt
         file today, it raises now; if it takes the span, the two decoders disagree, and that is an engine fault."""
@@ -449,92 +431,101 @@ class TextReader(threading.Thread):
         raise RuntimeError(f"{self.path}: the device decoder disagrees with libdeflate: it refused BGZF block {index} of "
                            f"the blocks at compressed offset {lo}, which libdeflate inflates without an error")
 
-    def _run_device(self):
+    def _bgzf_text(self, pend: _Pending):
+        """The device mode: the BGZF blocks at the head of the file, a span at a time, inflated into ``pend``'s buffer by
+        its memory, an inflater (``inflater.py``); one piece per block (ISIZE, newlines from the inflater).  When the run
+        ends -- the end of the file, a member that is not BGZF, a block cut short -- what is left goes to a pinned host
+        buffer and the host's source goes on behind it: a foreign tail member, blank lines, a missing final newline, an
+        empty last read are all the host's business, in one place."""
         from .inflater import SPAN
-        inf = self._make_inflater()
-        need = 4 * self.chunk_reads
-        est = 400
+        inf, pos = pend.mem, 0
         fh = open(self.path, "rb")
         mm = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
         mapped = np.frombuffer(mm, dtype=np.uint8)
-        buf = inf.take(int(self.chunk_reads * est * 1.25) + 2 * _BLOCK)
-        fill, lines, done, pos = 0, 0, 0, 0
-        marks: List[tuple] = []  # one per BGZF block behind buf[:fill]: (offset, ISIZE, newlines from the inflater)
-        resume = None
         try:
-            while not self._halt:
-                ended = False
-                while lines < need and not ended:
-                    rows, end = codec.bgzf_index(mm, pos, pos + SPAN + (1 << 16))
-                    if not rows:  # the end of the file, a member that is not BGZF, or a block cut short
-                        ended = True
-                        break
-                    total = sum(r[2] for r in rows)  # (known beforehand: the ISIZE prefix sums are the output offsets)
-                    if buf.size - fill < total:
-                        bigger = inf.take(max(buf.size + buf.size // 2, fill + total))
-                        inf.copy(bigger, 0, buf, 0, fill)
-                        inf.give(buf)
-                        buf = bigger
-                    t0 = time.perf_counter()
-                    got, bad = inf.inflate(mapped, pos, rows, buf, fill)
-                    _tick("device_inflate", t0)
-                    if bad >= 0:
-                        self._refused(mm, pos, end, bad)
-                    for (_, _, isize, _), found in zip(rows, got):
-                        marks.append((fill, isize, int(found)))
-                        fill += isize
-                        lines += int(found)
-                    if PROFILE:
-                        _count_inflate("device_blocks", len(rows))
-                    pos = end
-                if lines < need:
-                    break  # the BGZF run has ended: less than one block of records is left
+            while True:
+                rows, end = codec.bgzf_index(mm, pos, pos + SPAN + (1 << 16))
+                if not rows:
+                    break
+                pend.room(sum(r[2] for r in rows))  # (known beforehand: the ISIZE prefix sums are the output offsets)
                 t0 = time.perf_counter()
-                cum, cut, at = 0, -1, 0
-                for at, (off, nbytes, found) in enumerate(marks):
-                    if cum + found >= need:
-                        cut = off + inf.after_kth_newline(buf, off, nbytes, need - cum)
-                        break
-                    cum += found
-                assert cut > 0
-                nxt = inf.take(max(buf.size, int(self.chunk_reads * est * 1.25) + 2 * _BLOCK))
-                carry = fill - cut
-                inf.copy(nxt, 0, buf, cut, carry)
-                block = TextBlock(None, cut, need // 4, done, dbuf=buf, owner=inf)
-                done += need // 4
-                est = max(64, cut // (need // 4) + 1)
-                off, nbytes, found = marks[at]  # the block the cut went through keeps its rest, the others move up
-                marks = [(0, off + nbytes - cut, found - (need - cum))] + [(o - cut, n, f) for o, n, f in marks[at + 1:]]
-                buf, fill, lines = nxt, carry, lines - need
-                _tick("cut+carry", t0)
-                if not self._put(block):
-                    block.release()
-                    return
-            if self._halt:
-                return
-            # End of the run: what is left goes to a pinned host buffer, and the host path finishes -- a foreign tail
-            # member, blank lines, a missing final newline, an empty last read are all its business, in one place.
-            hbuf = fastq.PINNED.take(fill + 2 * _BLOCK)
-            inf.to_host(hbuf, buf, 0, fill)
-            resume = (hbuf, fill, lines, done, pos)
+                got, bad = inf.inflate(mapped, pos, rows, pend.buf, pend.fill)
+                _tick("device_inflate", t0)
+                if bad >= 0:
+                    self._refused(mm, pos, end, bad)
+                for (_, _, isize, _), found in zip(rows, got):
+                    pend.added(isize, int(found))
+                if PROFILE:
+                    _count_inflate("device_blocks", len(rows))
+                pos = end
+                yield True
+            pend.to_host(2 * _BLOCK)
+            inf.close()
         finally:
-            if buf is not None:
-                inf.give(buf)
             del mapped
             try:
                 mm.close()
             except BufferError:
                 pass
             fh.close()
-            inf.close()
-        self._run(resume=resume)
+        yield from self._host_text(pend, pos)
+
+    # -- the one cutting loop: fill up to `need` lines, cut, carry -- in pinned memory or in an inflater's ------------------
+    def _cut_blocks(self, pend: _Pending, source) -> None:
+        done, skip = 0, self.skip_lines
+        left = self.max_records  # records still to hand out (None: everything)
+
+        def fill(goal: int) -> None:
+            pend.goal = goal
+            while pend.lines < goal and next(source, False):
+                pass
+            pend.settle()
+
+        while not self._halt and left != 0:
+            need = 4 * (self.chunk_reads if left is None else min(self.chunk_reads, left))
+            if skip:  # (the share starts `skip` lines into its first gzip member)
+                fill(skip)
+                if pend.lines >= skip:
+                    pend.drop_lines(skip)
+                    skip = 0
+            fill(need)
+            if pend.lines < need:  # the end of the input (a source that ends leaves the text in pinned memory)
+                end, records, newline = _end_of_input(memoryview(pend.buf)[:pend.fill], self.path)
+                if records and newline:
+                    pend.room(1)
+                    pend.buf[end - 1] = 0x0A
+                if records:
+                    block, pend.buf = self._block(_HOST, pend.buf, end, records, done), None
+                    if not self._put(block):
+                        block.release()
+                        return
+                break
+            # the block ends right behind newline number `need`
+            t0 = time.perf_counter()
+            buf, cut = pend.cut(need)
+            block = self._block(pend.mem, buf, cut, need // 4, done)
+            done += need // 4
+            if left is not None:
+                left -= need // 4
+            pend.est = max(64, cut // (need // 4) + 1)
+            _tick("cut+carry", t0)
+            if not self._put(block):
+                block.release()
+                return
+        self._put(None)
 
     def run(self):
         try:
-            if self._make_inflater is not None:
-                self._run_device()
-            else:
-                self._run()
+            mem = self._make_inflater() if self._make_inflater is not None else _HOST
+            pend = _Pending(mem, self.chunk_reads)
+            source = self._bgzf_text(pend) if mem is not _HOST else self._host_text(pend, self.start_at)
+            try:
+                self._cut_blocks(pend, source)
+            finally:
+                pend.close()
+                source.close()
+                if pend.mem is not _HOST:  # (the BGZF source closes the inflater behind its last block; it did not get there)
+                    pend.mem.close()
         except BaseException as exc:
             self._put(fastq._Failure(exc))
 
