@@ -242,7 +242,8 @@ def test_device_compressed_output_is_gzip_of_the_same_text(n, lz, monkeypatch):
     stored blocks where that does not pay: the one-record case) -- any inflater must give back exactly the text the
     uncompressed form returns, CRC-32 and ISIZE included (Python's gzip checks both).  The ratio is pinned: the
     counterpart of xopen's level-1 writer must not quietly get worse (zlib level 1 on the same text is within a few
-    per cent of the LZ form, profiles/r04_gzip_ratio.json)."""
+    per cent of the LZ form, profiles/r04_gzip_ratio.json).
+    What the member IS -- layout, tokens, codes -- is held to tests/gzip_rule.py in tests/test_gpu_gzip_structure.py."""
     import gzip
     import zlib
     if not lz:
