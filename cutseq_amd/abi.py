@@ -169,7 +169,7 @@ class cs_text_params(C.Structure):
         ("has_umi", C.c_uint8),
         ("untrimmed_filter", C.c_uint8),
         ("reverse_complement", C.c_uint8),
-        ("compress", C.c_uint8),
+        ("compress", C.c_uint8),  # 0 text, 1 one gzip member per route, 2 BGZF blocks (no EOF marker)
         ("max_tag", C.c_uint32),
         ("suffix1", C.c_char_p * 2),
         ("suffix2", C.c_char_p * 2),

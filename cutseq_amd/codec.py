@@ -96,6 +96,29 @@ def gzip_member(data, level: int = 1) -> bytes:
     return bytes(memoryview(out)[:got])
 
 
+BGZF_HEADER = bytes.fromhex("1f8b08040000000000ff060042430200")  # + BSIZE: the block's size less one, 16 bits
+BGZF_EOF = BGZF_HEADER + bytes.fromhex("1b0003000000000000000000")  # the empty block that ends a BGZF file
+BGZF_TEXT = 65280  # text bytes per block of the host writer (bgzip's figure: a stored block of them fits 64 KiB)
+
+
+def bgzf_blocks(data, level: int = 1) -> bytes:
+    """``data`` (bytes-like) as BGZF blocks of at most ``BGZF_TEXT`` text bytes each, without the EOF marker: the host
+    form of what the device writes with ``cs_text_params.compress = 2``.  Every block is :func:`gzip_member`'s deflate
+    stream of its piece behind the 18-byte BGZF header; one that would not fit 64 KiB that way is stored."""
+    mv = memoryview(data).cast("B")
+    out = []
+    for lo in range(0, len(mv), BGZF_TEXT):
+        piece = mv[lo:lo + BGZF_TEXT]
+        member = gzip_member(piece, level)
+        assert member[3] == 0, "gzip_member: a header with optional fields"
+        payload, trailer = member[10:-8], member[-8:]
+        if 18 + len(payload) + 8 > 65536:  # (incompressible text: one stored block, final)
+            n = len(piece)
+            payload = b"\x01" + struct.pack("<HH", n, ~n & 0xFFFF) + bytes(piece)
+        out += (BGZF_HEADER, struct.pack("<H", 18 + len(payload) + 8 - 1), payload, trailer)
+    return b"".join(out)
+
+
 def _decompressor():
     d = getattr(_tls, "decomp", None)
     if d is None:

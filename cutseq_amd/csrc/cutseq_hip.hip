@@ -1547,6 +1547,7 @@ struct cs_text {
   uint32_t seg_blocks = 0, fmt_blocks = 0;
   bool needs_cap2 = false;
   bool compress = false;      // the output streams leave the device as gzip members
+  bool bgzf = false;          // ... as BGZF blocks, one per chunk (cs_text_params.compress = 2; the info table's too)
   bool mixed_formats = false; // the streams differ in format (tp.fasta_routes): format_copy decides per record
   bool literal_only = false;  // ... from literal-only blocks (CUTSEQ_GPU_LZ=0: no run / record-name matches)
   uint32_t max_chunks = 0;
@@ -1576,7 +1577,7 @@ __global__ void text_init_meta(cstext::TextMeta *m) {
 // into them.  `route_bytes` / `gz_route_bytes`: the [route][mate] sizes of the stream's mate, raw (in) and gzip (out).
 void launch_deflate(hipStream_t rs, const GzStream &z, const uint8_t *text, const unsigned long long *route_bytes,
                     unsigned long long *gz_route_bytes, uint32_t n_routes, unsigned long long *gz_total,
-                    uint32_t fasta_classes, bool literal_only, const unsigned long long *gate) {
+                    uint32_t fasta_classes, bool literal_only, bool bgzf, const unsigned long long *gate) {
   csdefl::DeflateArgs da;
   da.text = text;
   da.route_bytes = route_bytes;
@@ -1587,7 +1588,22 @@ void launch_deflate(hipStream_t rs, const GzStream &z, const uint8_t *text, cons
   da.gate = gate;
   da.fasta_classes = fasta_classes;
   da.literal_only = literal_only ? 1u : 0u;
-  hipLaunchKernelGGL(csdefl::deflate_chunks, dim3(z.chunks), dim3(256), 0, rs, da);
+  if (bgzf) {  // every chunk a BGZF block of its own: one kernel finds its place and wraps the copy
+    hipLaunchKernelGGL(csdefl::deflate_chunks<true>, dim3(z.chunks), dim3(256), 0, rs, da);
+    csdefl::BgzfArgs ba;
+    ba.info = z.chunk;
+    ba.stage = z.stage;
+    ba.route_bytes = route_bytes;
+    ba.n_routes = n_routes;
+    ba.chunk_dst = z.chunk_dst;
+    ba.gz = z.gz;
+    ba.gz_route_bytes = gz_route_bytes;
+    ba.gz_total = gz_total;
+    ba.gate = gate;
+    hipLaunchKernelGGL(csdefl::bgzf_layout, dim3(z.chunks), dim3(256), 0, rs, ba);
+    return;
+  }
+  hipLaunchKernelGGL(csdefl::deflate_chunks<false>, dim3(z.chunks), dim3(256), 0, rs, da);
   csdefl::LayoutArgs la;
   la.info = z.chunk;
   la.route_bytes = route_bytes;
@@ -1829,7 +1845,12 @@ int cs_text_create_interleaved(cs_engine *eng, const cs_text_params *params, uin
     }
   // a second capture exists only in single-end chains (cs_cap2)
   t->needs_cap2 = !eng->paired && params->has_umi;
+  if (params->compress > 2) {
+    delete t;
+    return fail(CS_ERR_ARG, "compress = %u: 0 (text), 1 (gzip members) or 2 (BGZF blocks)", (unsigned)params->compress);
+  }
   t->compress = params->compress != 0;
+  t->bgzf = params->compress == 2;
   {
     const char *env = getenv("CUTSEQ_GPU_LZ");
     t->literal_only = env && atoi(env) == 0;
@@ -2199,7 +2220,7 @@ static int text_submit_from(cs_text *t, uint32_t slot, const void *text1, uint64
       LAUNCH_NAMED(csinfo::info_copy, dim3((uint32_t)(iwant > 32768ull ? 32768ull : iwant)), dim3(256), fa, t->tp, ia);
       if (t->info & CS_INFO_GZIP) {  // one more stream for the deflate kernels: one gzip member per batch, like a route
         launch_deflate(rs, s.info_gz, s.d_info, &s.d_imeta->bytes, &s.d_imeta->gz_bytes, 1, &s.d_imeta->gz_total, 0,
-                       t->literal_only, &s.d_meta->err);
+                       t->literal_only, t->bgzf, &s.d_meta->err);
       }
       HIP_TRY(hipGetLastError());
     }
@@ -2210,7 +2231,7 @@ static int text_submit_from(cs_text *t, uint32_t slot, const void *text1, uint64
         for (uint32_t c = 0; c < 4u; ++c) fasta_classes |= ((t->tp.fasta_routes >> (2u * c + m)) & 1u) << c;
         launch_deflate(rs, s.gz[m], s.d_out[m], t->route_block ? &s.d_routes->bytes[0][m] : &s.d_meta->route_bytes[0][m],
                        t->route_block ? &s.d_routes->gz_bytes[0][m] : &s.d_meta->gz_route_bytes[0][m], t->n_routes,
-                       &s.d_meta->gz_bytes[m], fasta_classes, t->literal_only, &s.d_meta->err);
+                       &s.d_meta->gz_bytes[m], fasta_classes, t->literal_only, t->bgzf, &s.d_meta->err);
       }
       HIP_TRY(hipGetLastError());
     }

@@ -16,6 +16,9 @@
 // wraps the chunks of a stream into ONE gzip member (header, blocks, final empty block, CRC-32, ISIZE): the host
 // writes the bytes it downloads, nothing else.  Any inflater reads the result; what parity is defined on -- the
 // decompressed bytes -- is unchanged.
+// BGZF (cs_text_params.compress = 2, the CLI's --bgzf): the same chunks, each a gzip member of its own with htslib's
+// 'BC' extra field -- deflate_chunks<true> and bgzf_layout in place of deflate_chunks<false>, deflate_layout and
+// deflate_compact; see bgzf_layout.
 
 namespace csdefl {
 
@@ -429,6 +432,9 @@ __device__ __forceinline__ uint32_t crc_step(const uint32_t *crc_tab, uint32_t c
   return crc_tab[(crc ^ byte) & 0xffu] ^ (crc >> 8);
 }
 
+// kBgzf (cs_text_params.compress = 2): the chunk is a stream of its own -- its first byte has no byte in front of it
+// and starts a line -- so that its block inflates alone.  A template parameter: the kernel is register-critical.
+template <bool kBgzf>
 __global__ void __launch_bounds__(256) deflate_chunks(DeflateArgs a) {
   if (a.gate && *a.gate != ~0ull) return;
   __shared__ uint32_t obuf[kOutWords];
@@ -496,7 +502,7 @@ __global__ void __launch_bounds__(256) deflate_chunks(DeflateArgs a) {
     for (int d = 0; d < 33; ++d) raw[d] = (uint32_t)d < words ? al[d] : 0u;
 #pragma unroll
     for (int d = 0; d < 32; ++d) w[d] = __builtin_amdgcn_alignbyte(raw[d + 1], raw[d], shift);
-    if (n_valid && (chunk0 + lo) > 0) prev_byte = src[(long long)lo - 1];
+    if (n_valid && (kBgzf ? (long long)lo : chunk0 + lo) > 0) prev_byte = src[(long long)lo - 1];
   }
   // CRC-32 of the slice, moved to the chunk's front by the bytes behind it (see crc_step)
   uint32_t crc_moved = 0;
@@ -542,7 +548,7 @@ __global__ void __launch_bounds__(256) deflate_chunks(DeflateArgs a) {
       for (uint32_t i = m128_next_set(m.nl, 0u); i < 128u && at < kMaxLines; i = m128_next_set(m.nl, i + 1u)) u.nl_pos[at++] = (uint16_t)(lo + i);
     }
     __syncthreads();
-    const bool chunk_starts_line = chunk0 == 0 || src[-1] == '\n';
+    const bool chunk_starts_line = kBgzf || chunk0 == 0 || src[-1] == '\n';
     if (n_valid)
       find_matches(src, lo, n_valid, m, prev_byte == 0x100u || prev_byte == '\n', lines_before, u.nl_pos, lines, chunk_starts_line,
                    [&](uint32_t at, uint32_t len, uint32_t dist) {
@@ -787,6 +793,87 @@ __global__ void __launch_bounds__(256) deflate_compact(CompactArgs a) {
   const uint8_t *src = a.stage + (size_t)blockIdx.x * kSlot;
   uint8_t *dst = a.gz + a.chunk_dst[blockIdx.x];
   for (uint32_t i = threadIdx.x; i < n; i += 256) dst[i] = src[i];
+}
+
+// ---- BGZF (cs_text_params.compress = 2): every chunk is a gzip member of its own, a BGZF block (SAM specification 4.1):
+// 18 header bytes -- FEXTRA with the subfield 'B' 'C', whose value BSIZE is the block's size less one --, the chunk as
+// deflate_chunks<true> staged it, the final empty fixed block, the CHUNK's CRC-32 and length.  Nothing is combined and no
+// route is walked serially: a chunk's place is the sum of comp_len + kBgzfWrap over the chunks in front of it, routes
+// back to back, and the block that copies a chunk finds that sum itself (a few thousand chunks a batch at most: a dozen
+// loads a thread), writes the header and the trailer around the copy, and the route's and the mate's sizes where its
+// chunk is the route's or the mate's last.  The EOF marker is the file's, not the stream's: the host appends it.
+constexpr uint32_t kBgzfHead = 18, kBgzfTail = 10, kBgzfWrap = kBgzfHead + kBgzfTail;
+static_assert(kBgzfWrap + kChunk + 5u <= 65536u, "BSIZE: a stored chunk's block has to fit 16 bits");
+static_assert(kBgzfWrap + kChunk + 5u <= kSlot, "a block takes no more of the gz buffer than its chunk's staging slot");
+static_assert(kOutWords * 4u <= kChunk + 5u, "a dynamic chunk is no larger than a stored one");
+
+struct BgzfArgs {
+  const ChunkInfo *info;
+  const uint8_t *stage;
+  const unsigned long long *route_bytes;  // [route * 2]: raw bytes of the stream
+  uint32_t n_routes;
+  uint32_t *chunk_dst;                    // per chunk: byte offset of its block inside the mate's gzip buffer
+  uint8_t *gz;
+  unsigned long long *gz_route_bytes;     // out [route * 2]: bytes of the route's blocks (0: nothing to write)
+  unsigned long long *gz_total;           // out: sum
+  const unsigned long long *gate;
+};
+
+__global__ void __launch_bounds__(256) bgzf_layout(BgzfArgs a) {
+  if (a.gate && *a.gate != ~0ull) return;
+  __shared__ uint32_t s_sum[2][4];
+  const uint32_t tid = threadIdx.x, c = blockIdx.x;
+  // this block's chunk: its route's first chunk and chunk count, and the chunks of the mate
+  constexpr uint32_t kNone = 0xffffffffu;
+  uint32_t total = 0, first = kNone, nch_route = 0, route = 0;
+  for (uint32_t r = 0; r < a.n_routes; ++r) {
+    const uint32_t nch = (uint32_t)((a.route_bytes[r * 2] + kChunk - 1) / kChunk);
+    if (first == kNone && c < total + nch) {
+      first = total;
+      nch_route = nch;
+      route = r;
+    }
+    if (c == 0 && tid == 0 && nch == 0) a.gz_route_bytes[r * 2] = 0;
+    total += nch;
+  }
+  if (c == 0 && tid == 0 && total == 0) *a.gz_total = 0;
+  if (first == kNone) return;  // beyond the last chunk (block-uniform)
+  // bytes in front of the route and, from there, in front of the chunk
+  uint32_t before_route = 0, in_route = 0;
+  for (uint32_t j = tid; j < c; j += 256) {
+    const uint32_t n = a.info[j].comp_len + kBgzfWrap;
+    if (j < first) before_route += n; else in_route += n;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    before_route += __shfl_xor(before_route, o, 64);
+    in_route += __shfl_xor(in_route, o, 64);
+  }
+  if ((tid & 63u) == 0) {
+    s_sum[0][tid >> 6] = before_route;
+    s_sum[1][tid >> 6] = in_route;
+  }
+  __syncthreads();
+  before_route = s_sum[0][0] + s_sum[0][1] + s_sum[0][2] + s_sum[0][3];
+  in_route = s_sum[1][0] + s_sum[1][1] + s_sum[1][2] + s_sum[1][3];
+  const ChunkInfo ci = a.info[c];
+  const uint32_t at = before_route + in_route, size = ci.comp_len + kBgzfWrap;
+  uint8_t *dst = a.gz + at;
+  if (tid < kBgzfHead) {
+    // 1f 8b 08 04 (FEXTRA), MTIME 0, XFL 0, OS ff, XLEN 6, 'B' 'C', SLEN 2, BSIZE
+    const unsigned long long h0 = 0x0000000004088b1full, h1 = 0x000243420006ff00ull;
+    dst[tid] = (uint8_t)(tid < 8u ? h0 >> (8u * tid) : tid < 16u ? h1 >> (8u * (tid - 8u)) : (size - 1u) >> (8u * (tid - 16u)));
+  } else if (tid >= 32u && tid < 32u + kBgzfTail) {
+    // 03 00 (final block, fixed Huffman, end of block), the chunk's CRC-32, its length
+    const uint32_t k = tid - 32u;
+    dst[kBgzfHead + ci.comp_len + k] = (uint8_t)(k < 2u ? 0x0003u >> (8u * k) : k < 6u ? ci.crc >> (8u * (k - 2u)) : ci.raw_len >> (8u * (k - 6u)));
+  }
+  const uint8_t *src = a.stage + (size_t)c * kSlot;
+  for (uint32_t i = tid; i < ci.comp_len; i += 256) dst[kBgzfHead + i] = src[i];
+  if (tid == 0) {
+    a.chunk_dst[c] = at;
+    if (c + 1u == first + nch_route) a.gz_route_bytes[route * 2] = (unsigned long long)in_route + size;
+    if (c + 1u == total) *a.gz_total = (unsigned long long)at + size;
+  }
 }
 
 }  // namespace csdefl

@@ -71,6 +71,7 @@ class OutputLayout:
     interleaved_in: bool = False      # --interleaved: one input file holds both mates
     interleaved_out: bool = False     # ... every class is one file of woven pairs
     info_file: Optional[str] = None
+    bgzf: bool = False                # --bgzf: every output whose container is gzip is written as BGZF
 
     @classmethod
     def of(cls, trimmed, short, untrimmed, too_long=None, barcodes=None, **flags) -> "OutputLayout":
@@ -153,13 +154,14 @@ def resolve(args, interleaved_in: bool, interleaved_out: bool, wants_untrimmed: 
     if args.demux is not None:  # one pair of trimmed files per barcode instead of the common one
         barcodes = {name: output_paths(None, inputs, args.output_prefix, f"{name}_trimmed") for name in args.demux[0]}
     return OutputLayout.of(*three, too_long, barcodes, paired=len(inputs) == 2 or interleaved_in or interleaved_out,
-                           interleaved_in=interleaved_in, interleaved_out=interleaved_out, info_file=args.info_file)
+                           interleaved_in=interleaved_in, interleaved_out=interleaved_out, info_file=args.info_file,
+                           bgzf=bool(getattr(args, "bgzf", False)))
 
 
 @dataclass(frozen=True)
 class TextOptions:
     """What a text engine is told about the outputs (the keywords of ``textpath.TextEngine`` of the same names)."""
-    compress: bool = False        # every route leaves the device as a gzip member
+    compress: int = False         # every route leaves the device as a gzip member (True) or as BGZF blocks (2: --bgzf)
     bins: int = 0                 # demultiplexing: one route per barcode behind the three ordinary ones
     fasta_routes: int = 0         # bit 2 * class + mate: that stream's records leave as FASTA
     info: int = 0                 # abi.CS_INFO_* bits: the batches also yield the --info-file table

@@ -150,6 +150,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "(-o takes one name). An interleaved run takes one name each for -o, -s, -u and "
                         "--too-long-output; '-' reads standard input / writes standard output. Not with "
                         "--demux-barcodes.")
+    p.add_argument("--bgzf", action="store_true",
+                   help="Extension: write every output whose name ends in .gz (-o, -s, -u, --too-long-output, the -O "
+                        "defaults, the barcodes' files, --info-file) as BGZF, htslib's blocked form of gzip: any gzip "
+                        "reader takes it, bgzip -r / tabix / samtools and this tool (CUTSEQ_GPU_INFLATE=1) get random "
+                        "access and parallel decoding. Blocks of 32 KiB of text, laid out on the GPU; the file ends "
+                        "with the BGZF EOF marker. Other outputs are untouched. Refused when no output is a .gz file "
+                        "and with CUTSEQ_TEXT_PATH=0.")
     p.add_argument("--rank-spec", type=str, help=argparse.SUPPRESS)  # a child of --ranks: its share of the run
     p.add_argument("--demux-barcodes", type=str, metavar="FILE",
                    help="Extension: demultiplex on the 5' inline barcode. FILE lists 'name<TAB>sequence' per line (all as "
@@ -286,6 +293,14 @@ def resolve_args(args):
     layout = args.outputs = outputs.resolve(args, interleaved_in, interleaved_out, wants_untrimmed)
     # (what the options resolved to, for callers that look: nothing in this package reads them from here on)
     args.paired, args.interleaved_in, args.interleaved_out = layout.paired, interleaved_in, interleaved_out
+    if layout.bgzf:
+        from . import codec
+        if not switches.enabled("TEXT_PATH"):
+            _fail("--bgzf needs the text path: the blocks are laid out on the GPU and closed by the text path's writers "
+                  "(CUTSEQ_TEXT_PATH=0 is set).")
+        if not any(n != "-" and codec.container_of_name(n) == "gzip" for n in layout.names()):
+            _fail("--bgzf: no output of this run is a gzip file (BGZF is a form of gzip: it goes by the .gz in an "
+                  "output's name), so the option would change nothing.")
     for cls in layout.classes:
         if not cls.barcode:
             setattr(args, cls.key, list(cls.names))
@@ -433,6 +448,10 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
     formatted / compressed / written strictly in input order (``fanout.run_ordered``)."""
     from . import capi, fastq
 
+    if args.outputs.bgzf and not switches.enabled("TEXT_PATH"):
+        # (resolve_args refuses this; a caller that flips the switch behind it must not get plain gzip members from
+        # fastq.py's writers under --bgzf)
+        _fail("--bgzf: the record path's writers (CUTSEQ_TEXT_PATH=0) write plain gzip members, not BGZF.")
     n_dev = capi.device_count()
     _phase("devices counted")
     if n_dev <= 0:

@@ -587,8 +587,11 @@ class StreamWriter:
     of about 4 MB, compressed in the pool (level 1 = cutadapt's default; any split of the text is a valid gzip
     file and decompresses to the same bytes); plain: big pieces are written with several ``pwrite`` calls at once."""
 
-    def __init__(self, path: str, level: int = 1, precompressed: bool = False):
-        """``precompressed``: what arrives are finished gzip members (the device compressed them): written as they are."""
+    def __init__(self, path: str, level: int = 1, precompressed: bool = False, bgzf: bool = False):
+        """``precompressed``: what arrives are finished gzip members (the device compressed them): written as they are.
+        ``bgzf`` (``--bgzf``; a gzip file only): the file is BGZF -- the host branch compresses into blocks
+        (``codec.bgzf_blocks``), the precompressed branch takes the device's blocks -- and :meth:`close` ends it with
+        the EOF marker."""
         # xopen's rules (cutseq/run.py:437, 754: OutputFiles): the container goes by the name's extension, "-" is
         # standard output.  gzip and plain files keep their parallel paths; bzip2 / xz / zstandard streams are
         # compressed by this writer's own thread (stdlib codecs), standard output takes sequential writes.
@@ -596,6 +599,7 @@ class StreamWriter:
         self.container = codec.container_of_name(path) if path != "-" else "plain"
         self.gz = self.container == "gzip"
         self.precompressed = precompressed and self.gz
+        self.bgzf = bgzf and self.gz
         self.codec = codec.make_compressor(self.container, level) if self.container in ("bz2", "xz", "zst") else None
         self.stdout = path == "-"
         if self.stdout:
@@ -619,7 +623,8 @@ class StreamWriter:
             raise self.err
         if self.gz and not self.precompressed:
             pool = fastq._pool()
-            futs = [pool.submit(codec.gzip_member, view[lo:lo + _GZ_PIECE], self.level) for lo in range(0, len(view), _GZ_PIECE)]
+            member = codec.bgzf_blocks if self.bgzf else codec.gzip_member
+            futs = [pool.submit(member, view[lo:lo + _GZ_PIECE], self.level) for lo in range(0, len(view), _GZ_PIECE)]
             self.q.put((futs, shared))
         else:
             self.q.put((view, shared))
@@ -716,7 +721,9 @@ class StreamWriter:
         self.q.put(None)
         self.t.join()
         try:
-            if self.err is None and self.gz and self.pos == 0:
+            if self.err is None and self.bgzf:
+                self._write_all(codec.BGZF_EOF)  # (an empty output is the marker alone)
+            elif self.err is None and self.gz and self.pos == 0:
                 self._write_all(codec.gzip_member(b"", self.level))  # an empty stream is still a valid gzip file
             if self.err is None and self.codec is not None:
                 tail, self.codec = self.codec[1](), None
@@ -911,15 +918,22 @@ def text_options(layout, tp, fasta: bool, gpu_deflate: bool) -> TextOptions:
     ``compress``: every output a ".gz" file -- the device compresses (deflate_kernels.hip.inc) and the writers pass the
     members through; otherwise text comes back and ".gz" outputs are deflated in the host pool.  ``info``: the
     --info-file table is one more stream per batch; its container goes by the file's name like a record output's, and a
-    ".gz" table leaves the device as gzip members under the same switch."""
+    ".gz" table leaves the device as gzip members under the same switch.  ``--bgzf`` (``layout.bgzf``): ``compress`` is
+    2, the device writes BGZF blocks; a handle has one form for all it compresses, so a ".gz" table beside records the
+    host compresses is the host's too."""
     groups = layout.name_groups(tp.swap_outputs)
     names = layout.names(info=False)
+    compress = gpu_deflate and bool(names) and all(n != "-" and codec.container_of_name(n) == "gzip" for n in names)
+    if compress and layout.bgzf:
+        compress = 2
     info = 0
     if layout.info_file:
         info_gz = gpu_deflate and layout.info_file != "-" and codec.container_of_name(layout.info_file) == "gzip"
+        if layout.bgzf and not compress:
+            info_gz = False
         info = abi.CS_INFO_ON | (abi.CS_INFO_GZIP if info_gz else 0) | (abi.CS_INFO_NO_QUAL if fasta else 0)
     return TextOptions(
-        compress=gpu_deflate and bool(names) and all(n != "-" and codec.container_of_name(n) == "gzip" for n in names),
+        compress=compress,
         bins=len(tp.demux.barcodes) if tp.demux is not None else 0,  # (table form: the pairs of barcode b are route 3 + b)
         # (an interleaved class is one file, hence one format: both mates' bits follow its name)
         fasta_routes=output_formats([g * 2 for g in groups] if layout.interleaved_out else groups, has_qualities=not fasta),
@@ -966,7 +980,7 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         options = text_options(layout, tp, r1.fasta, switches.enabled("GPU_DEFLATE"))
 
         def writer(name, precompressed):
-            opened.append(StreamWriter(name, precompressed=precompressed))
+            opened.append(StreamWriter(name, precompressed=bool(precompressed), bgzf=layout.bgzf))
             return opened[-1]
 
         outs = [[writer(n, options.compress) if n else None for n in names] for names in layout.name_groups(tp.swap_outputs)]

@@ -62,7 +62,7 @@ class TextEngine:
     """``slots`` batches in flight on one :class:`TrimEngine` (its plan, streams and statistics block)."""
 
     def __init__(self, engine: TrimEngine, slots: int = 3, max_text_bytes: int = 64 << 20, max_records: int = 1 << 18,
-                 stride: int = 152, compress: bool = False, bins: int = 0, fasta: bool = False,
+                 stride: int = 152, compress: int = False, bins: int = 0, fasta: bool = False,
                  fasta_routes: int = 0, info: int = 0, too_long_route: bool = False,
                  interleave_in: bool = False, interleave_out: bool = False, mate2_first: bool = False, rename=None):
         """``rename``: a :class:`cutseq_amd.rename.Compiled` -- cutadapt's ``--rename``, every record's name by that template
@@ -75,7 +75,8 @@ class TextEngine:
         fourth stream (:meth:`routes`), class 3 of ``fasta_routes``; the plan needs ``max_length`` and no ``bins``.
         ``info``: ``abi.CS_INFO_*`` bits -- the batch also yields cutadapt's ``--info-file`` table for read 1
         (:meth:`info`, :meth:`fetch_info`).  ``compress``: every route's output leaves the device as one gzip member (``res.route_bytes`` then counts
-        compressed bytes): what ``.gz`` output files take as they are.  ``bins``: the plan demultiplexes (table form)
+        compressed bytes): what ``.gz`` output files take as they are; 2: as BGZF blocks, one per 32 KB chunk, without the
+        EOF marker (``cs_text_params.compress``).  ``bins``: the plan demultiplexes (table form)
         into that many barcodes; the trimmed records of barcode b are route 3 + b (:meth:`routes`).  ``fasta``: every
         record leaves as ``>id\nsequence\n``; ``fasta_routes``: the same per stream, bit ``2 * class + mate`` (class 0
         trimmed, 1 too short, 2 untrimmed, 3 every barcode's route), for output files that name different formats."""
@@ -87,7 +88,7 @@ class TextEngine:
         p.has_umi = 1 if plan.has_umi else 0
         p.untrimmed_filter = 1 if plan.untrimmed_filter else 0
         p.reverse_complement = 1 if plan.reverse_complement else 0
-        p.compress = 1 if compress else 0
+        p.compress = 2 if compress == 2 else (1 if compress else 0)
         p.fasta_out = 1 if fasta else 0  # records leave as ">id\nsequence\n" (no qualities to write)
         p.fasta_routes = int(fasta_routes)
         self.compress = bool(compress)

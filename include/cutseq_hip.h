@@ -463,7 +463,13 @@ typedef struct cs_text_params {
   uint8_t compress;           /* 1: every route's output leaves the device as ONE gzip member (32 KB deflate blocks with
                                  their own dynamic Huffman codes behind an LZ77 stage -- byte runs and the previous
                                  record's name as matches, bases as literals; the counterpart of xopen's level-1 writer
-                                 the reference's OutputFiles use): route_bytes / out_bytes then count compressed bytes  */
+                                 the reference's OutputFiles use): route_bytes / out_bytes then count compressed bytes.
+                                 2: BGZF -- every 32 KB chunk of every stream the handle compresses (the info table's
+                                 with CS_INFO_GZIP) is a gzip member of its own with the 'BC' extra field: 18 header
+                                 bytes, the chunk's blocks, 03 00, the chunk's CRC-32 and length; at most 32 801 bytes;
+                                 no run reaches in front of its chunk.  A route's bytes are its blocks back to back,
+                                 WITHOUT the 28-byte EOF marker: that ends a file, and the host appends it.
+                                 Other values: CS_ERR_ARG                                                              */
   uint32_t max_tag;           /* most bytes a record name can gain: 1 + the plan's capture lengths (0 = no UMI) */
   const char *suffix1[2];     /* SuffixRemover literals of mate 1, applied in order (NULL = none)               */
   const char *suffix2[2];

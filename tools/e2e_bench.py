@@ -3,6 +3,8 @@
 
   python tools/e2e_bench.py [pairs] [workdir] [--forms plain_warm,plain_to_gz] [--tree DIR] [--keep] [--extra='-M 100']
 
+``--forms plain_to_gz_warm`` (only when named) runs plain -> gz twice in the process and reports the second run too, with
+the bytes of the output files (``--extra='-t 16 --bgzf'`` against ``--extra='-t 16'``: profiles/bgzf_out_ab.log).
 ``--forms bgzf_to_gz`` (only when named) adds BGZF input: the same records bgzip-style, read with and without
 ``CUTSEQ_GPU_INFLATE=1`` (the caller sets it), once cold and once warm.
 
@@ -72,7 +74,8 @@ def main():
 
     def run(tag, inputs, outputs):
         if opts.forms and tag not in opts.forms and not (tag == "plain_cold" and "plain_warm" in opts.forms) \
-                and not (tag == "bgzf_to_gz_warm" and "bgzf_to_gz" in opts.forms):
+                and not (tag == "bgzf_to_gz_warm" and "bgzf_to_gz" in opts.forms) \
+                and not (tag == "plain_to_gz" and "plain_to_gz_warm" in opts.forms):
             return
         for old in work.glob("o[12].fastq"), work.glob("s[12].fastq"), work.glob("gzout_*"):
             for f in old:  # a run writes NEW files: freeing the previous run's gigabytes of tmpfs pages is not its job
@@ -95,6 +98,9 @@ def main():
     run("gz_to_gz", gz_in, ["-O", str(work / "gzout")])
     run("gz_to_gz_warm", gz_in, ["-O", str(work / "gzout")])
     run("plain_to_gz", plain_in, ["-O", str(work / "gzout")])
+    if opts.forms and "plain_to_gz_warm" in opts.forms:
+        run("plain_to_gz_warm", plain_in, ["-O", str(work / "gzout")])
+        out["plain_to_gz_warm"]["output_bytes"] = {f.name: f.stat().st_size for f in sorted(work.glob("gzout_*"))}
     if opts.forms and "bgzf_to_gz" in opts.forms:
         # bgzip'd input (what CUTSEQ_GPU_INFLATE=1 inflates on the device): written with the tests' BGZF writer -- there
         # is no bgzip here --, 65 280 bytes of text per block at zlib level 6 (bgzip's default), the pool compressing
