@@ -151,6 +151,10 @@ class cs_reads(C.Structure):
 
 CS_TEXT_OK, CS_TEXT_ERR_MALFORMED, CS_TEXT_ERR_TOO_LONG, CS_TEXT_ERR_IDS_DIFFER, CS_TEXT_ERR_LINE_COUNT = 0, 1, 2, 3, 4
 CS_TEXT_ERR_INFO_MISMATCH, CS_TEXT_ERR_INFO_OVERFLOW = 5, 6
+# cs_text_submit_bam: a refused BAM record (include/cutseq_bam.h, in the order they are tested); | _MATE2 for bam2's
+(CS_TEXT_ERR_BAM_BLOCK_SIZE, CS_TEXT_ERR_BAM_OVERRUN, CS_TEXT_ERR_BAM_NAME, CS_TEXT_ERR_BAM_ALIGNED,
+ CS_TEXT_ERR_BAM_NAME_LINE_END, CS_TEXT_ERR_BAM_NO_QUAL, CS_TEXT_ERR_BAM_QUAL_RANGE) = range(16, 23)
+CS_TEXT_ERR_BAM_MATE2 = 0x40
 CS_INFO_ON, CS_INFO_GZIP, CS_INFO_NO_QUAL = 1, 2, 4  # cs_text_params.info
 CS_INTERLEAVE_IN, CS_INTERLEAVE_OUT, CS_INTERLEAVE_OUT_MATE2_FIRST = 1, 2, 4  # cs_text_create_interleaved
 # cs_text_set_rename: segment kinds, the "written mate's own" capture, the table's limits

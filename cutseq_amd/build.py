@@ -12,7 +12,8 @@ SRC = HERE / "csrc" / "cutseq_hip.hip"
 DEPS = [SRC, HERE / "csrc" / "trim_kernel.hip.inc", HERE / "csrc" / "long_kernel.hip.inc",
         HERE / "csrc" / "text_kernels.hip.inc", HERE / "csrc" / "deflate_kernels.hip.inc",
         HERE / "csrc" / "info_kernels.hip.inc", HERE / "csrc" / "inflate_kernels.hip.inc",
-        HERE.parent / "include" / "cutseq_hip.h", HERE.parent / "include" / "cutseq_inflate.h"]
+        HERE / "csrc" / "bam_kernels.hip.inc", HERE.parent / "include" / "cutseq_hip.h",
+        HERE.parent / "include" / "cutseq_inflate.h", HERE.parent / "include" / "cutseq_bam.h"]
 OUT = HERE / "libcutseq_hip.so"
 
 
@@ -49,7 +50,8 @@ def build(force: bool = False, verbose: bool = False) -> Path:
 
 HOST_SRC = HERE / "csrc" / "cutseq_host.c"
 HOST_SRCS = (HOST_SRC, HERE / "csrc" / "pinflate.c")
-HOST_DEPS = HOST_SRCS + (HERE / "csrc" / "pinflate_loop.h", HERE.parent / "include" / "cutseq_synth.h")
+HOST_DEPS = HOST_SRCS + (HERE / "csrc" / "pinflate_loop.h", HERE.parent / "include" / "cutseq_synth.h",
+                         HERE.parent / "include" / "cutseq_bam.h")
 HOST_OUT = HERE / "libcutseq_host.so"
 
 

@@ -22,7 +22,7 @@ EXPORTS = (
     "cs_text_create", "cs_text_destroy", "cs_text_submit", "cs_text_wait", "cs_text_routes", "cs_text_fetch",
     "cs_text_info", "cs_text_fetch_info", "cs_text_create_interleaved", "cs_text_set_rename",
     "cs_copy_on_device", "cs_text_submit_device", "cs_dtext_after_kth_newline", "cs_inflate_create", "cs_inflate_destroy",
-    "cs_inflate_bgzf", "cs_polya_bp_fetch",
+    "cs_inflate_bgzf", "cs_polya_bp_fetch", "cs_text_submit_bam",
 )
 
 
@@ -159,6 +159,9 @@ def load() -> C.CDLL:
         L.cs_inflate_destroy.argtypes = [vp]
         L.cs_inflate_bgzf.restype = i32
         L.cs_inflate_bgzf.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp, vp, C.POINTER(abi.cs_inflate_result)]
+    if hasattr(L, "cs_text_submit_bam"):  # (likewise)
+        L.cs_text_submit_bam.restype = i32
+        L.cs_text_submit_bam.argtypes = [vp, u32, vp, u64, vp, vp, u64, vp, u32]
     if L.cs_abi_version() != abi.CS_ABI_VERSION:
         raise HipUnavailable(f"ABI mismatch: library {L.cs_abi_version()} vs python {abi.CS_ABI_VERSION}")
     _lib = L

@@ -925,9 +925,9 @@ class _Peeked:
 
 
 def sniff_input(path: str):
-    """-> (container, first byte of the TEXT behind leading white space, opener) where ``opener()`` gives a fresh binary
-    reader of the decompressed text.  ``path`` "-" is standard input (compression recognised by its magic bytes, as for
-    files)."""
+    """-> (container, first four bytes of the TEXT behind leading white space, opener) where ``opener()`` gives a fresh
+    binary reader of the decompressed text.  ``path`` "-" is standard input (compression recognised by its magic bytes,
+    as for files).  The first byte tells FASTA from FASTQ, all four an unaligned BAM (:func:`is_bam`)."""
     if path == "-":
         raw = sys.stdin.buffer
         head = raw.read(8) or b""
@@ -935,7 +935,7 @@ def sniff_input(path: str):
         peeked = _Peeked(head, raw)
         dec = open_decoder(peeked, container)
         text = dec.read(65536) or b""
-        first = text.lstrip()[:1]
+        first = text.lstrip()[:4]
         stream = _Peeked(text, dec)
         return container, first, (lambda: stream)
     with open(path, "rb") as fh:
@@ -947,7 +947,15 @@ def sniff_input(path: str):
 
     with opener() as dec:
         text = dec.read(65536) or b""
-    return container, text.lstrip()[:1], opener
+    return container, text.lstrip()[:4], opener
+
+
+BAM_MAGIC = b"BAM\x01"
+
+
+def is_bam(container: str, first: bytes) -> bool:
+    """What :func:`sniff_input` saw is a BAM file: a gzip container (BGZF) whose decoded text starts with the magic."""
+    return container == "gzip" and first == BAM_MAGIC
 
 
 class FastaSource:

@@ -25,6 +25,7 @@
 #include "deflate_kernels.hip.inc"
 #include "info_kernels.hip.inc"
 #include "inflate_kernels.hip.inc"
+#include "bam_kernels.hip.inc"
 
 namespace {
 
@@ -1532,6 +1533,15 @@ struct TextSlot {
   uint8_t *d_info = nullptr;
   GzStream info_gz;
   csinfo::InfoMeta *d_imeta = nullptr, *h_imeta = nullptr;
+  // cs_text_submit_bam: per text the record bytes, their offsets and the expansion's sums -- an allocation of its own,
+  // made by the first such call (a cs_text that never sees BAM records has none)
+  uint8_t *d_bam_arena = nullptr;
+  uint64_t bam_cap = 0;  // record bytes per text it holds
+  uint8_t *d_bam[2] = {nullptr, nullptr};
+  uint32_t *d_boff[2] = {nullptr, nullptr}, *d_btoff[2] = {nullptr, nullptr}, *d_bblk[2] = {nullptr, nullptr};
+  unsigned long long *d_btotal = nullptr;
+  unsigned long long *d_berr = nullptr, *h_berr = nullptr;  // the refused record's key (BamArgs.err); h_berr is pinned
+  bool bam = false;                                         // the batch in the slot came through cs_text_submit_bam
   hipEvent_t uploaded = nullptr, formatted = nullptr, fetched = nullptr;
   uint32_t n = 0;
   bool busy = false, waited = false;
@@ -1751,12 +1761,57 @@ hipError_t alloc_slot_arena(cs_text *t, TextSlot &s) {
   return e;
 }
 
+// The staging of cs_text_submit_bam for a slot that is not in flight: room for `need` record bytes per text and for the
+// offsets and sums of every record the slot can hold.  Sized by the slot's text capacity at first use -- records without
+// tags are shorter than their text --, so that only a batch heavy with tags makes it grow (a new allocation; hipFree
+// waits for the device).
+hipError_t ensure_bam_staging(cs_text *t, TextSlot &s, uint64_t need) {
+  if (s.d_bam_arena && need <= s.bam_cap) return hipSuccess;
+  if (s.d_bam_arena) {
+    hipError_t e = hipFree(s.d_bam_arena);
+    s.d_bam_arena = nullptr;
+    s.bam_cap = 0;
+    if (e != hipSuccess) return e;
+  }
+  const bool woven_in = (t->interleave & CS_INTERLEAVE_IN) != 0;
+  const int texts = woven_in ? 1 : (t->eng->paired ? 2 : 1);
+  const size_t recs = (size_t)t->max_records * (woven_in ? 2u : 1u);
+  const uint64_t cap = std::max<uint64_t>(need + need / 4 + (1ull << 20), t->max_text);
+  auto carve = [&](uint8_t *base) {
+    Carver c{base};
+    for (int m = 0; m < texts; ++m) {
+      c.take(s.d_bam[m], cap + 64);
+      c.take(s.d_boff[m], recs + 1);
+      c.take(s.d_btoff[m], recs);
+      c.take(s.d_bblk[m], (recs + 255) / 256 + 1);
+    }
+    c.take(s.d_btotal, 2);
+    c.take(s.d_berr, 1);
+    return c.at;
+  };
+  hipError_t e = s.h_berr ? hipSuccess : hipHostMalloc(&s.h_berr, sizeof(unsigned long long), hipHostMallocPortable);
+  if (e != hipSuccess) {
+    s.h_berr = nullptr;
+    return e;
+  }
+  e = hipMalloc(&s.d_bam_arena, carve(nullptr));
+  if (e != hipSuccess) {
+    s.d_bam_arena = nullptr;
+    return e;
+  }
+  carve(s.d_bam_arena);
+  s.bam_cap = cap;
+  return hipSuccess;
+}
+
 void free_text(cs_text *t) {
   if (!t) return;
   if (t->eng) (void)hipSetDevice(t->eng->device);
   for (TextSlot &s : t->slots) {
     if (s.busy && s.formatted) (void)hipEventSynchronize(s.formatted);
     if (s.d_arena) (void)hipFree(s.d_arena);  // (every device array of the slot is a piece of it)
+    if (s.d_bam_arena) (void)hipFree(s.d_bam_arena);
+    if (s.h_berr) (void)hipHostFree(s.h_berr);
     if (s.h_meta) (void)hipHostFree(s.h_meta);
     if (s.h_routes) (void)hipHostFree(s.h_routes);
     if (s.h_imeta) (void)hipHostFree(s.h_imeta);
@@ -2010,10 +2065,18 @@ int cs_text_set_rename(cs_text *t, const cs_rename_seg *segments, uint32_t n, co
   return CS_OK;
 }
 
-// cs_text_submit and cs_text_submit_device: `kind` says where the texts are; everything behind the copy into the slot's
-// text buffers is the same
+// cs_text_submit_bam: what stands in for the texts -- per text the records (host memory), their bytes and offsets.  The
+// bytes1 / bytes2 of text_submit_from are then the sizes of the texts the records expand to.
+struct BamInput {
+  const void *rec[2];
+  uint64_t bytes[2];
+  const uint32_t *off[2];
+};
+
+// cs_text_submit and cs_text_submit_device: `kind` says where the texts are; cs_text_submit_bam: `bam` holds records the
+// device expands into the slot's text buffers.  Everything behind "the text stands in the slot" is the same
 static int text_submit_from(cs_text *t, uint32_t slot, const void *text1, uint64_t bytes1, const void *text2, uint64_t bytes2,
-                            uint32_t n_records, hipMemcpyKind kind) {
+                            uint32_t n_records, hipMemcpyKind kind, const BamInput *bam = nullptr) {
   if (!t || !text1) return fail(CS_ERR_ARG, "null text engine or text");
   if (slot >= t->slots.size()) return fail(CS_ERR_ARG, "slot %u out of range", slot);
   cs_engine *eng = t->eng;
@@ -2031,22 +2094,56 @@ static int text_submit_from(cs_text *t, uint32_t slot, const void *text1, uint64
   const int texts = woven_in ? 1 : mates;  // texts uploaded and indexed
   const void *src[2] = {text1, text2};
   const uint64_t bytes[2] = {bytes1, bytes2};
-  for (int m = 0; m < texts; ++m)
+  // (records whose parts do not fit their blocks count no text: bam_sizes refuses them with their own code)
+  for (int m = 0; m < texts && !bam; ++m)
     if (n_records && !bytes[m]) return fail(CS_ERR_ARG, "mate %d: %u records in 0 bytes of text", m + 1, n_records);
+  const uint32_t text_records = (woven_in ? 2u : 1u) * n_records;  // records in one text
+  if (bam) HIP_TRY(ensure_bam_staging(t, s, std::max(bam->bytes[0], texts == 2 ? bam->bytes[1] : (uint64_t)0)));
   s.n = n_records;
   s.waited = false;
+  s.bam = bam != nullptr;
   t->submitted = true;
   hipStream_t st = eng->stream, rs = eng->resolve_stream;
-  for (int m = 0; m < texts; ++m)
-    if (bytes[m]) HIP_TRY(hipMemcpyAsync(s.d_text[m], src[m], bytes[m], kind, t->h2d));
+  if (bam) HIP_TRY(hipMemsetAsync(s.d_berr, 0xff, sizeof(unsigned long long), t->h2d));
+  for (int m = 0; m < texts; ++m) {
+    if (bam) {
+      if (bam->bytes[m]) HIP_TRY(hipMemcpyAsync(s.d_bam[m], bam->rec[m], bam->bytes[m], hipMemcpyHostToDevice, t->h2d));
+      HIP_TRY(hipMemcpyAsync(s.d_boff[m], bam->off[m], ((size_t)text_records + 1) * sizeof(uint32_t), hipMemcpyHostToDevice,
+                             t->h2d));
+    } else if (bytes[m]) {
+      HIP_TRY(hipMemcpyAsync(s.d_text[m], src[m], bytes[m], kind, t->h2d));
+    }
+  }
   HIP_TRY(hipEventRecord(s.uploaded, t->h2d));
   HIP_TRY(hipStreamWaitEvent(st, s.uploaded, 0));
   hipLaunchKernelGGL(text_init_meta, dim3(1), dim3(64), 0, st, s.d_meta);
+  if (bam && n_records) {  // the front step: records -> the text the kernels below parse
+    for (int m = 0; m < texts; ++m) {
+      csbam::BamArgs ba;
+      ba.rec = s.d_bam[m];
+      ba.off = s.d_boff[m];
+      ba.n = text_records;
+      ba.toff = s.d_btoff[m];
+      ba.blk = s.d_bblk[m];
+      ba.text = s.d_text[m];
+      ba.cap = (uint32_t)bytes[m];
+      ba.mate_flag = m ? (uint32_t)CS_TEXT_ERR_BAM_MATE2 : 0u;
+      ba.err = s.d_berr;
+      ba.meta = s.d_meta;
+      const uint32_t bb = (text_records + 255u) / 256u;
+      hipLaunchKernelGGL(csbam::bam_sizes, dim3(bb), dim3(256), 0, st, ba);
+      hipLaunchKernelGGL(cstext::text_scan_blocks, dim3(1), dim3(1024), 0, st, s.d_bblk[m], bb, 1u, s.d_btotal + m);
+      const unsigned long long want = ((unsigned long long)text_records * 32ull + 255ull) / 256ull;
+      hipLaunchKernelGGL(csbam::bam_expand, dim3((uint32_t)(want > 32768ull ? 32768ull : want)), dim3(256), 0, st, ba);
+    }
+    HIP_TRY(hipGetLastError());
+  }
   uint32_t *blk_nl[2] = {s.d_blk, s.d_blk + t->seg_blocks + 1};
   uint32_t *blk_fmt = s.d_blk + 2 * (t->seg_blocks + 1);
   if (n_records) {
     for (int m = 0; m < texts; ++m) {
-      const uint32_t nb = (uint32_t)((bytes[m] + cstext::kSeg - 1) / cstext::kSeg);
+      // (at least one block: a BAM text all of whose records were refused is empty, and the passes still run)
+      const uint32_t nb = std::max(1u, (uint32_t)((bytes[m] + cstext::kSeg - 1) / cstext::kSeg));
       hipLaunchKernelGGL(cstext::text_count_nl, dim3(nb), dim3(cstext::kSegThreads), 0, st, s.d_text[m], (uint32_t)bytes[m],
                          blk_nl[m]);
       hipLaunchKernelGGL(cstext::text_scan_blocks, dim3(1), dim3(1024), 0, st, blk_nl[m], nb, 1u, s.d_totals + m);
@@ -2241,6 +2338,7 @@ static int text_submit_from(cs_text *t, uint32_t slot, const void *text1, uint64
     if (t->info) HIP_TRY(hipMemsetAsync(s.d_imeta, 0, sizeof(csinfo::InfoMeta), rs));
   }
   HIP_TRY(hipMemcpyAsync(s.h_meta, s.d_meta, sizeof(cstext::TextMeta), hipMemcpyDeviceToHost, rs));
+  if (bam) HIP_TRY(hipMemcpyAsync(s.h_berr, s.d_berr, sizeof(unsigned long long), hipMemcpyDeviceToHost, rs));
   if (t->info) HIP_TRY(hipMemcpyAsync(s.h_imeta, s.d_imeta, sizeof(csinfo::InfoMeta), hipMemcpyDeviceToHost, rs));
   if (t->route_block) {
     if (!n_records) HIP_TRY(hipMemsetAsync(s.d_routes, 0, sizeof(RouteBlock), rs));
@@ -2261,6 +2359,41 @@ int cs_text_submit_device(cs_text *t, uint32_t slot, const void *dtext1, uint64_
   return text_submit_from(t, slot, dtext1, bytes1, dtext2, bytes2, n_records, hipMemcpyDefault);
 }
 
+int cs_text_submit_bam(cs_text *t, uint32_t slot, const void *bam1, uint64_t bytes1, const uint32_t *off1, const void *bam2,
+                       uint64_t bytes2, const uint32_t *off2, uint32_t n_records) {
+  if (!t || !bam1 || !off1) return fail(CS_ERR_ARG, "null text engine, records or offsets");
+  const bool woven_in = (t->interleave & CS_INTERLEAVE_IN) != 0;
+  if (woven_in && (bam2 || bytes2 || off2))
+    return fail(CS_ERR_ARG, "CS_INTERLEAVE_IN: both mates come in bam1 (bam2 and off2 must be NULL, bytes2 0)");
+  if (!woven_in && ((bam2 != nullptr) != t->eng->paired || (off2 != nullptr) != t->eng->paired))
+    return fail(CS_ERR_ARG, "plan is %s-end", t->eng->paired ? "paired" : "single");
+  if (n_records > t->max_records)
+    return fail(CS_ERR_ARG, "batch of %u records exceeds the slot (%u records)", n_records, t->max_records);
+  BamInput in = {{bam1, bam2}, {bytes1, bytes2}, {off1, off2}};
+  uint64_t text[2] = {0, 0};
+  const uint32_t text_records = (woven_in ? 2u : 1u) * n_records;
+  for (int m = 0; m < (woven_in || !t->eng->paired ? 1 : 2); ++m) {
+    if (in.bytes[m] >= (1ull << 31)) return fail(CS_ERR_ARG, "mate %d: a batch is limited to 2 GiB of BAM records", m + 1);
+    const uint8_t *rec = static_cast<const uint8_t *>(in.rec[m]);
+    const uint32_t *off = in.off[m];
+    for (uint32_t r = 0; r < text_records; ++r) {
+      const uint32_t a = off[r], b = off[r + 1];
+      if (b < a) return fail(CS_ERR_ARG, "mate %d: the offsets of record %u are not ascending", m + 1, r);
+      if (b > in.bytes[m]) return fail(CS_ERR_ARG, "mate %d: record %u leaves the %llu bytes of records", m + 1, r,
+                                      (unsigned long long)in.bytes[m]);
+      if (b - a < CSB_FIXED) return fail(CS_ERR_ARG, "mate %d: record %u is shorter than the %u bytes of a BAM record's fixed part",
+                                         m + 1, r, CSB_FIXED);
+      csb_shape_t s;
+      if (csb_shape(rec + a, b - a, &s) == CSB_OK) text[m] += s.text_len;  // (any other record the device refuses)
+    }
+    if (text[m] > t->max_text)
+      return fail(CS_ERR_ARG, "mate %d: the %u records expand to %llu bytes of text, the slot takes %llu "
+                  "(smaller blocks: CUTSEQ_CHUNK_READS)", m + 1, text_records, (unsigned long long)text[m],
+                  (unsigned long long)t->max_text);
+  }
+  return text_submit_from(t, slot, bam1, text[0], bam2, text[1], n_records, hipMemcpyHostToDevice, &in);
+}
+
 int cs_text_wait(cs_text *t, uint32_t slot, cs_text_result *res) {
   if (!t || !res) return fail(CS_ERR_ARG, "null argument");
   if (slot >= t->slots.size()) return fail(CS_ERR_ARG, "slot %u out of range", slot);
@@ -2272,9 +2405,11 @@ int cs_text_wait(cs_text *t, uint32_t slot, cs_text_result *res) {
   const cstext::TextMeta &m = *s.h_meta;
   res->n_records = s.n;
   res->max_len = m.max_len;
-  if (m.err != ~0ull) {
-    res->error = (int32_t)(m.err & 0xffu);
-    res->error_record = (uint32_t)(m.err >> 8);
+  // (a BAM record the front step refused: its key, not the line-count key the newline passes put in front of it)
+  const unsigned long long err = s.bam && *s.h_berr != ~0ull ? *s.h_berr : m.err;
+  if (err != ~0ull) {
+    res->error = (int32_t)(err & 0xffu);
+    res->error_record = (uint32_t)(err >> 8);
   }
   for (int q = 0; q < 3; ++q) {
     res->route_count[q] = m.route_count[q];

@@ -766,3 +766,60 @@ int64_t csh_fasta_to_fastq(const uint8_t *src, int64_t n, uint8_t *dst, int64_t 
   *records = recs;
   return o;
 }
+
+/* ---- unaligned BAM input: where the records start ------------------------------------------------------------------
+ * Records are length-prefixed: their starts are a serial chain, one cached load per hop, walked here; everything a
+ * record holds is the device's to check and to expand (bam_kernels.hip.inc).  The decisions both sides share live in
+ * include/cutseq_bam.h. */
+#include "../../include/cutseq_bam.h"
+
+/* The header of the inflated BAM stream buf[0 .. n): "BAM\1", l_text, text, n_ref, n_ref x (l_name, name, l_ref).
+ * -> its size (the first record starts there), 0 while it is not all in the buffer, -1 for a wrong magic, -2 for a
+ * negative length field. */
+int64_t csh_bam_header(const uint8_t *buf, int64_t n) {
+  static const uint8_t magic[4] = {'B', 'A', 'M', 1};
+  if (memcmp(buf, magic, (size_t)(n < 4 ? (n < 0 ? 0 : n) : 4)) != 0) return -1;
+  int64_t at = 4;
+  if (n < at + 4) return 0;
+  const int32_t l_text = (int32_t)csb_u32(buf + at);
+  if (l_text < 0) return -2;
+  at += 4 + (int64_t)l_text;
+  if (n < at + 4) return 0;
+  const int32_t n_ref = (int32_t)csb_u32(buf + at);
+  if (n_ref < 0) return -2;
+  at += 4;
+  for (int32_t r = 0; r < n_ref; ++r) {
+    if (n < at + 4) return 0;
+    const int32_t l_name = (int32_t)csb_u32(buf + at);
+    if (l_name < 0) return -2;
+    at += 4 + (int64_t)l_name + 4;
+    if (n < at) return 0;
+  }
+  return at;
+}
+
+/* Up to max_records records that lie completely inside buf[from .. n), n < 2^31: offsets[i] = where record i starts.
+ * -> how many; *next = where the walk stopped (the end of the last record found: the start of the first one that is
+ * incomplete, beyond max_records, or bad), *text_bytes = the FASTQ text they expand to (a record whose parts do not fit
+ * its block counts 0: the device refuses it), *bad = 1 when the walk stopped at a block_size below 32.  The walk checks
+ * what it needs for its own safety and nothing else. */
+int64_t csh_bam_walk(const uint8_t *buf, int64_t n, int64_t from, int64_t max_records, uint32_t *offsets, int64_t *next,
+                     int64_t *text_bytes, int32_t *bad) {
+  int64_t at = from, found = 0, text = 0;
+  *bad = 0;
+  while (found < max_records && at + 4 <= n) {
+    const uint32_t block_size = csb_u32(buf + at);
+    if (block_size < CSB_MIN_BLOCK || block_size >= 0x80000000u) {
+      *bad = 1;
+      break;
+    }
+    if (at + 4 + (int64_t)block_size > n) break; /* incomplete: the caller carries it */
+    csb_shape_t s;
+    if (csb_shape(buf + at, block_size + 4u, &s) == CSB_OK) text += s.text_len;
+    offsets[found++] = (uint32_t)at;
+    at += 4 + (int64_t)block_size;
+  }
+  *next = at;
+  *text_bytes = text;
+  return found;
+}

@@ -302,7 +302,7 @@ def run_parent(argv: List[str], args, tp) -> Optional[dict]:
         return None
     for path in paths:
         container, first, _ = codec.sniff_input(path)
-        if container not in ("plain", "gzip") or first in (b">", b"#"):
+        if container not in ("plain", "gzip") or first[:1] in (b">", b"#"):
             logging.warning(f"--ranks {world} ignored: {path} is not a plain or gzip FASTQ file.")
             return None
     t0 = time.perf_counter()

@@ -479,7 +479,7 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
     from . import codec
     for name in args.input_file:  # the host parser reads plain and gzip FASTQ files, nothing else
         container, first, _ = codec.sniff_input(name) if name != "-" else ("stdin", b"", None)
-        if container not in ("plain", "gzip") or first in (b">", b"#"):
+        if container not in ("plain", "gzip") or first[:1] in (b">", b"#"):
             _fail(f"{name}: FASTA input, standard input and bzip2 / xz / zstandard files need the text path (CUTSEQ_TEXT_PATH unset).")
     chunk_reads = switches.int_value("CHUNK_READS")
     if chunk_reads is None:
@@ -563,6 +563,26 @@ def run_pipeline(args, tp: TrimPlan, shares=None) -> dict:
     return totals
 
 
+def _refuse_bam_forms(args) -> None:
+    """Unaligned BAM inputs (recognised by content) and what they do not combine with -- said before a device is touched.
+    (Standard input is sniffed by its reader, once; it meets the same refusals there.)"""
+    from . import codec
+    kinds = {}
+    for name in args.input_file:
+        if name != "-" and os.path.isfile(name):
+            container, first, _ = codec.sniff_input(name)
+            kinds[name] = codec.is_bam(container, first)
+    bams = [name for name, bam in kinds.items() if bam]
+    if not bams:
+        return
+    if len(bams) < len(kinds):
+        _fail("the two input files are in different formats (one BAM, one FASTQ or FASTA)")
+    if args.ranks > 1 or args.rank_spec:
+        _fail(f"{bams[0]}: only plain and gzip FASTQ files can be split between ranks")
+    if not switches.enabled("TEXT_PATH"):
+        _fail(f"{bams[0]}: BAM input needs the text path (CUTSEQ_TEXT_PATH unset): the record path is not extended to it.")
+
+
 def run_cutseq(args, argv=None):
     barcode = BarcodeConfig(args.adapter_scheme)
     settings = settings_from_args(args)
@@ -578,8 +598,9 @@ def run_cutseq(args, argv=None):
         if wanted:
             from . import codec
             for name in args.input_file:
-                if name != "-" and codec.sniff_input(name)[1] in (b">", b"#"):
+                if name != "-" and codec.sniff_input(name)[1][:1] in (b">", b"#"):
                     _fail(f"{option} needs qualities: {name} is a FASTA file.")
+    _refuse_bam_forms(args)
     totals = None
     if args.rank_spec:  # a child of --ranks: its share, its part files, its totals; the parent reports
         from . import ranks

@@ -9,7 +9,10 @@ order.  Counterpart of ``runner.run(pipeline, Progress(), outfiles)`` with ``mak
   TextReader    one thread per input file and one cutting loop with two memories: a source (page cache, several
                 ``pread`` calls at once; the inflate pool; BGZF spans through an inflater, CUTSEQ_GPU_INFLATE) appends
                 to ``_Pending``, which cuts behind newline 4 * chunk_reads and carries the rest -- in pinned memory or
-                in the inflater's (device memory) -> ``TextBlock(buf, nbytes, n_records)``
+                in the inflater's (device memory) -> ``TextBlock(buf, nbytes, n_records)``.  An unaligned BAM input
+                (by content) is the same loop with a second unit: ``_PendingRecords`` cuts in front of record
+                chunk_reads of the length-prefixed chain (``csh_bam_walk``); its blocks hold raw records, their offsets
+                and the size of the text the device expands them to (``cs_text_submit_bam``)
   TextWorker    one thread per GPU (a ``fanout.Worker``): a ``TrimEngine`` + ``TextEngine``, three batches in flight;
                 grows the row stride or the text capacity when a batch needs it
   run_text_pipeline   pairs the mates' blocks and hands them to ``fanout.run_ordered`` (round-robin deal, results back
@@ -80,19 +83,32 @@ def _host():
         L.csh_fasta_to_fastq.restype = C.c_int64
         L.csh_fasta_to_fastq.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.csh_bam_header.restype = C.c_int64
+        L.csh_bam_header.argtypes = [C.c_void_p, C.c_int64]
+        L.csh_bam_walk.restype = C.c_int64
+        L.csh_bam_walk.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64),
+                                   C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L._text_bound = True
     return L
 
 
 class TextBlock:
     """``n_records`` complete records in ``buf[:nbytes]`` (a pinned arena buffer) -- or, from a reader in device mode,
-    in the first ``nbytes`` of ``dbuf``, a buffer of the inflater ``owner`` (``buf`` is None then)."""
+    in the first ``nbytes`` of ``dbuf``, a buffer of the inflater ``owner`` (``buf`` is None then).  A block of a BAM
+    input holds raw BAM records: ``offsets`` (a pinned buffer read as uint32) has their starts and the end of the last
+    one, ``text_bytes`` is the size of the FASTQ text they expand to."""
 
-    __slots__ = ("buf", "nbytes", "n", "first_record", "dbuf", "owner")
+    __slots__ = ("buf", "nbytes", "n", "first_record", "dbuf", "owner", "offsets", "text_bytes")
 
-    def __init__(self, buf: Optional[np.ndarray], nbytes: int, n: int, first_record: int, dbuf=None, owner=None):
+    def __init__(self, buf: Optional[np.ndarray], nbytes: int, n: int, first_record: int, dbuf=None, owner=None,
+                 offsets: Optional[np.ndarray] = None, text_bytes: int = 0):
         self.buf, self.nbytes, self.n, self.first_record = buf, nbytes, n, first_record
         self.dbuf, self.owner = dbuf, owner
+        self.offsets, self.text_bytes = offsets, text_bytes
+
+    def text_size(self) -> int:
+        """Bytes of the text the block is (or becomes on the device): what sizes the slot."""
+        return self.text_bytes if self.offsets is not None else self.nbytes
 
     def text_address(self) -> int:
         """Where the text is: a host address, or a device address (``dbuf``)."""
@@ -102,6 +118,9 @@ class TextBlock:
         if self.buf is not None:
             fastq.PINNED.give(self.buf)
             self.buf = None
+        if self.offsets is not None:
+            fastq.PINNED.give(self.offsets)
+            self.offsets = None
         if self.dbuf is not None:
             self.owner.give(self.dbuf)
             self.dbuf = None
@@ -129,7 +148,11 @@ _HOST = _HostMemory()
 class _Pending:
     """The text behind the last block that went out: ``buf[:fill]``, a buffer of ``mem`` (:class:`_HostMemory` or an
     inflater), holds ``lines`` newlines; ``marks`` has one (offset, nbytes, newlines) per piece a source appended.
-    ``goal`` (the lines the loop is filling up to) and ``est`` are there for the sources to size their reads by."""
+    ``goal`` (the lines the loop is filling up to) and ``est`` are there for the sources to size their reads by.
+    The unit the loop counts and cuts by is the line, ``per_record`` of them to a record; :class:`_PendingRecords`
+    counts whole BAM records instead."""
+
+    per_record = 4
 
     def __init__(self, mem, chunk_reads: int):
         self.mem, self.chunk_reads = mem, chunk_reads
@@ -162,9 +185,13 @@ class _Pending:
         self.fill += nbytes
         self.lines += newlines
 
-    def cut(self, k: int):
-        """-> (buffer, cut): the text up to newline ``k`` leaves in its buffer, what is behind it is carried into a
-        fresh one.  ``marks`` say which piece holds the newline, and only that piece is searched for it."""
+    def refresh(self) -> None:
+        """The units in ``buf[:fill]`` are counted, up to ``goal`` (lines are, piece by piece, as they arrive)."""
+
+    def _cut_point(self, k: int):
+        """-> (the offset behind unit ``k``, what a block of this unit needs beyond its bytes -- lines: nothing); what
+        the pending keeps about its pieces is moved up to the cut.  ``marks`` say which piece holds the newline, and only
+        that piece is searched for it."""
         cum = 0
         for at, (off, nbytes, found) in enumerate(self.marks):
             if cum + found >= k:
@@ -172,13 +199,23 @@ class _Pending:
             cum += found
         cut = off + self.mem.after_kth_newline(self.buf, off, nbytes, k - cum)
         assert cum + found >= k and cut > 0
-        nxt = self.mem.take(max(self.buf.size, self.size()))
-        self.mem.copy(nxt, 0, self.buf, cut, self.fill - cut)
         # the piece the cut went through keeps its rest, the others move up
         self.marks = [(0, off + nbytes - cut, found - (k - cum))] + [(o - cut, n, f) for o, n, f in self.marks[at + 1:]]
+        return cut, None
+
+    def cut(self, k: int):
+        """-> (buffer, cut, extra): the text up to unit ``k`` (newline ``k``) leaves in its buffer, what is behind it is
+        carried into a fresh one.  ``extra``: :meth:`_cut_point`'s."""
+        cut, extra = self._cut_point(k)
+        nxt = self.mem.take(max(self.buf.size, self.size()))
+        self.mem.copy(nxt, 0, self.buf, cut, self.fill - cut)
         old, self.buf = self.buf, nxt
         self.fill, self.lines = self.fill - cut, self.lines - k
-        return old, cut
+        return old, cut, extra
+
+    def end_of_input(self, path: str):
+        """What is left when the source has ended -> ``_end_of_input``'s triple and the last block's ``extra``."""
+        return _end_of_input(memoryview(self.buf)[:self.fill], path) + (None,)
 
     def drop_lines(self, k: int) -> None:
         self.mem.give(self.cut(k)[0])
@@ -198,6 +235,90 @@ class _Pending:
         if self.buf is not None:
             self.mem.give(self.buf)
             self.buf = None
+
+
+class _PendingRecords(_Pending):
+    """:class:`_Pending` for an unaligned BAM input: the unit is the whole record (``per_record`` 1), ``lines`` counts
+    the records found behind the header.  Records are length-prefixed, so their starts are a serial chain:
+    ``csh_bam_walk`` follows it over what has arrived (:meth:`refresh`), never further than the loop's ``goal``, and notes
+    every start; a cut is the noted start of record ``k``.  Pieces need no marks."""
+
+    per_record = 1
+
+    def __init__(self, mem, chunk_reads: int, path: str):
+        super().__init__(mem, chunk_reads)
+        self.path = path
+        self.header = False   # the BAM header has been dropped from the front
+        self.records_out = 0  # records in the blocks that left (for messages)
+        self.walked = 0       # buf[:walked] is `lines` whole records
+        self.text = 0         # ... that expand to this much FASTQ text
+        self.offs = fastq.PINNED.take(4 * (chunk_reads + 1))
+
+    def added(self, nbytes: int, newlines: int) -> None:
+        self.fill += nbytes
+
+    def _skip_header(self) -> bool:
+        size = int(_host().csh_bam_header(self.buf.ctypes.data, self.fill))
+        if size == -1:
+            raise fastq.FastqFormatError(f"{self.path}: malformed BAM: the stream does not start with the magic 'BAM\\1'")
+        if size == -2:
+            raise fastq.FastqFormatError(f"{self.path}: malformed BAM: a negative length in the header")
+        if size == 0:
+            return False
+        self.mem.copy(self.buf, 0, self.buf, size, self.fill - size)  # (memmove: the ranges overlap)
+        self.fill -= size
+        self.header = True
+        return True
+
+    def refresh(self) -> None:
+        want = self.goal - self.lines
+        if want <= 0:
+            return
+        self.settle()  # (the chain is followed over bytes that have arrived)
+        if not self.header and not self._skip_header():
+            return
+        if self.fill >= 1 << 31:
+            raise ReadTooLong(f"{self.path}: a block of BAM records outgrew 2 GiB (smaller blocks: CUTSEQ_CHUNK_READS)", 0)
+        offs = self.offs.view(np.uint32)
+        nxt, text, bad = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        t0 = time.perf_counter()
+        found = int(_host().csh_bam_walk(self.buf.ctypes.data, self.fill, self.walked, want, offs[self.lines:].ctypes.data,
+                                         C.byref(nxt), C.byref(text), C.byref(bad)))
+        _tick("bam_walk", t0)
+        self.lines += found
+        self.walked, self.text = int(nxt.value), self.text + int(text.value)
+        if bad.value:
+            raise fastq.FastqFormatError(
+                f"{self.path}: malformed BAM: record {self.records_out + self.lines} has a block_size below 32")
+
+    def _block_extra(self, k: int):
+        """The offsets of the first ``k`` records and the end of the last one, in a buffer of their own."""
+        assert k == self.lines, "the walk stops at the goal: a cut takes every record found"
+        out = fastq.PINNED.take(4 * (k + 1))
+        offs = out.view(np.uint32)
+        offs[:k] = self.offs.view(np.uint32)[:k]
+        offs[k] = self.walked
+        return out, self.text
+
+    def _cut_point(self, k: int):
+        extra = self._block_extra(k)
+        cut, self.walked, self.text = self.walked, 0, 0
+        self.records_out += k
+        return cut, extra
+
+    def end_of_input(self, path: str):
+        if not self.header:
+            raise fastq.FastqFormatError(f"{path}: malformed BAM: the stream ends inside the header")
+        if self.walked < self.fill:
+            raise fastq.FastqFormatError(
+                f"{path}: malformed BAM: the stream ends inside record {self.records_out + self.lines}")
+        return self.fill, self.lines, False, (self._block_extra(self.lines) if self.lines else None)
+
+    def close(self) -> None:
+        super().close()
+        if self.offs is not None:
+            fastq.PINNED.give(self.offs)
+            self.offs = None
 
 
 def _copy_in(dst: int, text: np.ndarray, nbytes: int) -> None:
@@ -263,14 +384,16 @@ class TextReader(threading.Thread):
         # gzip and plain FASTQ files take the parallel paths; standard input ("-"), bzip2 / xz / zstandard files and
         # FASTA text come through a sequential reader (codec.StreamSource), FASTA re-shaped into four-line records.
         self.container, first, self._opener = codec.sniff_input(path)
-        self.fasta = first in (b">", b"#")  # (dnaio: a leading comment line means FASTA too)
+        self.fasta = first[:1] in (b">", b"#")  # (dnaio: a leading comment line means FASTA too)
+        # an unaligned BAM (a BGZF container whose text starts "BAM\1"): the same sources, records cut by their lengths
+        self.bam = codec.is_bam(self.container, first)
         self.sequential = path == "-" or self.container in ("bz2", "xz", "zst") or (self.fasta and self.container == "plain")
         self.gz = self.container == "gzip" and not self.sequential
-        if (self.sequential or self.fasta or (stop is not None and not self.gz)) and (
+        if (self.sequential or self.fasta or self.bam or (stop is not None and not self.gz)) and (
                 start or skip_lines or max_records is not None or stop is not None):
             raise ValueError(f"{path}: only plain and gzip FASTQ files can be split between ranks")
         self._make_inflater = None
-        if (inflater is not None and self.gz and not self.fasta and not interleaved and codec.libdeflate() is not None
+        if (inflater is not None and self.gz and not self.fasta and not self.bam and not interleaved and codec.libdeflate() is not None
                 and not (start or skip_lines or max_records is not None or stop is not None)):
             with open(path, "rb") as fh:
                 if codec._bgzf_block_size(fh.read(1 << 16), 0):
@@ -319,13 +442,20 @@ class TextReader(threading.Thread):
                 "has no partner.")
         return records // 2
 
-    def _block(self, mem, buf, nbytes: int, records: int, done: int) -> TextBlock:
-        """The block of ``records`` records behind the ``done`` records handed out so far, in a buffer of ``mem``."""
+    def _block(self, mem, buf, nbytes: int, records: int, done: int, extra=None) -> TextBlock:
+        """The block of ``records`` records behind the ``done`` records handed out so far, in a buffer of ``mem``.
+        ``extra``: a BAM block's (offsets, text bytes)."""
         if mem is not _HOST:
             return TextBlock(None, nbytes, records, done, dbuf=buf, owner=mem)
+        offsets, text_bytes = extra if extra is not None else (None, 0)
         if self.interleaved:
-            return TextBlock(buf, nbytes, self.pair_count(records, self.path), done // 2)
-        return TextBlock(buf, nbytes, records, done)
+            try:
+                return TextBlock(buf, nbytes, self.pair_count(records, self.path), done // 2, offsets=offsets, text_bytes=text_bytes)
+            except BaseException:
+                if offsets is not None:
+                    fastq.PINNED.give(offsets)
+                raise
+        return TextBlock(buf, nbytes, records, done, offsets=offsets, text_bytes=text_bytes)
 
     @staticmethod
     def _members_until(src, start: int, stop: int):
@@ -391,8 +521,9 @@ class TextReader(threading.Thread):
         sequential stream, FASTA re-shaped into four-line records --, copied in by the pool."""
         L = _host()
         if self.gz and not self.fasta:
-            src = codec.GzipSource(self.path, fastq._pool(), fastq.ARENA.take, fastq.ARENA.give,
-                                   post=lambda addr, nbytes: int(L.csh_count_newlines(addr, nbytes)))
+            # (a BAM's blocks hold no lines to count: its records are found once the bytes stand in a row)
+            count = None if self.bam else (lambda addr, nbytes: int(L.csh_count_newlines(addr, nbytes)))
+            src = codec.GzipSource(self.path, fastq._pool(), fastq.ARENA.take, fastq.ARENA.give, post=count)
             gen = src.blocks(pos) if self.stop_at is None else self._members_until(src, pos, self.stop_at)
             if pos >= src.size:  # (a BGZF run that went through the inflater was the whole file)
                 gen = iter(())
@@ -410,7 +541,9 @@ class TextReader(threading.Thread):
                     _count_inflate("host_blocks", 1)
                 pend.room(nbytes)
                 got = src.side(text)
-                if got is None:
+                if self.bam:
+                    got = 0
+                elif got is None:
                     got = int(L.csh_count_newlines(text.ctypes.data, nbytes))
                 pend.copies.append(fastq._pool().submit(_copy_in, pend.buf.ctypes.data + pend.fill, text, nbytes))
                 pend.added(nbytes, got)
@@ -475,14 +608,17 @@ class TextReader(threading.Thread):
         done, skip = 0, self.skip_lines
         left = self.max_records  # records still to hand out (None: everything)
 
+        per = pend.per_record  # units (lines; whole records of a BAM input) to a record
+
         def fill(goal: int) -> None:
             pend.goal = goal
+            pend.refresh()
             while pend.lines < goal and next(source, False):
-                pass
+                pend.refresh()
             pend.settle()
 
         while not self._halt and left != 0:
-            need = 4 * (self.chunk_reads if left is None else min(self.chunk_reads, left))
+            need = per * (self.chunk_reads if left is None else min(self.chunk_reads, left))
             if skip:  # (the share starts `skip` lines into its first gzip member)
                 fill(skip)
                 if pend.lines >= skip:
@@ -490,24 +626,24 @@ class TextReader(threading.Thread):
                     skip = 0
             fill(need)
             if pend.lines < need:  # the end of the input (a source that ends leaves the text in pinned memory)
-                end, records, newline = _end_of_input(memoryview(pend.buf)[:pend.fill], self.path)
+                end, records, newline, extra = pend.end_of_input(self.path)
                 if records and newline:
                     pend.room(1)
                     pend.buf[end - 1] = 0x0A
                 if records:
-                    block, pend.buf = self._block(_HOST, pend.buf, end, records, done), None
+                    block, pend.buf = self._block(_HOST, pend.buf, end, records, done, extra), None
                     if not self._put(block):
                         block.release()
                         return
                 break
-            # the block ends right behind newline number `need`
+            # the block ends right behind newline number `need` (in front of BAM record number `need`)
             t0 = time.perf_counter()
-            buf, cut = pend.cut(need)
-            block = self._block(pend.mem, buf, cut, need // 4, done)
-            done += need // 4
+            buf, cut, extra = pend.cut(need)
+            block = self._block(pend.mem, buf, cut, need // per, done, extra)
+            done += need // per
             if left is not None:
-                left -= need // 4
-            pend.est = max(64, cut // (need // 4) + 1)
+                left -= need // per
+            pend.est = max(64, cut // (need // per) + 1)
             _tick("cut+carry", t0)
             if not self._put(block):
                 block.release()
@@ -517,7 +653,7 @@ class TextReader(threading.Thread):
     def run(self):
         try:
             mem = self._make_inflater() if self._make_inflater is not None else _HOST
-            pend = _Pending(mem, self.chunk_reads)
+            pend = _PendingRecords(mem, self.chunk_reads, self.path) if self.bam else _Pending(mem, self.chunk_reads)
             source = self._bgzf_text(pend) if mem is not _HOST else self._host_text(pend, self.start_at)
             try:
                 self._cut_blocks(pend, source)
@@ -768,7 +904,7 @@ class TextWorker(fanout.Worker):
     def ensure(self, item):
         """The text engine, rebuilt for longer rows or bigger blocks -- after everything in flight came back."""
         b1, b2 = item
-        text_bytes = max(b1.nbytes, b2.nbytes if b2 is not None else 0)
+        text_bytes = max(b1.text_size(), b2.text_size() if b2 is not None else 0)
         stride = max(self.stride, self.want_stride)
         if self.text is not None and stride <= self.stride and text_bytes <= self.capacity:
             return
@@ -789,6 +925,10 @@ class TextWorker(fanout.Worker):
             self.text.submit_device(slot, b1.text_address(), b1.nbytes, b2.text_address() if b2 is not None else 0,
                                     b2.nbytes if b2 is not None else 0, b1.n)
             return item
+        if b1.offsets is not None:  # BAM records: the device expands them to the text (both mates are BAM or none is)
+            self.text.submit_bam(slot, b1.buf, b1.nbytes, b1.offsets, b2.buf if b2 is not None else None,
+                                 b2.nbytes if b2 is not None else 0, b2.offsets if b2 is not None else None, b1.n)
+            return item
         self.text.submit(slot, b1.buf, b1.nbytes, b2.buf if b2 is not None else None, b2.nbytes if b2 is not None else 0, b1.n)
         return item
 
@@ -796,7 +936,10 @@ class TextWorker(fanout.Worker):
         b1, b2 = item
         t0 = time.perf_counter()
         try:
-            res = self.text.wait(slot, first_record=b1.first_record)
+            # (a refused BAM record is named by its number in its file: an interleaved block's first record is 2 * its
+            # first pair; every other message counts as it does for FASTQ)
+            woven_bam = b1.offsets is not None and b2 is None and self.tp.paired
+            res = self.text.wait(slot, first_record=b1.first_record, bam_first_record=b1.first_record * (2 if woven_bam else 1))
             t0 = _tick("wait", t0)
         except ReadTooLong as exc:
             raise ReadTooLong(f"{exc} in records {b1.first_record + 1}..{b1.first_record + b1.n}", exc.longest)
@@ -971,6 +1114,8 @@ def run_text_pipeline(args, tp, devices, chunk_reads: int, shares=None) -> dict:
         r2 = TextReader(args.input_file[1], chunk_reads, **share[1]) if paired and not woven_in else None
         report.phase("readers started")
 
+        if r2 is not None and r1.bam != r2.bam:
+            raise fastq.FastqFormatError("the two input files are in different formats (one BAM, one FASTQ or FASTA)")
         if r2 is not None and r1.fasta != r2.fasta:
             raise fastq.FastqFormatError("the two input files are in different formats (one FASTA, one FASTQ)")
         if r1.fasta and tp.max_ee is not None:

@@ -29,6 +29,18 @@ class TextFormatError(ValueError):
         self.code, self.record = code, record
 
 
+# What a refused BAM record raises ({n}: the record's 0-based number in its file); one sentence per refusal.
+BAM_MESSAGES = {
+    abi.CS_TEXT_ERR_BAM_BLOCK_SIZE: "malformed BAM: record {n} has a block_size below 32",
+    abi.CS_TEXT_ERR_BAM_OVERRUN: "malformed BAM: name, cigar, bases and qualities of record {n} exceed its block_size",
+    abi.CS_TEXT_ERR_BAM_NAME: "malformed BAM: the read name of record {n} is empty or lacks its NUL",
+    abi.CS_TEXT_ERR_BAM_ALIGNED: "only unaligned BAM is supported: record {n} is aligned",
+    abi.CS_TEXT_ERR_BAM_NAME_LINE_END: "malformed BAM: a line end inside the read name of record {n}",
+    abi.CS_TEXT_ERR_BAM_NO_QUAL: "BAM record without qualities: record {n}",
+    abi.CS_TEXT_ERR_BAM_QUAL_RANGE: "malformed BAM: a quality above 93 in record {n}",
+}
+
+
 class InfoMismatch(RuntimeError):
     """``CS_TEXT_ERR_INFO_MISMATCH`` / ``CS_TEXT_ERR_INFO_OVERFLOW``: an engine fault, never the input's."""
 
@@ -145,9 +157,22 @@ class TextEngine:
         ``dtext2`` are device addresses (0: no such mate), complete when the call is made."""
         capi.check(self.L.cs_text_submit_device(self._h, slot, dtext1 or None, bytes1, dtext2 or None, bytes2, n_records))
 
-    def wait(self, slot: int, first_record: int = 0, names=("mate 1", "mate 2")) -> abi.cs_text_result:
+    def submit_bam(self, slot: int, bam1, bytes1: int, off1, bam2=None, bytes2: int = 0, off2=None,
+                   n_records: int = 0) -> None:
+        """:meth:`submit` for unaligned BAM records (``cs_text_submit_bam``): ``bam1`` / ``bam2`` hold whole records back
+        to back, ``off1`` / ``off2`` (uint32 arrays) their ``n_records + 1`` ascending offsets (``interleave_in``:
+        ``2 * n_records + 1`` in ``off1``); the device expands them to the text :meth:`submit` takes."""
+        if not hasattr(self.L, "cs_text_submit_bam"):
+            raise capi.HipUnavailable("this build of libcutseq_hip.so has no cs_text_submit_bam")
+        capi.check(self.L.cs_text_submit_bam(self._h, slot, _address(bam1), bytes1, _address(off1), _address(bam2) or None,
+                                             bytes2, _address(off2) or None, n_records))
+
+    def wait(self, slot: int, first_record: int = 0, names=("mate 1", "mate 2"),
+             bam_first_record: Optional[int] = None) -> abi.cs_text_result:
         """Blocks until the batch is formatted on the device.  Raises what the reference's reader would raise for a
-        bad record.  Reads longer than the rows are not an error: they took the long-read kernel (``res.n_long``)."""
+        bad record.  Reads longer than the rows are not an error: they took the long-read kernel (``res.n_long``).
+        ``bam_first_record``: the number in its file of the batch's first BAM record, where that is not
+        ``first_record`` (an interleaved text counts two records to a pair); a refused BAM record is named by it."""
         res = abi.cs_text_result()
         capi.check(self.L.cs_text_wait(self._h, slot, C.byref(res)))
         if res.error == abi.CS_TEXT_ERR_TOO_LONG:
@@ -164,6 +189,11 @@ class TextEngine:
             raise TextFormatError(res.error, first_record,
                                   f"the text block does not hold the announced number of records ({res.n_records} records, "
                                   f"{res.n_lines[0]} / {res.n_lines[1]} line ends)")
+        if (res.error & ~abi.CS_TEXT_ERR_BAM_MATE2) in BAM_MESSAGES:
+            record = (first_record if bam_first_record is None else bam_first_record) + res.error_record
+            mate = names[1 if res.error & abi.CS_TEXT_ERR_BAM_MATE2 else 0]
+            text = BAM_MESSAGES[res.error & ~abi.CS_TEXT_ERR_BAM_MATE2].format(n=record)
+            raise TextFormatError(res.error, record, f"{mate}: {text}")
         if res.error == abi.CS_TEXT_ERR_INFO_MISMATCH:
             raise InfoMismatch(f"--info-file: the match recorder and the trimming kernels disagree on record "
                                f"{first_record + res.error_record + 1}; no table is written for a batch that "

@@ -439,9 +439,20 @@ enum {
   CS_TEXT_ERR_INFO_MISMATCH = 5, /* cs_text_params.info: the match recorder's final interval or flags of record
                                    `error_record` differ from what the trimming kernels produced: an engine fault,
                                    reported instead of a table that contradicts the records                          */
-  CS_TEXT_ERR_INFO_OVERFLOW = 6  /* cs_text_params.info: the table of the batch is larger than the bound cs_text_create
+  CS_TEXT_ERR_INFO_OVERFLOW = 6, /* cs_text_params.info: the table of the batch is larger than the bound cs_text_create
                                    derived for it (an engine fault too: the bound covers every possible table); nothing
                                    of it was written                                                                 */
+  /* cs_text_submit_bam: BAM record `error_record` (counted in its text; an interleaved engine: 2r + m) is refused.
+   * The values are the CSB_ERR_* of include/cutseq_bam.h, tested in this order; CS_TEXT_ERR_BAM_MATE2 is set on top
+   * when the record is one of bam2's. */
+  CS_TEXT_ERR_BAM_BLOCK_SIZE = 16,    /* block_size below 32, or beyond the bytes its offsets give the record          */
+  CS_TEXT_ERR_BAM_OVERRUN = 17,       /* fixed part, name, cigar, bases and qualities exceed block_size                */
+  CS_TEXT_ERR_BAM_NAME = 18,          /* l_read_name == 0 or no NUL at the name's end                                  */
+  CS_TEXT_ERR_BAM_ALIGNED = 19,       /* flag bit 0x4 not set: an aligned record                                       */
+  CS_TEXT_ERR_BAM_NAME_LINE_END = 20, /* '\n' or '\r' inside the name                                                  */
+  CS_TEXT_ERR_BAM_NO_QUAL = 21,       /* l_seq > 0 and qual[0] == 0xFF                                                 */
+  CS_TEXT_ERR_BAM_QUAL_RANGE = 22,    /* a quality above 93                                                            */
+  CS_TEXT_ERR_BAM_MATE2 = 0x40
 };
 
 /* cs_text_params.info: cutadapt's --info-file for read 1 (a TODO of the reference, cutseq/run.py "report info"):
@@ -630,6 +641,22 @@ int cs_copy_on_device(int device, void *dst, const void *src, size_t bytes);
  * may be passed as it is.) */
 int cs_text_submit_device(cs_text *t, uint32_t slot, const void *dtext1, uint64_t bytes1, const void *dtext2,
                           uint64_t bytes2, uint32_t n_records);
+
+/* ---- unaligned BAM records, expanded to FASTQ text on the device ---------------------------------------------------
+ * cs_text_submit for record bytes: bamM holds whole BAM records (block_size and block, include/cutseq_bam.h) back to
+ * back, offM[r] is where record r starts and offM[n] where the last one ends -- n_records + 1 entries, ascending; for an
+ * interleaved engine, CS_INTERLEAVE_IN, 2 * n_records + 1 entries in bam1 / off1, mate 1 and mate 2 alternating, and
+ * bam2 / off2 NULL.  Both are host memory (pinned for speed) and stay untouched until cs_text_wait returns.  The call
+ * uploads them, three launches per text (bam_sizes, text_scan_blocks, bam_expand: bam_kernels.hip.inc) write
+ *     @<read_name>\n<l_seq letters of "=ACMGRSVTWYHKDBN">\n+\n<qual + 33>\n
+ * per record into the slot's text buffer, and from there on it is cs_text_submit: the same kernels, results, errors,
+ * slots and lifetime rules, interleave, rename, info, compress and the too-long route included.  Tags, cigar, mapq, bin
+ * and positions are not read.  A record the device refuses (CS_TEXT_ERR_BAM_*) ends the batch like any reader error.
+ * CS_ERR_ARG, with nothing launched: offsets that descend or leave bytesM, a record of less than 36 bytes, records that
+ * expand to more text than max_text_bytes.  The device staging for records and offsets is allocated by the first such
+ * call on a slot (and again when a batch brings more bytes than it holds); a cs_text that never gets one has none. */
+int cs_text_submit_bam(cs_text *t, uint32_t slot, const void *bam1, uint64_t bytes1, const uint32_t *off1, const void *bam2,
+                       uint64_t bytes2, const uint32_t *off2, uint32_t n_records);
 
 /* The device twin of the host library's csh_after_kth_newline: *offset = the offset behind newline number k of
  * dtext[0 .. nbytes) (device memory on `device`), 0 for k < 1, -1 when the text holds fewer than k.  Blocks. */

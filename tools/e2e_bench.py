@@ -7,6 +7,8 @@
 the bytes of the output files (``--extra='-t 16 --bgzf'`` against ``--extra='-t 16'``: profiles/bgzf_out_ab.log).
 ``--forms bgzf_to_gz`` (only when named) adds BGZF input: the same records bgzip-style, read with and without
 ``CUTSEQ_GPU_INFLATE=1`` (the caller sets it), once cold and once warm.
+``--forms bam_to_gz`` (only when named) adds unaligned BAM input: the same records as R1.bam + R2.bam, written by the
+tests' BAM rule in BGZF blocks of 65 280 bytes at zlib level 6, once cold and once warm (profiles/bam_input_ab.log).
 
 Writes a synthetic paired data set once (plain text and multi-member gzip), then runs
 ``cutseq_amd.run.main`` on it: plain -> plain twice (the second run has warm buffers and page cache),
@@ -32,6 +34,8 @@ sys.path.insert(0, str(ROOT))
 
 
 def main():
+    if sys.argv[1:2] == ["--write-ubam"]:  # the child process of the bam_to_gz form: FASTQ FASTQ BAM BAM
+        return write_ubam(sys.argv[2:4], sys.argv[4:6])
     ap = argparse.ArgumentParser()
     ap.add_argument("pairs", type=int, nargs="?", default=8_000_000)
     ap.add_argument("workdir", nargs="?", default="/dev/shm/cutseq_e2e")
@@ -72,9 +76,19 @@ def main():
         src.close()
     out["gunzip_s"] = round(time.perf_counter() - t0, 2)
 
+    plain_in = [str(work / "plain_R1.fastq"), str(work / "plain_R2.fastq")]
+    bam_in = [str(work / f"ubam_R{m}.bam") for m in (1, 2)]
+    if opts.forms and "bam_to_gz" in opts.forms and not (opts.keep and all(Path(p).exists() for p in bam_in)):
+        # in a process of its own, like make_fastq.py, and before this one runs anything: the writer's process pool must
+        # not be forked from a process that holds a GPU
+        t0 = time.perf_counter()
+        subprocess.run([sys.executable, str(Path(__file__).resolve()), "--write-ubam", *plain_in, *bam_in], check=True)
+        out["make_bam_s"] = round(time.perf_counter() - t0, 2)
+
     def run(tag, inputs, outputs):
         if opts.forms and tag not in opts.forms and not (tag == "plain_cold" and "plain_warm" in opts.forms) \
                 and not (tag == "bgzf_to_gz_warm" and "bgzf_to_gz" in opts.forms) \
+                and not (tag == "bam_to_gz_warm" and "bam_to_gz" in opts.forms) \
                 and not (tag == "plain_to_gz" and "plain_to_gz_warm" in opts.forms):
             return
         for old in work.glob("o[12].fastq"), work.glob("s[12].fastq"), work.glob("gzout_*"):
@@ -90,7 +104,6 @@ def main():
         out[tag] = {"seconds": round(dt, 3), "M_pairs_per_s": round(n / dt / 1e6, 3)}
 
 
-    plain_in = [str(work / "plain_R1.fastq"), str(work / "plain_R2.fastq")]
     plain_out = ["-o", str(work / "o1.fastq"), str(work / "o2.fastq"), "-s", str(work / "s1.fastq"), str(work / "s2.fastq")]
     run("plain_cold", plain_in, plain_out)
     run("plain_warm", plain_in, plain_out)
@@ -109,6 +122,10 @@ def main():
             write_bgzf(plain_in, bgzf_in)
         run("bgzf_to_gz", bgzf_in, ["-O", str(work / "gzout")])
         run("bgzf_to_gz_warm", bgzf_in, ["-O", str(work / "gzout")])
+    if opts.forms and "bam_to_gz" in opts.forms:
+        out["bam_bytes"] = [Path(p).stat().st_size for p in bam_in]
+        run("bam_to_gz", bam_in, ["-O", str(work / "gzout")])
+        run("bam_to_gz_warm", bam_in, ["-O", str(work / "gzout")])
     # the usual sequencer output: ONE gzip member per file (gzip -1 of the first half of the records), which no
     # reader can enter in the middle
     n_single = n // 2
@@ -148,6 +165,48 @@ def write_bgzf(sources, targets, level=6, piece=64 * 65280):
                     if not data:
                         break
                 fout.write(bgzf_rule.EOF_MARKER)
+
+
+def _bam_records(lines):
+    """Pool job of write_ubam: the four-line records ``lines`` as BAM records, back to back."""
+    import bam_rule
+    minus33 = bytes((i - 33) & 0xFF for i in range(256))
+    return b"".join(bam_rule.record_bytes(bam_rule.Rec(lines[i][1:-1], lines[i + 1][:-1], lines[i + 3][:-1].translate(minus33)))
+                    for i in range(0, len(lines), 4))
+
+
+def write_ubam(sources, targets, level=6, piece=64 * 65280, records=50_000):
+    """Plain FASTQ files as unaligned BAM by tests/bam_rule.py: the records are built by a pool of processes, the stream is
+    cut into BGZF blocks of 65 280 bytes wherever they fall, as samtools does, and compressed by a pool of threads; at
+    most 16 of each.  Runs in a process of its own (``--write-ubam``) that never opens a GPU."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import itertools
+    import bam_rule
+    from concurrent.futures import ProcessPoolExecutor, ThreadPoolExecutor
+    cpus = min(16, len(os.sched_getaffinity(0)))
+    with ProcessPoolExecutor(cpus) as procs, ThreadPoolExecutor(cpus) as threads:
+        for src, dst in zip(sources, targets):
+            with open(src, "rb") as fin, open(dst, "wb") as fout:
+                stream, blocks, jobs = bytearray(bam_rule.header_bytes(b"@HD\tVN:1.6\tSO:unsorted\n")), [], []
+
+                def drain(everything):
+                    while len(stream) >= piece or (everything and stream):
+                        blocks.append(threads.submit(bam_rule.bgzf_rule.bgzf, bytes(stream[:piece]), 65280, level))
+                        del stream[:piece]
+                    while blocks and (everything or len(blocks) > 4 * cpus):
+                        fout.write(blocks.pop(0).result())
+
+                while True:
+                    lines = list(itertools.islice(fin, 4 * records))
+                    if lines:
+                        jobs.append(procs.submit(_bam_records, lines))
+                    while jobs and (not lines or len(jobs) > 2 * cpus):
+                        stream += jobs.pop(0).result()
+                        drain(False)
+                    if not lines:
+                        break
+                drain(True)
+                fout.write(bam_rule.bgzf_rule.EOF_MARKER)
 
 
 def finish(work, out, keep):
